@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark: VO frames/s on the BASELINE.json config-2 workload, through the device-resident frame loop.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: one rank per GPU under torch.distributed.run; started that way by the driver, or by this script
    itself when it is called directly with --gpus N)
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline, and what the timed steps' own
+records say about them (`loop`, `chain_us`).  --full adds everything else the line used to carry, each measured by a
+run of its own: the whole first pass against the stream's ground truth and against the CPU oracle of the loop (which
+is also the CPU baseline), the all-kernel event profile and the roofline of the dominant kernel (HIP events around
+it inside the timed region), the API and host-memory legs, and the in-line detector-every-frame and 16-sequence legs.
+--dump-outputs DIR: after the timed steps, what the last one handed its caller (every sequence's step record and the
+Features / State the loop carries on) as DIR/<name>.npy, float64; the inputs depend on the arguments alone.
 
 The stream is SURVEY.md 8d's: 100 frames of a strictly forward drive (0.8 m per frame, src/main.py:248), all resident
 in HBM, walked 2 -> 99 pass after pass.  At the end of a pass the look-ahead is drained and the state the bootstrap
@@ -317,33 +325,30 @@ def cfg3_main(args, tracker="sift"):
     walker = Walker(pipe, N_FRAMES)
     first_pass = []
     ORACLE_FRAMES = 3
-    walker.run(ORACLE_FRAMES, lookahead=False, on_step=lambda b, rs: first_pass.append((b, rs[0])))
-    first_state = pipe.get_state()
-    walker.run(N_FRAMES - 1 - PASS_START - ORACLE_FRAMES, lookahead=False, on_step=lambda b, rs: first_pass.append((b, rs[0])))
-    walker.run(args.warmup)
-    ctx.prof_enable(-1)
-    pipe.prof_reset()
-    walker.run(8)
     per = {}
-    for kid in range(_native.K_COUNT):
-        ms, n = pipe.prof_read(kid)
-        if n:
-            per[ctx.kernel_name(kid)] = ms / n * 1e3
-    ctx.prof_disable()
+    if args.full:
+        walker.run(ORACLE_FRAMES, lookahead=False, on_step=lambda b, rs: first_pass.append((b, rs[0])))
+        first_state = pipe.get_state()
+        walker.run(N_FRAMES - 1 - PASS_START - ORACLE_FRAMES, lookahead=False, on_step=lambda b, rs: first_pass.append((b, rs[0])))
+    walker.run(args.warmup)
+    if args.full:
+        ctx.prof_enable(-1)
+        pipe.prof_reset()
+        walker.run(8)
+        for kid in range(_native.K_COUNT):
+            ms, n = pipe.prof_read(kid)
+            if n:
+                per[ctx.kernel_name(kid)] = ms / n * 1e3
+        ctx.prof_disable()
     recs = []
     ctx.sync()
     t0 = time.perf_counter()
     walker.run(args.steps, on_step=lambda b, rs: recs.extend(rs))
     ctx.sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe, recs[-1:])
     st = loop_stats(recs)
-    # ground truth over the first pass; oracle of the same loop on its first frames (also the CPU baseline)
-    scale = 2 * synthetic.STEP_Z / max(np.linalg.norm(state.curr_pose[:3, 3]), 1e-12)
-    gt_err = []
-    for b, r in first_pass:
-        Twc = r.pose_world_cam()
-        gt = np.linalg.inv(stream.T_world_cam(0)) @ stream.T_world_cam(b)
-        gt_err.append((float(np.linalg.norm(Twc[:3, :3] - gt[:3, :3])), float(np.linalg.norm(scale * Twc[:3, 3] - gt[:3, 3]))))
     out = {"metric": "VO frames/sec at 1376x1241, 2k keypoints; pose err vs reference", "value": round(args.steps / dt, 2),
            "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
@@ -360,13 +365,21 @@ def cfg3_main(args, tracker="sift"):
                                    "bookkeeping, candidate DLT; device-resident (vo_pipeline tracker_mode = harris)") % (W, H, N_FRAMES, CAP, HYP),
                       "keypoints": CAP, "frames_resident": N_FRAMES, "frame_lookahead": 1,
                       "passes_started_in_timed_region": walker.passes},
-           "loop": dict(st, bootstrap_landmarks=int((feats.state == 2).sum())),
-           "per_kernel_us": {k: round(v, 1) for k, v in sorted(per.items())},
-           "pose_err_vs_ground_truth": {"rot_fro_median": float(np.median([e[0] for e in gt_err])),
-                                        "trans_m_median": float(np.median([e[1] for e in gt_err])),
-                                        "trans_m_last": round(gt_err[-1][1], 3),
-                                        "trans_m_every_8th_frame": [round(e[1], 3) for e in gt_err[::8]],
-                                        "path_m": round((N_FRAMES - 1 - PASS_START) * synthetic.STEP_Z, 1), "frames": len(gt_err)}}
+           "loop": dict(st, bootstrap_landmarks=int((feats.state == 2).sum()))}
+    if args.full:
+        # ground truth over the first pass; oracle of the same loop on its first frames (also the CPU baseline)
+        scale = 2 * synthetic.STEP_Z / max(np.linalg.norm(state.curr_pose[:3, 3]), 1e-12)
+        gt_err = []
+        for b, r in first_pass:
+            Twc = r.pose_world_cam()
+            gt = np.linalg.inv(stream.T_world_cam(0)) @ stream.T_world_cam(b)
+            gt_err.append((float(np.linalg.norm(Twc[:3, :3] - gt[:3, :3])), float(np.linalg.norm(scale * Twc[:3, 3] - gt[:3, 3]))))
+        out["per_kernel_us"] = {k: round(v, 1) for k, v in sorted(per.items())}
+        out["pose_err_vs_ground_truth"] = {"rot_fro_median": float(np.median([e[0] for e in gt_err])),
+                                           "trans_m_median": float(np.median([e[1] for e in gt_err])),
+                                           "trans_m_last": round(gt_err[-1][1], 3),
+                                           "trans_m_every_8th_frame": [round(e[1], 3) for e in gt_err[::8]],
+                                           "path_m": round((N_FRAMES - 1 - PASS_START) * synthetic.STEP_Z, 1), "frames": len(gt_err)}
     ss_us = per.get("sift_scale_space")
     if ss_us:
         ss_bytes = (4 * H * W * 4) * (4.0 / 3.0) * 22
@@ -382,7 +395,7 @@ def cfg3_main(args, tracker="sift"):
                           "avg_launch_us": round(m_us, 1), "ops": flops, "achieved": round(flops / (m_us * 1e-6) / 1e12, 2),
                           "peak": 5000.0, "unit": "TOP/s", "frac": round(flops / (m_us * 1e-6) / 1e12 / 5000.0, 5),
                           "note": "2000 x 2000 x 128: 1 GOP -- latency-bound, not MFMA-bound"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from pipeline_oracle import OracleLoop
         orc = OracleLoop(stream, CAP, WIN, MAX_LEVEL, refine_iters=REFINE_ITERS, tracker=tracker)
@@ -540,6 +553,45 @@ def loop_stats(records):
             "refine_steps_median": float(np.median([r.refine_iterations for r in records]))}
 
 
+DUMP_LIMIT = (64 << 20) - (64 << 10)      # array bytes: 64 MB in all with the .npy headers
+STEP_FIELDS = ("R", "t", "R_refined", "t_refined", "T_wc", "refine_cost", "n_features_in", "n_tracked", "n_triangulated",
+               "n_inliers", "best_index", "hyp_valid", "ransac_iterations", "draws_consumed", "refine_iterations", "redetected",
+               "n_candidates", "n_dropped", "n_landmarks", "fault", "recovered", "detector_ran")
+STATE_ROWS = {"keypoints": 2, "state": 1, "candidate_mask": 1, "landmarks": 3, "tracks": 2, "poses": 16}   # values per row
+# rows that hold NaN where the loop has no value (a feature without a landmark, a track or a start pose: the
+# reference's own "none", state.hip / refine.hip write it so); dumped as 0 with a <name>_valid row of 1 / 0 beside them
+NO_VALUE_ROWS = ("landmarks", "tracks", "poses")
+
+
+def dump_outputs(d, pipe, last):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files in `d`: step_<field> (one row
+    per sequence) from the step records `last` (device clock stamps left out: they are times, not results), and the
+    Features / State every sequence carries into the next step -- state_<array> with the sequences' rows one after the
+    other, state_n their counts; the NaN "none" of NO_VALUE_ROWS as 0 with state_<array>_valid.  Above DUMP_LIMIT bytes
+    the state rows are a fixed, seeded sample (state_rows: their indices)."""
+    out = {"step_" + k: np.array([np.array(getattr(r, k), dtype=np.float64) for r in last]) for k in STEP_FIELDS}
+    st = [pipe.get_state(seq=q) for q in range(len(last))]
+    out["state_n"] = np.array([s["n"] for s in st], dtype=np.float64)
+    for k in ("curr_pose", "prev_pose", "n_iterations", "outlier_ratio", "num_features"):
+        out["state_" + k] = np.array([s[k] for s in st], dtype=np.float64)
+    rows = {k: np.concatenate([s[k].reshape(s["n"], w) for s in st]).astype(np.float64) for k, w in STATE_ROWS.items()}
+    for k in NO_VALUE_ROWS:
+        finite = np.isfinite(rows[k])
+        rows[k + "_valid"] = finite.all(axis=1, keepdims=True).astype(np.float64)
+        rows[k] = np.where(finite, rows[k], 0.0)
+    fixed = sum(a.nbytes for a in out.values())
+    per_row = 8 * (sum(STATE_ROWS.values()) + len(NO_VALUE_ROWS) + 1)
+    n = len(rows["keypoints"])
+    if fixed + n * per_row > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(0).choice(n, (DUMP_LIMIT - fixed) // per_row, replace=False))
+        rows = {k: a[keep] for k, a in rows.items()}
+        out["state_rows"] = keep.astype(np.float64)
+    out.update(("state_" + k, a) for k, a in rows.items())
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def timed_leg(ctx, pipe, S, warm, steps):
     """warm untimed + `steps` timed steps of `pipe` (look-ahead, seams included); the leg's dict."""
     w = Walker(pipe, N_FRAMES)
@@ -583,12 +635,17 @@ def main():
     _Stdout.isolate()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api", action="store_true", help="skip the drop-in API frames/s leg")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 2000; cfg3 / harris: 150)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 200; cfg3 / harris: 10)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the ground-truth and oracle comparisons, the CPU baseline, the per-kernel profile and roofline, "
+                         "the API legs and the in-line legs (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the oracle / CPU-baseline leg")
+    ap.add_argument("--no-api", action="store_true", help="--full without the drop-in API frames/s leg")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the in-line detector-every-frame and 16-sequences legs (profiling runs of the headline alone)")
+                    help="--full without the in-line detector-every-frame and 16-sequences legs")
     ap.add_argument("--no-lookahead", dest="lookahead", action="store_false",
                     help="one blocking vo_pipeline_step per frame instead of submitting frame k+1 before "
                          "collecting frame k (vo_pipeline_submit / _collect)")
@@ -598,9 +655,14 @@ def main():
     ap.add_argument("--exchange", action="store_true",
                     help="run the all-gather of {pose, landmarks} records even on one GPU (always on for --gpus > 1)")
     args = ap.parse_args()
-    if CONFIG in ("cfg3", "harris"):
-        if args.steps == 2000:
-            args.steps, args.warmup = 150, 10
+    cfg3 = CONFIG in ("cfg3", "harris")
+    if args.steps is None:
+        args.steps = 150 if cfg3 else 2000
+    if args.warmup is None:
+        args.warmup = 10 if cfg3 else 200
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if cfg3:
         return cfg3_main(args, "sift" if CONFIG == "cfg3" else "harris")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -611,7 +673,8 @@ def main():
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     S = max(1, args.sequences)
-    legs = world == 1 and not args.no_legs and CONFIG == "cfg2"
+    full = args.full
+    legs = full and world == 1 and not args.no_legs and CONFIG == "cfg2"
     # the frames first, in worker processes, before this process touches the GPU: every sequence of every rank is its
     # own scene (its own texture seed); the 16-sequences leg gets 16 more
     from vo import synthetic
@@ -691,13 +754,15 @@ def main():
         ctx.sync()
         torch.cuda.synchronize()
 
-    # ---- untimed: the whole first pass, blocking.  Its first frames are kept for the parity / CPU-baseline leg, all of
-    # it for the comparison with the analytic ground truth ----
+    # ---- --full, untimed: the whole first pass, blocking.  Its first frames are kept for the parity / CPU-baseline leg,
+    # all of it for the comparison with the analytic ground truth.  With the exchange it also runs in a plain run: it
+    # puts the pipeline's streams on their hardware queues before RCCL's (below) ----
     ORACLE_FRAMES = 4
-    first = run(ORACLE_FRAMES, record=True, lookahead=False)
-    first_state = pipe.get_state()
-    first_pass = first + run(N_FRAMES - 1 - PASS_START - ORACLE_FRAMES, record=True, lookahead=False)
-    ctx.sync()
+    if full or want_exchange:
+        first = run(ORACLE_FRAMES, record=True, lookahead=False)
+        first_state = pipe.get_state()
+        first_pass = first + run(N_FRAMES - 1 - PASS_START - ORACLE_FRAMES, record=True, lookahead=False)
+        ctx.sync()
     # The process group comes up only now: HIP spreads streams over its hardware queues in the order they first run,
     # and the pipeline's main stream should not end up sharing a queue with RCCL's (measured in round 1).
     if want_exchange:
@@ -707,98 +772,76 @@ def main():
         torch.cuda.set_stream(comm)      # the collectives are issued from this stream; the pipeline has its own
         exchange = True
 
-    # untimed: warmup, and one all-kernel event profile to find the dominant kernel
+    # untimed: warmup, and (--full) one all-kernel event profile to find the dominant kernel
     run(args.warmup)
-    ctx.prof_enable(-1)
-    pipe.prof_reset()
-    run(16)
-    per_kernel = {}
-    for kid in range(_native.K_COUNT):
-        ms, n = pipe.prof_read(kid)
-        if n:
-            per_kernel[ctx.kernel_name(kid)] = (ms, n)
-    ctx.prof_disable()
-    dom_name = max(per_kernel, key=lambda k: per_kernel[k][0])
-    dom_id = [k for k in range(_native.K_COUNT) if ctx.kernel_name(k) == dom_name][0]
+    if full:
+        ctx.prof_enable(-1)
+        pipe.prof_reset()
+        run(16)
+        per_kernel = {}
+        for kid in range(_native.K_COUNT):
+            ms, n = pipe.prof_read(kid)
+            if n:
+                per_kernel[ctx.kernel_name(kid)] = (ms, n)
+        ctx.prof_disable()
+        dom_name = max(per_kernel, key=lambda k: per_kernel[k][0])
+        dom_id = [k for k in range(_native.K_COUNT) if ctx.kernel_name(k) == dom_name][0]
 
-    # timed region: exactly K steps, events only around the dominant kernel (every PROF_EVERY-th launch: an event
-    # pair costs the stream ~5 us, bracketing every launch would slow the step it measures)
-    pipe.prof_reset()
-    ctx.prof_set_sampling(PROF_EVERY)
-    ctx.prof_enable(dom_id)
+        # events only around the dominant kernel in the timed region (every PROF_EVERY-th launch: an event pair costs
+        # the stream ~5 us, bracketing every launch would slow the step it measures)
+        pipe.prof_reset()
+        ctx.prof_set_sampling(PROF_EVERY)
+        ctx.prof_enable(dom_id)
+
+    # timed region: exactly K steps
     passes0 = walker.passes
     fence()
     t0 = time.perf_counter()
     timed = run(args.steps, record=True)
     fence()
     dt = time.perf_counter() - t0
-    dom_ms, dom_n = pipe.prof_read(dom_id)
-    ctx.prof_disable()
-    ctx.prof_set_sampling(1)
+    if full:
+        dom_ms, dom_n = pipe.prof_read(dom_id)
+        ctx.prof_disable()
+        ctx.prof_set_sampling(1)
 
     dt_t = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt_max = float(dt_t.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe, timed[-1][1])
+
     if rank == 0:
         every = [r for _, rs in timed for r in rs]           # all sequences' records
         res = [rs[0] for _, rs in timed]                     # sequence 0: chain stamps
         lstats = loop_stats(every)
-        n_in, n_trk, n_tri = lstats["features_in_median"], lstats["tracked_median"], lstats["landmarks_p3p_median"]
-        avg_us = dom_ms / max(dom_n, 1) * 1e3
-
-        def abytes(k):                                       # one launch processes all S sequences
-            v = algorithmic_bytes(k, n_in, n_trk, n_tri)
-            return None if v is None else v * S
-
-        ab = abytes(dom_name)
-        roof = {"bound": "hbm", "kernel": KERNEL_LABEL.get(dom_name, dom_name), "avg_launch_us": round(avg_us, 3), "launches": dom_n,
-                "algorithmic_bytes_per_launch": ab, "sequences_per_launch": S, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "traffic": pmc_traffic(dom_name) if S == 1 else None}
-        if ab and avg_us > 0:
-            ach = ab / (avg_us * 1e-6) / 1e9
-            roof["achieved"] = round(ach, 2)
-            roof["frac"] = round(ach / HBM_PEAK_GBS, 5)
-        else:
-            roof["achieved"] = None
-            roof["frac"] = None
-
-        def us(k):
-            return per_kernel[k][0] / per_kernel[k][1] * 1e3
-
-        # pose against the analytic ground truth of the stream over the whole first pass: the bootstrap fixes the unit of
-        # length (|t| = 1 between frames 0 and 2, 1.6 m apart), positions compared after that one scale
-        scale = 2 * synthetic.STEP_Z / max(np.linalg.norm(state.curr_pose[:3, 3]), 1e-12)
-        gt_err = []
-        for b, rs in first_pass:
-            r = rs[0]
-            Twc = r.pose_world_cam()
-            gt = np.linalg.inv(stream.T_world_cam(0)) @ stream.T_world_cam(b)
-            gt_err.append((float(np.linalg.norm(Twc[:3, :3] - gt[:3, :3])), float(np.linalg.norm(scale * Twc[:3, 3] - gt[:3, 3]))))
         # device clock (100 MHz) stamps the kernels of the chain leave in every record: where a step's time goes
         # (steps right behind a seam start from a drained pipeline: their period is the seam's, not the chain's)
         ts = np.array([[r.ts[k] for k in range(8)] for r in res], dtype=np.float64) * 1e-2          # us
         period = np.diff(ts[:, 1])
         seam = np.array([timed[i + 1][0] == PASS_START + 1 for i in range(len(timed) - 1)], dtype=bool)
         inpass = period[~seam] if (~seam).any() else period
-        chain = {"tracker_start_to_regroup_start": float(np.median(ts[:, 1] - ts[:, 0])),
-                 "regroup_to_hypotheses": float(np.median(ts[:, 2] - ts[:, 1])),
-                 "hypotheses_to_pose": float(np.median(ts[:, 3] - ts[:, 2])),
-                 "pose_to_landmarks": float(np.median(ts[:, 4] - ts[:, 3])),
-                 "landmarks_to_record": float(np.median(ts[:, 5] - ts[:, 4])),
-                 "record_to_next_regroup": float(np.median((ts[1:, 1] - ts[:-1, 5])[~seam])) if (~seam).any() else None,
-                 "regroup_to_next_tracker_start": float(np.median((ts[1:, 0] - ts[:-1, 1])[~seam])) if (~seam).any() else None,
-                 "step_period": float(np.median(inpass)),
-                 "step_period_mean": float(np.mean(inpass)),
-                 "step_period_percentiles_10_50_90_99": [float(v) for v in np.percentile(inpass, [10, 50, 90, 99])],
-                 "seam_period": [float(v) for v in period[seam]][:8],
-                 "redetect_step_period_median": (float(np.median([period[i] for i in range(len(period)) if res[i + 1].redetected and not seam[i]]))
-                                                 if any(res[i + 1].redetected and not seam[i] for i in range(len(period))) else None),
-                 "unit": "us, medians over the timed steps, from wall_clock64() stamps of each kernel's first work item"}
-        if os.environ.get("VO_POSE_STAMPS"):
-            chain["pose_kernel_replay_refine_candidates"] = [float(np.median(ts[:, 6] - ts[:, 3])), float(np.median(ts[:, 7] - ts[:, 6])),
-                                                             float(np.median(ts[:, 4] - ts[:, 7]))]
+        chain = None                                         # (one timed step: no period)
+        if len(period):
+            chain = {"tracker_start_to_regroup_start": float(np.median(ts[:, 1] - ts[:, 0])),
+                     "regroup_to_hypotheses": float(np.median(ts[:, 2] - ts[:, 1])),
+                     "hypotheses_to_pose": float(np.median(ts[:, 3] - ts[:, 2])),
+                     "pose_to_landmarks": float(np.median(ts[:, 4] - ts[:, 3])),
+                     "landmarks_to_record": float(np.median(ts[:, 5] - ts[:, 4])),
+                     "record_to_next_regroup": float(np.median((ts[1:, 1] - ts[:-1, 5])[~seam])) if (~seam).any() else None,
+                     "regroup_to_next_tracker_start": float(np.median((ts[1:, 0] - ts[:-1, 1])[~seam])) if (~seam).any() else None,
+                     "step_period": float(np.median(inpass)),
+                     "step_period_mean": float(np.mean(inpass)),
+                     "step_period_percentiles_10_50_90_99": [float(v) for v in np.percentile(inpass, [10, 50, 90, 99])],
+                     "seam_period": [float(v) for v in period[seam]][:8],
+                     "redetect_step_period_median": (float(np.median([period[i] for i in range(len(period)) if res[i + 1].redetected and not seam[i]]))
+                                                     if any(res[i + 1].redetected and not seam[i] for i in range(len(period))) else None),
+                     "unit": "us, medians over the timed steps, from wall_clock64() stamps of each kernel's first work item"}
+            if os.environ.get("VO_POSE_STAMPS"):
+                chain["pose_kernel_replay_refine_candidates"] = [float(np.median(ts[:, 6] - ts[:, 3])), float(np.median(ts[:, 7] - ts[:, 6])),
+                                                                 float(np.median(ts[:, 4] - ts[:, 7]))]
         out = {
             "metric": "VO frames/sec at 1376x1241, 2k keypoints; pose err vs reference" if CONFIG != "cfg5" else
                       "VO frames/sec at 3840x2160, 8k keypoints (stress configuration)",
@@ -838,32 +881,8 @@ def main():
                                     "path)" % (0.8 + DETECT_MARGIN)),
                        "rccl_world_size": dist.get_world_size() if exchange else 1,
                        "parallelism": "sequence-sharded x%d%s%s" % (world, ", %d sequences per GPU per launch" % S if S > 1 else "", ", RCCL all-gather of the {pose, landmarks} records of %d frames every %d frames" % (EXCHANGE_EVERY, EXCHANGE_EVERY) if exchange else "")},
-            "roofline": roof,
-            # the image-wide (streaming) kernels against the same HBM peak, from the untimed all-kernel event pass
-            # (the detector's kernels only when they run on every frame: a launch that a sequence sits out returns at once
-            #  and would flatter the average; VO_BENCH_DETECT_MARGIN=-1 gives their figures, profiles/ holds that line)
-            "roofline_streaming": {k: {"avg_launch_us": round(us(k), 2),
-                                       "algorithmic_bytes_per_launch": abytes(k),
-                                       "achieved": round(abytes(k) / (us(k) * 1e-6) / 1e9, 1),
-                                       "frac": round(abytes(k) / (us(k) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
-                                   for k in (("harris_response", "nms_candidates", "pyr_down") if DETECT_MARGIN < 0 else ("pyr_down",))
-                                   if k in per_kernel},
-            "per_kernel_us": {k: round(us(k), 2) for k in sorted(per_kernel)},
-            "per_kernel_note": "HIP-event averages over 16 untimed steps with every kernel bracketed (streams overlap: a kernel's "
-                               "time includes what it waits for the others)" + ("" if DETECT_MARGIN < 0 else
-                               "; harris_response / nms_* average over launches most sequences sit out"),
             "chain_us": chain,
             "loop": dict(lstats, bootstrap_landmarks=n_boot),
-            "pose_err_vs_ground_truth": {"rot_fro_median": float(np.median([e[0] for e in gt_err])),
-                                         "rot_fro_max": float(np.max([e[0] for e in gt_err])),
-                                         "trans_m_median": float(np.median([e[1] for e in gt_err])),
-                                         "trans_m_last": round(gt_err[-1][1], 3),
-                                         "trans_m_every_8th_frame": [round(e[1], 3) for e in gt_err[::8]],
-                                         "path_m": round((N_FRAMES - 1 - PASS_START) * synthetic.STEP_Z, 1),
-                                         "frames": len(gt_err),
-                                         "steps_finished_by_host_path": int(sum(rs[0].recovered for _, rs in first_pass)),
-                                         "note": "the whole first pass (frames %d..%d) vs the analytic poses of the synthetic stream, "
-                                                 "monocular scale fixed once by the bootstrap baseline" % (PASS_START + 1, N_FRAMES - 1)},
             "setup_s": {"render_%d_frames_%d_workers" % (len(jobs), workers): round(render_s, 1)},
             "bootstrap": {"relative_pose_ms": round(1e3 * boot_info.get("relative_pose_seconds", 0.0), 3),
                           "correspondences": boot_info.get("correspondences"), "inliers": boot_info.get("inliers"),
@@ -871,11 +890,69 @@ def main():
                                   "counts, closing fit, E decomposition, four cheirality votes and the triangulation on the "
                                   "device; the sequential accept rule and the Python classes around it on the host; untimed"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if full:
+            n_in, n_trk, n_tri = lstats["features_in_median"], lstats["tracked_median"], lstats["landmarks_p3p_median"]
+            avg_us = dom_ms / max(dom_n, 1) * 1e3
+
+            def abytes(k):                                   # one launch processes all S sequences
+                v = algorithmic_bytes(k, n_in, n_trk, n_tri)
+                return None if v is None else v * S
+
+            ab = abytes(dom_name)
+            roof = {"bound": "hbm", "kernel": KERNEL_LABEL.get(dom_name, dom_name), "avg_launch_us": round(avg_us, 3), "launches": dom_n,
+                    "algorithmic_bytes_per_launch": ab, "sequences_per_launch": S, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "traffic": pmc_traffic(dom_name) if S == 1 else None}
+            if ab and avg_us > 0:
+                ach = ab / (avg_us * 1e-6) / 1e9
+                roof["achieved"] = round(ach, 2)
+                roof["frac"] = round(ach / HBM_PEAK_GBS, 5)
+            else:
+                roof["achieved"] = None
+                roof["frac"] = None
+
+            def us(k):
+                return per_kernel[k][0] / per_kernel[k][1] * 1e3
+
+            # pose against the analytic ground truth of the stream over the whole first pass: the bootstrap fixes the unit
+            # of length (|t| = 1 between frames 0 and 2, 1.6 m apart), positions compared after that one scale
+            scale = 2 * synthetic.STEP_Z / max(np.linalg.norm(state.curr_pose[:3, 3]), 1e-12)
+            gt_err = []
+            for b, rs in first_pass:
+                r = rs[0]
+                Twc = r.pose_world_cam()
+                gt = np.linalg.inv(stream.T_world_cam(0)) @ stream.T_world_cam(b)
+                gt_err.append((float(np.linalg.norm(Twc[:3, :3] - gt[:3, :3])), float(np.linalg.norm(scale * Twc[:3, 3] - gt[:3, 3]))))
+            out.update({
+                "roofline": roof,
+                # the image-wide (streaming) kernels against the same HBM peak, from the untimed all-kernel event pass
+                # (the detector's kernels only when they run on every frame: a launch that a sequence sits out returns at once
+                #  and would flatter the average; VO_BENCH_DETECT_MARGIN=-1 gives their figures, profiles/ holds that line)
+                "roofline_streaming": {k: {"avg_launch_us": round(us(k), 2),
+                                           "algorithmic_bytes_per_launch": abytes(k),
+                                           "achieved": round(abytes(k) / (us(k) * 1e-6) / 1e9, 1),
+                                           "frac": round(abytes(k) / (us(k) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
+                                       for k in (("harris_response", "nms_candidates", "pyr_down") if DETECT_MARGIN < 0 else ("pyr_down",))
+                                       if k in per_kernel},
+                "per_kernel_us": {k: round(us(k), 2) for k in sorted(per_kernel)},
+                "per_kernel_note": "HIP-event averages over 16 untimed steps with every kernel bracketed (streams overlap: a kernel's "
+                                   "time includes what it waits for the others)" + ("" if DETECT_MARGIN < 0 else
+                                   "; harris_response / nms_* average over launches most sequences sit out"),
+                "pose_err_vs_ground_truth": {"rot_fro_median": float(np.median([e[0] for e in gt_err])),
+                                             "rot_fro_max": float(np.max([e[0] for e in gt_err])),
+                                             "trans_m_median": float(np.median([e[1] for e in gt_err])),
+                                             "trans_m_last": round(gt_err[-1][1], 3),
+                                             "trans_m_every_8th_frame": [round(e[1], 3) for e in gt_err[::8]],
+                                             "path_m": round((N_FRAMES - 1 - PASS_START) * synthetic.STEP_Z, 1),
+                                             "frames": len(gt_err),
+                                             "steps_finished_by_host_path": int(sum(rs[0].recovered for _, rs in first_pass)),
+                                             "note": "the whole first pass (frames %d..%d) vs the analytic poses of the synthetic stream, "
+                                                     "monocular scale fixed once by the bootstrap baseline" % (PASS_START + 1, N_FRAMES - 1)},
+            })
+        if full and world == 1 and not args.no_cpu_baseline:
             parity, base = oracle_leg(stream, state, [rs[0] for _, rs in first_pass[:CPU_BASELINE_FRAMES]], first_state, ORACLE_FRAMES)
             out["pose_vs_oracle"] = parity
             out["cpu_baseline"] = base
-        if world == 1 and not args.no_api:
+        if full and world == 1 and not args.no_api:
             # the API legs with every other pipeline closed (a second pipeline's streams share the device's hardware queues
             # with the first one's: beside the open headline pipeline these legs ran at half their rate)
             if pipe is not None:

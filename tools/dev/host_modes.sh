@@ -1,10 +1,11 @@
 #!/bin/bash
 # bench with legs under detector-prediction settings
+out=$(mktemp -d)
 run() {
-  timeout -k 10 400 python bench.py --steps 1000 --warmup 50 --no-api --no-cpu-baseline > gpurun_out/b8.json 2> gpurun_out/b8.err || tail -3 gpurun_out/b8.err
+  timeout -k 10 400 python bench.py --full --steps 1000 --warmup 50 --no-api --no-cpu-baseline > $out/b8.json 2> $out/b8.err || tail -3 $out/b8.err
   python - <<PY
 import json
-d = json.load(open("gpurun_out/b8.json"))
+d = json.load(open("$out/b8.json"))
 c = d["chain_us"]
 l = d["loop"]; s = d["sequences_16"]
 print("$1:", d["value"], "det %.2f host %d %s" % (l["detector_executed_fraction_of_steps"], l["steps_finished_by_host_path"], l["host_path_reasons"]), "| S16", s["frames_per_s"], "det %.2f host %d %s" % (s["detector_executed_fraction_of_steps"], s["steps_finished_by_host_path"], s["host_path_reasons"]))

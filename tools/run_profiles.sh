@@ -5,8 +5,8 @@
 # 2./3. one PMC pass each for FETCH_SIZE and WRITE_SIZE (never combined with a trace), with the detector on every
 #    frame so that every kernel's figures are per executed launch; 4. kernel-trace statistics of that mode and of the
 #    16-sequence run; 4b. the same runs with every pipeline stream mapped onto the main stream (each kernel's duration
-#    without the others beside it); 5. the bench lines: headline (with the CPU baseline, API and in-line legs), 16
-#    sequences per GPU, detector on every frame, cfg-3, cfg-5.
+#    without the others beside it); 5. the bench lines, --full: headline (with the CPU baseline, API and in-line legs), 16
+#    sequences per GPU, detector on every frame, cfg-3, cfg-5 (and the driver's plain --steps 20 --warmup 5).
 set -eo pipefail
 tag=${1:-r03}
 out=gpurun_out/prof_$tag
@@ -42,13 +42,13 @@ cp "$(ls $out/stats/*/*kernel_stats.csv | head -1)" $out/${tag}_bench_kernel_sta
 cp "$(ls $out/stats_s16/*/*kernel_stats.csv | head -1)" $out/${tag}_s16_kernel_stats.csv
 # the bench line reads the PMC figures it reports as roofline.traffic from profiles/<tag>_pmc_traffic.json
 cp $out/${tag}_pmc_traffic.json profiles/${tag}_pmc_traffic.json
-timeout -k 10 300 python3 bench.py > $out/${tag}_bench_line.json 2> $out/bench.err
+timeout -k 10 300 python3 bench.py --full > $out/${tag}_bench_line.json 2> $out/bench.err
 timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $out/${tag}_bench_line_driver_flags.json 2> $out/bench_drv.err
-timeout -k 10 300 python3 bench.py --sequences 16 --steps 300 --warmup 30 --no-cpu-baseline --no-api --no-legs > $out/${tag}_s16_bench_line.json 2> $out/bench_s16.err
-VO_BENCH_DETECT_MARGIN=-1 timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-api --no-legs > $out/${tag}_detect_every_frame_bench_line.json 2> $out/bench_da.err
-VO_BENCH_CONFIG=cfg3 timeout -k 10 300 python3 bench.py > $out/${tag}_cfg3_bench_line.json 2> $out/bench_cfg3.err
-VO_BENCH_CONFIG=harris timeout -k 10 300 python3 bench.py > $out/${tag}_harris_bench_line.json 2> $out/bench_harris.err
-VO_BENCH_CONFIG=cfg5 timeout -k 10 300 python3 bench.py --steps 300 --warmup 40 --no-cpu-baseline --no-api --no-legs > $out/${tag}_cfg5_bench_line.json 2> $out/bench_cfg5.err
+timeout -k 10 300 python3 bench.py --full --sequences 16 --steps 300 --warmup 30 --no-cpu-baseline --no-api --no-legs > $out/${tag}_s16_bench_line.json 2> $out/bench_s16.err
+VO_BENCH_DETECT_MARGIN=-1 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-api --no-legs > $out/${tag}_detect_every_frame_bench_line.json 2> $out/bench_da.err
+VO_BENCH_CONFIG=cfg3 timeout -k 10 300 python3 bench.py --full > $out/${tag}_cfg3_bench_line.json 2> $out/bench_cfg3.err
+VO_BENCH_CONFIG=harris timeout -k 10 300 python3 bench.py --full > $out/${tag}_harris_bench_line.json 2> $out/bench_harris.err
+VO_BENCH_CONFIG=cfg5 timeout -k 10 300 python3 bench.py --full --steps 300 --warmup 40 --no-cpu-baseline --no-api --no-legs > $out/${tag}_cfg5_bench_line.json 2> $out/bench_cfg5.err
 for f in $out/${tag}*_bench_line*.json; do echo "$f: $(grep -o '"value": [0-9.]*' $f | head -1)"; done
 # only the condensed files travel back (the raw traces are tens of MB)
 mkdir -p gpurun_out/profiles_$tag
