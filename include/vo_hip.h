@@ -538,6 +538,35 @@ int vo_pipeline_get_state_seq(vo_pipeline* p, int seq, int32_t* n_out, double* k
                               double* T_wc, double* T_wc_prev, vo_ransac_state* rs, int32_t* num_features);
 int vo_pipeline_get_rng_seq(vo_pipeline* p, int seq, vo_pcg64* rng);
 int vo_pipeline_collect_all(vo_pipeline* p, vo_step_result* outs);
+/* ---- lanes: many recordings through one pipeline ------------------------------------------------------------
+ * Each sequence of an S-sequence pipeline is a lane that can hold one recording after another, each handled as the
+ * reference handles a recording per process [ref: src/main.py:168-230, per recording: its camera, its bootstrap, a fresh
+ * RANSAC object and generator].  All three need nothing in flight (vo.driver.run_batch_on_device drains before them).
+ *
+ * _set_camera_seq: lane seq's intrinsics from now on (Kinv NULL: computed as at create).  Every kernel reads its
+ *   sequence's entry of a device table of S cameras (P3P hypotheses, pose + refinement, candidates, DLT, landmarks), and
+ *   so does the host recovery path.  A pipeline starts with cfg.K in every entry.
+ * _set_active_seq(seq, 0): the lane goes idle.  No kernel of a step works on it (its pyramid is left out of the launch, its
+ *   detector does not run, the tracker gets no features, the main chain's kernels return on the control block's
+ *   VO_FAULT_IDLE bit), it consumes no draws and it never enters the host recovery path.  collect_all still returns S
+ *   records; an idle lane's record has n_features_in = -1, fault = 256 (VO_FAULT_IDLE), best_index = -1,
+ *   refine_iterations = -1, raw_pos = its generator position, every other field 0.  _set_active_seq(seq, 1) only
+ *   accepts a lane that is active already: an idle lane comes back through _restart_seq.  While a lane is idle its frame
+ *   in the slot the next submit starts from may be replaced (vo_pipeline_set_frame_seq / _pinned), which is how a
+ *   restart gets its recording's first frame there.
+ * _restart_seq: a new recording for lane seq alone -- the arrays of vo_pipeline_set_state_seq for frame slot idx, which
+ *   must be the `prev` of the next submit; a fresh RANSAC object [ref: src/vo/algorithms/ransac.py:47-56]; the lane's
+ *   generator from *rng (NULL: the state of the last vo_pipeline_seed, i.e. what a fresh pipeline seeded the same way
+ *   starts from).  The pyramid and the detection of that frame are made for this lane only; the other lanes' Features,
+ *   control blocks, generators and pyramids are not touched.  A pyramid vo_pipeline_prepare built is dropped.  The lane
+ *   is active afterwards.  Cost: the drain before it (the look-ahead step is lost once) and one lane's pyramid +
+ *   detection, waited for (lanes).  KLT tracker mode.                                                   */
+int vo_pipeline_set_camera_seq(vo_pipeline* p, int seq, const double K[9], const double Kinv[9]);
+int vo_pipeline_set_active_seq(vo_pipeline* p, int seq, int active);
+int vo_pipeline_restart_seq(vo_pipeline* p, int seq, int idx, int n, const double* kp, const uint8_t* state,
+                            const double* landmarks, const double* tracks, const double* poses,
+                            const double* T_wc, const double* T_cw, const double* T_wc_prev,
+                            const double* T_cw_prev, int num_features, const vo_pcg64* rng);
 
 /* ---- shared map over RCCL ------------------------------------------------------------------
  * The reference is one process and one thread (README.md:49); frame streams shard at sequence granularity (one

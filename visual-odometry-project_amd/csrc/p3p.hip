@@ -491,6 +491,13 @@ p3p_hyp_kernel(const double* __restrict__ Xw, const double* __restrict__ xi,
     counts += q * (size_t)Hyp;
     if (masks) masks += q * (size_t)Hyp * words;
   }
+  if (B.cam) {                         // per-sequence intrinsics (uniform in the workgroup: scalar loads)
+    const double* K = B.cam + blockIdx.y * B.cam_stride;
+    fx = K[0];
+    fy = K[4];
+    cx = K[2];
+    cy = K[5];
+  }
   if (ts_out && blockIdx.x == 0 && tid == 0) *ts_out = wall_clock64();
   const int N = *d_n;
   const int h0 = blockIdx.x * HG;

@@ -48,7 +48,14 @@ struct vo_pipeline {
   vo_ctx* trk = nullptr;             // tracker stream: pyramid and KLT of step k+1 run beside the pose estimation of step k
   hipEvent_t evKlt[2] = {nullptr, nullptr}, evRegroup[2] = {nullptr, nullptr};
   vo_pipeline_config cfg;
-  vo_cam cam;
+  // intrinsics per sequence (vo_pipeline_set_camera_seq; all cfg.K at create): host copy (the recovery path) and the device
+  // table the kernels read entry q of
+  std::vector<vo_cam> cams;
+  vo_cam* d_cams = nullptr;          // [S]
+  // lanes (vo_pipeline_set_active_seq / vo_pipeline_restart_seq): idle[q] = sequence q does no work and its control block
+  // carries VO_FAULT_IDLE; seed_rng: the generator state of the last vo_pipeline_seed (a restarted lane's default)
+  std::vector<char> idle;
+  vo_pcg64 seed_rng;
   int n_levels = 1, cap = 0, words = 0, S = 1;
   size_t px = 0, pyr_bytes = 0;
   // ---- per-sequence buffers: S consecutive blocks each ----
@@ -60,13 +67,20 @@ struct vo_pipeline {
   double detect_limit = 0.0;         // detect when n < detect_limit * num_features (< 0: always)
   double detect_losses = 2.5;        // ... with n extrapolated by this many times the last step's loss
   hipEvent_t evPyr[3] = {nullptr, nullptr, nullptr}, evDet[3] = {nullptr, nullptr, nullptr};
-  // frame upload: pinned staging per (sequence, frame slot), allocated on first use; evImg[idx]: slot idx is in HBM
+  // frame upload: pinned staging per (sequence, frame slot), allocated on first use; evImg[idx]: every copy into slot idx
+  // that vo_pipeline_set_frame queued (tracker's stream) is in HBM
   std::vector<uint8_t*> h_img;
   std::vector<hipEvent_t> evImg;
   // vo_pipeline_set_frame_pinned: DMA straight from the caller's pinned buffer on a stream of its own (beside the kernels,
-  // not in front of the pyramid); side[idx]: slot idx was last filled that way -- the tracker's stream waits for evImg too
+  // not in front of the pyramid); evUp[idx]: every such copy into slot idx is in HBM.  The sequences of one slot may be
+  // filled either way (a batch driver mixes them; a restart fills one sequence's frame): pinned[q * n_frames + idx] = the
+  // last upload of (q, idx) was pinned, n_pinned[idx] = how many sequences of slot idx that holds for -- the pyramid and
+  // the detector wait for evUp while it is > 0; plain_used[idx]: a plain upload went into slot idx (the detector waits
+  // for evImg)
   hipStream_t up_stream = nullptr;
-  std::vector<char> side;
+  std::vector<hipEvent_t> evUp;
+  std::vector<char> pinned, plain_used;
+  std::vector<int> n_pinned;
   // vo_pipeline_prepare: the pyramid of frame slot prepared_idx sits in pyramid slot prepared_slot, built behind the
   // previous tracker -- the next submit whose `next` is that frame does not build it again (-1: none)
   int prepared_idx = -1, prepared_slot = -1;
@@ -199,6 +213,10 @@ __global__ __launch_bounds__(64) void detect_decide_kernel(const vo_seq_ctl* __r
                                                            int force, int* __restrict__ go, double losses) {
   const int q = blockIdx.x * 64 + threadIdx.x;
   if (q >= S) return;
+  if (ctl[q].fault & VO_FAULT_IDLE) {  // (an idle lane: vo_pipeline_set_active_seq)
+    go[q] = 0;
+    return;
+  }
   const int n2 = ctl[q].n2;
   const int lost = max(ctl[q].n_in - (ctl[q].redetected ? n_det : 0) - n2, 0);
   go[q] = (force || limit < 0.0 || (limit > 0.0 && (double)n2 - losses * (double)lost < (double)ctl[q].num_features * limit)) ? 1 : 0;
@@ -354,6 +372,20 @@ size_t feat_bytes(int cap, int S) {
   return (size_t)(q - (char*)nullptr);
 }
 
+// K and its inverse: Kinv as given, or (NULL) computed as the reference's np.linalg.inv gives it for a pinhole K
+vo_cam make_cam(const double* K, const double* Kinv) {
+  vo_cam c;
+  memcpy(c.K, K, sizeof(c.K));
+  if (Kinv) {
+    memcpy(c.Kinv, Kinv, sizeof(c.Kinv));
+  } else {
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    const double ki[9] = {1.0 / fx, 0.0, -cx / fx, 0.0, 1.0 / fy, -cy / fy, 0.0, 0.0, 1.0};
+    memcpy(c.Kinv, ki, sizeof(ki));
+  }
+  return c;
+}
+
 void sync_prof(vo_pipeline* p) {
   for (vo_ctx* q : {p->det, p->trk}) {
     q->prof_on = p->ctx->prof_on;
@@ -472,7 +504,7 @@ static void dbg_stage(const char* what) {
 
 static void worker_main(vo_pipeline* p);
 
-static int enqueue_pyramid(vo_pipeline* p, int frame, int s);
+static int enqueue_pyramid(vo_pipeline* p, int frame, int s, int q0 = 0, int Sn = 0);
 
 extern "C" {
 
@@ -497,7 +529,7 @@ void vo_pipeline_destroy(vo_pipeline* p) {
   void* dev[] = {p->d_det_go, p->d_img, p->d_pyr, p->d_kp, p->d_scores[0], p->d_scores[1], p->feat_mem, p->d_ctl, p->d_next, p->d_err,
                  p->d_status, p->d_R, p->d_t, p->d_valid, p->d_counts, p->d_samples, p->d_masks, p->d_best_mask, p->d_table,
                  p->d_raws, p->d_newkp, p->d_pairs, p->d_ckpt_feat, p->d_ckpt_ctl, p->d_skp, p->d_sdesc, p->d_sn, p->d_fdesc,
-                 p->d_srcrow, p->d_ckpt_fdesc, p->d_pend};
+                 p->d_srcrow, p->d_ckpt_fdesc, p->d_pend, p->d_cams};
   for (void* q : dev)
     if (q) (void)hipFree(q);
   void* pin[] = {p->h_stage, p->h_res, (void*)p->h_seq};
@@ -508,6 +540,8 @@ void vo_pipeline_destroy(vo_pipeline* p) {
   dbg_stage("destroy: memory freed");
   if (p->up_stream) (void)hipStreamDestroy(p->up_stream);
   for (hipEvent_t e : p->evImg)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : p->evUp)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {p->evPyr[0], p->evPyr[1], p->evPyr[2], p->evDet[0], p->evDet[1], p->evDet[2], p->evRaw, p->evA, p->evB,
                        p->evKlt[0], p->evKlt[1], p->evRegroup[0], p->evRegroup[1]})
@@ -557,18 +591,13 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   p->detect_limit = p->cfg.detect_margin < 0.0 ? -1.0 : p->cfg.redetect_fraction + p->cfg.detect_margin;
   if (p->cfg.debug_never_detect) p->detect_limit = 0.0;     // test hook: only forced detections (state hand-over, host path)
   if (const char* e = getenv("VO_DETECT_LOSSES")) p->detect_losses = atof(e);
-  memcpy(p->cam.K, cfg->K, sizeof(p->cam.K));
   {
     bool given = false;
     for (double v : cfg->Kinv) given |= v != 0.0;
-    if (given) {
-      memcpy(p->cam.Kinv, cfg->Kinv, sizeof(p->cam.Kinv));
-    } else {
-      const double fx = cfg->K[0], fy = cfg->K[4], cx = cfg->K[2], cy = cfg->K[5];
-      const double ki[9] = {1.0 / fx, 0.0, -cx / fx, 0.0, 1.0 / fy, -cy / fy, 0.0, 0.0, 1.0};
-      memcpy(p->cam.Kinv, ki, sizeof(ki));
-    }
+    p->cams.assign((size_t)p->S, make_cam(cfg->K, given ? cfg->Kinv : nullptr));
   }
+  p->idle.assign((size_t)p->S, 0);
+  memset(&p->seed_rng, 0, sizeof(p->seed_rng));
   int rc = VO_OK;
   // Three streams -- main (the caller's), tracker, detection -- plus the null stream (the caller's synchronous
   // copies, torch): the runtime spreads streams over four hardware queues and kernels of one queue run in order.
@@ -662,6 +691,7 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
     }
   }
   PA(dev_alloc(ctx, &p->d_ctl, Sz));
+  PA(dev_alloc(ctx, &p->d_cams, Sz));
   PA(dev_alloc(ctx, &p->d_next, Sz * cap * 2));
   PA(dev_alloc(ctx, &p->d_err, Sz * cap));
   PA(dev_alloc(ctx, &p->d_status, Sz * cap));
@@ -730,7 +760,8 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   }
   dbg_stage("create: events made");
   if (rc == VO_OK && (mcpy(ctx->stream, p->d_table, p->table.data(), p->table.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                      mset(ctx->stream, p->d_ctl, 0, Sz * sizeof(vo_seq_ctl)) != hipSuccess))
+                      mset(ctx->stream, p->d_ctl, 0, Sz * sizeof(vo_seq_ctl)) != hipSuccess ||
+                      mcpy(ctx->stream, p->d_cams, p->cams.data(), Sz * sizeof(vo_cam), hipMemcpyHostToDevice) != hipSuccess))
     rc = vo_set_error(ctx, VO_EHIP, "pipeline: initial uploads failed");
   if (rc != VO_OK) {
     vo_pipeline_destroy(p);
@@ -739,9 +770,14 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   dbg_stage("create: uploads made");
   p->h_img.assign(Sz * cfg->n_frames, nullptr);
   p->evImg.assign((size_t)cfg->n_frames, nullptr);
-  p->side.assign((size_t)cfg->n_frames, 0);
-  for (hipEvent_t& e : p->evImg)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = vo_set_error(ctx, VO_EHIP, "hipEventCreate failed");
+  p->evUp.assign((size_t)cfg->n_frames, nullptr);
+  p->pinned.assign(Sz * cfg->n_frames, 0);
+  p->plain_used.assign((size_t)cfg->n_frames, 0);
+  p->n_pinned.assign((size_t)cfg->n_frames, 0);
+  for (auto* v : {&p->evImg, &p->evUp})
+    for (hipEvent_t& e : *v)
+      if (rc == VO_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
+        rc = vo_set_error(ctx, VO_EHIP, "hipEventCreate failed");
   if (rc != VO_OK) {
     vo_pipeline_destroy(p);
     return rc;
@@ -792,8 +828,9 @@ int vo_pipeline_set_frame_seq(vo_pipeline* p, int seq, int idx, const uint8_t* i
   for (int k = 0; k < p->n_flight; ++k)
     VO_REQUIRE(ctx, p->flight[k].prev_idx != idx && p->flight[k].next_idx != idx,
                "pipeline_set_frame: slot %d belongs to a step in flight", idx);
-  // the frame submitted last is what the next step tracks FROM (and what a skipped detection is made up from)
-  VO_REQUIRE(ctx, !(p->have_state && p->primed && idx == p->prev_frame),
+  // the frame submitted last is what the next step tracks FROM (and what a skipped detection is made up from) -- except
+  // for an idle lane, whose frame there is the first of the recording vo_pipeline_restart_seq hands it next
+  VO_REQUIRE(ctx, !(p->have_state && p->primed && idx == p->prev_frame && !p->idle[seq]),
              "pipeline_set_frame: slot %d holds the frame the next step starts from", idx);
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   // Through a pinned staging buffer of this (sequence, slot), as one DMA queued on the tracker's stream -- in front of
@@ -810,9 +847,15 @@ int vo_pipeline_set_frame_seq(vo_pipeline* p, int seq, int idx, const uint8_t* i
   }
   VO_HIP_TRY(ctx, hipEventSynchronize(p->evImg[idx]));       // (the slot's previous upload has left the staging buffer)
   memcpy(stage, img, p->px);
+  char& pin = p->pinned[(size_t)seq * p->cfg.n_frames + idx];
+  if (pin) VO_HIP_TRY(ctx, hipStreamWaitEvent(p->trk->stream, p->evUp[idx], 0));   // (this copy lands after the pinned one)
   VO_HIP_TRY(ctx, hipMemcpyAsync(p->img(seq, idx), stage, p->px, hipMemcpyHostToDevice, p->trk->stream));
   VO_HIP_TRY(ctx, hipEventRecord(p->evImg[idx], p->trk->stream));
-  p->side[(size_t)idx] = 0;
+  if (pin) {
+    pin = 0;
+    --p->n_pinned[idx];
+  }
+  p->plain_used[idx] = 1;
   if (p->prepared_idx == idx) p->prepared_idx = p->prepared_slot = -1;
   return VO_OK;
 }
@@ -827,16 +870,20 @@ int vo_pipeline_set_frame_pinned(vo_pipeline* p, int seq, int idx, const uint8_t
   for (int k = 0; k < p->n_flight; ++k)
     VO_REQUIRE(ctx, p->flight[k].prev_idx != idx && p->flight[k].next_idx != idx,
                "pipeline_set_frame_pinned: slot %d belongs to a step in flight", idx);
-  VO_REQUIRE(ctx, !(p->have_state && p->primed && idx == p->prev_frame),
+  VO_REQUIRE(ctx, !(p->have_state && p->primed && idx == p->prev_frame && !p->idle[seq]),
              "pipeline_set_frame_pinned: slot %d holds the frame the next step starts from", idx);
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!p->up_stream) VO_HIP_TRY(ctx, hipStreamCreateWithFlags(&p->up_stream, hipStreamNonBlocking));
   // (a slot the tracker's stream filled last: that copy is in front of everything that read the slot; a step that read it
   //  has been collected -- the check above --, so nothing on the GPU still reads what this copy overwrites)
-  if (!p->side[(size_t)idx]) VO_HIP_TRY(ctx, hipStreamWaitEvent(p->up_stream, p->evImg[idx], 0));   // (a copy vo_pipeline_set_frame queued)
+  char& pin = p->pinned[(size_t)seq * p->cfg.n_frames + idx];
+  if (!pin && p->plain_used[idx]) VO_HIP_TRY(ctx, hipStreamWaitEvent(p->up_stream, p->evImg[idx], 0));   // (a copy vo_pipeline_set_frame queued)
   VO_HIP_TRY(ctx, hipMemcpyAsync(p->img(seq, idx), pinned_img, p->px, hipMemcpyHostToDevice, p->up_stream));
-  VO_HIP_TRY(ctx, hipEventRecord(p->evImg[idx], p->up_stream));
-  p->side[(size_t)idx] = 1;
+  VO_HIP_TRY(ctx, hipEventRecord(p->evUp[idx], p->up_stream));
+  if (!pin) {
+    pin = 1;
+    ++p->n_pinned[idx];
+  }
   if (p->prepared_idx == idx) p->prepared_idx = p->prepared_slot = -1;
   return VO_OK;
 }
@@ -846,10 +893,11 @@ int vo_pipeline_frame_uploaded(vo_pipeline* p, int idx, int wait) {
   vo_ctx* ctx = p->ctx;
   VO_REQUIRE(ctx, idx >= 0 && idx < p->cfg.n_frames, "pipeline_frame_uploaded: bad slot");
   if (wait) {
+    VO_HIP_TRY(ctx, hipEventSynchronize(p->evUp[idx]));
     VO_HIP_TRY(ctx, hipEventSynchronize(p->evImg[idx]));
     return 1;
   }
-  return hipEventQuery(p->evImg[idx]) == hipSuccess ? 1 : 0;
+  return hipEventQuery(p->evUp[idx]) == hipSuccess && hipEventQuery(p->evImg[idx]) == hipSuccess ? 1 : 0;
 }
 
 // The pyramid of a frame that a coming step will track INTO, built now, behind the tracker of the step submitted last (on
@@ -893,6 +941,7 @@ int vo_pipeline_set_frame(vo_pipeline* p, int idx, const uint8_t* img) { return 
 int vo_pipeline_seed(vo_pipeline* p, const vo_pcg64* rng) {
   if (!p || !rng) return VO_EINVAL;
   VO_REQUIRE(p->ctx, p->n_flight == 0, "pipeline_seed: %d submitted step(s) not collected", p->n_flight);
+  p->seed_rng = *rng;
   for (int q = 0; q < p->S; ++q) {     // every sequence has its own estimator object: each starts from this state
     p->rng[q] = *rng;
     p->raw_gen[q] = *rng;
@@ -918,28 +967,32 @@ int vo_pipeline_get_rng(vo_pipeline* p, vo_pcg64* rng) { return vo_pipeline_get_
 
 // Harris + NMS of frame slot `frame` into keypoint slot `s` on the detection stream; evDet[s] when done
 // (err_buf: the worker thread's private error text -- the pipeline context's buffer belongs to the caller's thread)
-static int enqueue_detection(vo_pipeline* p, int frame, int s, bool force, char* err_buf = nullptr) {
+// (q0, Sn): sequences q0 .. q0 + Sn - 1 (Sn = 0: all of them); an idle sequence's detector does not run (detect_decide_kernel)
+static int enqueue_detection(vo_pipeline* p, int frame, int s, bool force, char* err_buf = nullptr, int q0 = 0, int Sn = 0) {
   const vo_pipeline_config& c = p->cfg;
+  if (Sn <= 0) Sn = p->S - q0;
   p->det_flip ^= 1;
   vo_ctx* det = p->det;
   double* scores = p->d_scores[p->det_flip];
   det->nms_kp_f32 = nullptr;
-  int* go = p->d_det_go + (size_t)s * p->S;
-  if (hipStreamWaitEvent(det->stream, p->evImg[frame], 0) != hipSuccess) {   // the frame's upload (tracker's stream)
+  int* go = p->d_det_go + (size_t)s * p->S + q0;
+  bool wait_ok = hipStreamWaitEvent(det->stream, p->evImg[frame], 0) == hipSuccess;   // the frame's upload (tracker's stream)
+  if (wait_ok && p->n_pinned[frame] > 0) wait_ok = hipStreamWaitEvent(det->stream, p->evUp[frame], 0) == hipSuccess;   // (pinned)
+  if (!wait_ok) {
     if (err_buf) {
       snprintf(err_buf, 256, "detection: hipStreamWaitEvent failed");
       return VO_EHIP;
     }
     return vo_set_error(p->ctx, VO_EHIP, "detection: hipStreamWaitEvent failed");
   }
-  hipLaunchKernelGGL(detect_decide_kernel, dim3(vo_cdiv(p->S, 64)), dim3(64), 0, det->stream, p->d_ctl, p->S, p->detect_limit,
+  hipLaunchKernelGGL(detect_decide_kernel, dim3(vo_cdiv(Sn, 64)), dim3(64), 0, det->stream, p->d_ctl + q0, Sn, p->detect_limit,
                      c.n_keypoints, force ? 1 : 0, go, p->detect_losses);
   int rc = vo_check_launch(det, "detect_decide_kernel");
   if (rc == VO_OK)
-    rc = vo_harris_response_batch_dev(det, p->img(0, frame), p->img_stride(), p->S, c.H, c.W, c.harris_patch, c.harris_kappa,
+    rc = vo_harris_response_batch_dev(det, p->img(q0, frame), p->img_stride(), Sn, c.H, c.W, c.harris_patch, c.harris_kappa,
                                       scores, go);
   if (rc == VO_OK)
-    rc = vo_nms_keypoints_batch_dev(det, scores, p->S, c.H, c.W, c.n_keypoints, c.nms_radius, p->kp(0, s), p->det_stride(),
+    rc = vo_nms_keypoints_batch_dev(det, scores, Sn, c.H, c.W, c.n_keypoints, c.nms_radius, p->kp(q0, s), p->det_stride(),
                                     go);
   if (rc == VO_OK && hipEventRecord(p->evDet[s], det->stream) != hipSuccess) rc = VO_EHIP;
   if (rc != VO_OK) {
@@ -952,14 +1005,25 @@ static int enqueue_detection(vo_pipeline* p, int frame, int s, bool force, char*
   return VO_OK;
 }
 
-static int enqueue_pyramid(vo_pipeline* p, int frame, int s) {
+// (q0, Sn): sequences q0 .. q0 + Sn - 1 (Sn = 0: all of them); idle sequences are left out -- one launch per run of active ones
+static int enqueue_pyramid(vo_pipeline* p, int frame, int s, int q0, int Sn) {
   if (s == p->prepared_slot) p->prepared_idx = p->prepared_slot = -1;      // (whatever vo_pipeline_prepare left there goes)
-  if (p->side[(size_t)frame] && hipStreamWaitEvent(p->trk->stream, p->evImg[frame], 0) != hipSuccess)   // (vo_pipeline_set_frame_pinned)
+  if (p->n_pinned[frame] > 0 && hipStreamWaitEvent(p->trk->stream, p->evUp[frame], 0) != hipSuccess)   // (vo_pipeline_set_frame_pinned)
     return vo_set_error(p->ctx, VO_EHIP, "pyramid: hipStreamWaitEvent failed");
   const vo_pipeline_config& c = p->cfg;
-  const int rc = vo_pyramid_build_batch_dev(p->trk, p->img(0, frame), p->img_stride(), p->S, c.H, c.W, p->n_levels,
-                                            p->pyr(0, s), p->pyr_stride());
-  if (rc != VO_OK) return vo_set_error(p->ctx, rc, "pyramid: %s", vo_last_error(p->trk));
+  if (Sn <= 0) Sn = p->S - q0;
+  for (int a = q0; a < q0 + Sn;) {
+    if (p->idle[a]) {
+      ++a;
+      continue;
+    }
+    int b = a + 1;
+    while (b < q0 + Sn && !p->idle[b]) ++b;
+    const int rc = vo_pyramid_build_batch_dev(p->trk, p->img(a, frame), p->img_stride(), b - a, c.H, c.W, p->n_levels,
+                                              p->pyr(a, s), p->pyr_stride());
+    if (rc != VO_OK) return vo_set_error(p->ctx, rc, "pyramid: %s", vo_last_error(p->trk));
+    a = b;
+  }
   VO_HIP_TRY(p->ctx, hipEventRecord(p->evPyr[s], p->trk->stream));
   return VO_OK;
 }
@@ -1007,7 +1071,7 @@ static vo_pose_job make_pose_job(vo_pipeline* p, const vo_feat& B, int do_replay
   j.rp.best_mask = (unsigned long long*)p->d_best_mask + q * p->words;
   j.do_replay = do_replay;
   j.B = vo_feat_seq(B, q);
-  j.cam = p->cam;
+  j.cam = p->d_cams + q;
   j.bearing_thr = c.bearing_threshold;
   j.max_iter = c.refine_iters;
   j.tail = 0;
@@ -1126,6 +1190,8 @@ static int enqueue_pose_half(vo_pipeline* p, const vo_pipeline::flight_t& f, int
   hb.x = (size_t)p->cap * 2;
   hb.raws = p->ring_len;
   hb.ctl = sizeof(vo_seq_ctl);
+  hb.cam = reinterpret_cast<const double*>(p->d_cams + q);     // (K is the entry's first member)
+  hb.cam_stride = sizeof(vo_cam) / sizeof(double);
   VO_TRY(vo_p3p_hypotheses_ring_dev(ctx, B.land, B.kp64, &ctl->n_p3p, p->cap, c.K, p->d_raws + q * p->ring_len, &ctl->raw_pos,
                                     p->ring_len - 1, c.hyp, c.p3p_thr_sq, p->d_R + q * c.hyp * 9, p->d_t + q * c.hyp * 3,
                                     p->d_valid + q * c.hyp, p->d_counts + q * c.hyp, p->d_masks + q * c.hyp * p->words,
@@ -1154,14 +1220,14 @@ static int enqueue_pose_half(vo_pipeline* p, const vo_pipeline::flight_t& f, int
     const uint64_t* bm = p->d_best_mask + (size_t)q0 * p->words;
     const int rec_refined = c.refine_iters > 0 ? 1 : 0;
     if (walk_mode == 2) {
-      VO_TRY(vo_state_walk_landmarks(ctx, ctl, B, bm, p->words, p->cam, c.bearing_threshold, rec_refined, p->cap,
+      VO_TRY(vo_state_walk_landmarks(ctx, ctl, B, bm, p->words, p->d_cams + q0, c.bearing_threshold, rec_refined, p->cap,
                                      p->d_pend + q * p->cap, job.res, job.seq_word, seq, Sn));
       return VO_OK;
     }
     if (walk_mode == 1)
-      VO_TRY(vo_state_candidates(ctx, ctl, B, bm, p->cam, c.bearing_threshold, 1 /* ctl->refined: what the pose kernel's walk uses */,
+      VO_TRY(vo_state_candidates(ctx, ctl, B, bm, p->d_cams + q0, c.bearing_threshold, 1 /* ctl->refined: what the pose kernel's walk uses */,
                                  p->cap, Sn, p->words));
-    VO_TRY(vo_state_landmarks(ctx, ctl, B, p->cam, rec_refined, p->cap, job.res, job.seq_word, seq, Sn));
+    VO_TRY(vo_state_landmarks(ctx, ctl, B, p->d_cams + q0, rec_refined, p->cap, job.res, job.seq_word, seq, Sn));
     return VO_OK;
   }
   VO_TRY(vo_frame_pose(ctx, job, Sn));
@@ -1182,7 +1248,8 @@ static int enqueue_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, char* er
   vo_ctx* sc = ((f.k & 1) && !one_ctx) ? p->det : p->trk;
   const vo_pipeline_config& c = p->cfg;
   int rc = VO_OK;
-  if ((sc != p->trk || p->side[(size_t)f.next_idx]) && hipStreamWaitEvent(sc->stream, p->evImg[f.next_idx], 0) != hipSuccess) rc = VO_EHIP;   // (the upload)
+  if (sc != p->trk && hipStreamWaitEvent(sc->stream, p->evImg[f.next_idx], 0) != hipSuccess) rc = VO_EHIP;   // (the upload)
+  if (rc == VO_OK && p->n_pinned[f.next_idx] > 0 && hipStreamWaitEvent(sc->stream, p->evUp[f.next_idx], 0) != hipSuccess) rc = VO_EHIP;
   if (rc == VO_OK)
     rc = vo_sift_dev(sc, p->img(0, f.next_idx), c.H, c.W, p->sift_cap, p->d_skp + (size_t)f.b * p->sift_cap * 6, nullptr,
                      p->d_sdesc + (size_t)f.b * p->sift_cap * 128, p->d_sn + f.b);
@@ -1305,6 +1372,10 @@ static int worker_idle(vo_pipeline* p) {
 
 extern "C" {
 
+static int upload_state(vo_pipeline* p, int seq, int n, const double* kp, const uint8_t* state, const double* landmarks,
+                        const double* tracks, const double* poses, const double* T_wc, const double* T_cw,
+                        const double* T_wc_prev, const double* T_cw_prev, int num_features, bool keep_ransac,
+                        const uint64_t* raw_pos_set);
 int vo_pipeline_set_state_seq(vo_pipeline* p, int seq, int idx, int n, const double* kp, const uint8_t* state,
                               const double* landmarks, const double* tracks, const double* poses, const double* T_wc,
                               const double* T_cw, const double* T_wc_prev, const double* T_cw_prev, int num_features) {
@@ -1322,6 +1393,27 @@ int vo_pipeline_set_state_seq(vo_pipeline* p, int seq, int idx, int n, const dou
              p->prev_frame);
   VO_TRY(worker_idle(p));
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  VO_TRY(upload_state(p, seq, n, kp, state, landmarks, tracks, poses, T_wc, T_cw, T_wc_prev, T_cw_prev, num_features,
+                      p->seq_state[seq] != 0, nullptr));
+  // the pyramid and the detector's output of the frame the states belong to are made by the first submit
+  // (for all sequences at once: they share the frame slot, the last call's idx counts)
+  p->seq_state[seq] = 1;
+  p->slot = 0;
+  p->prev_frame = idx;
+  p->have_state = true;
+  p->primed = false;
+  return VO_OK;
+}
+
+// Features / State of sequence seq into the current Features buffer and its control block (nothing in flight).
+// keep_ransac: the RANSAC object's fields stay (a second hand-over to the same estimator), else RANSAC.__init__'s;
+// raw_pos: the generator position the device continues at (NULL: where it is).  The control block starts over (fault,
+// step, the VO_FAULT_IDLE bit included).
+static int upload_state(vo_pipeline* p, int seq, int n, const double* kp, const uint8_t* state, const double* landmarks,
+                        const double* tracks, const double* poses, const double* T_wc, const double* T_cw,
+                        const double* T_wc_prev, const double* T_cw_prev, int num_features, bool keep_ransac,
+                        const uint64_t* raw_pos_set) {
+  vo_ctx* ctx = p->ctx;
   hipStream_t st = ctx->stream;
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   const vo_feat F = vo_feat_seq(p->F[p->cur], (size_t)seq);
@@ -1343,11 +1435,10 @@ int vo_pipeline_set_state_seq(vo_pipeline* p, int seq, int idx, int n, const dou
   }
   vo_seq_ctl h;
   VO_HIP_TRY(ctx, mcpy(st, &h, p->d_ctl + seq, sizeof(h), hipMemcpyDeviceToHost));
-  const uint64_t raw_pos = h.raw_pos;
+  const uint64_t raw_pos = raw_pos_set ? *raw_pos_set : h.raw_pos;
   const int64_t n_it = h.n_iterations;
   const double orat = h.outlier_ratio;
   const uint32_t gate_klt = h.gate_klt;
-  const bool keep_ransac = p->seq_state[seq] != 0;
   memset(&h, 0, sizeof(h));
   h.n = n;
   h.n2 = n;
@@ -1369,13 +1460,7 @@ int vo_pipeline_set_state_seq(vo_pipeline* p, int seq, int idx, int n, const dou
   memcpy(h.T_wc_prev, T_wc_prev, 96);
   memcpy(h.T_cw_prev, T_cw_prev, 96);
   VO_HIP_TRY(ctx, mcpy(st, p->d_ctl + seq, &h, sizeof(h), hipMemcpyHostToDevice));
-  // the pyramid and the detector's output of the frame the states belong to are made by the first submit
-  // (for all sequences at once: they share the frame slot, the last call's idx counts)
-  p->seq_state[seq] = 1;
-  p->slot = 0;
-  p->prev_frame = idx;
-  p->have_state = true;
-  p->primed = false;
+  p->idle[seq] = 0;
   return VO_OK;
 }
 
@@ -1473,6 +1558,91 @@ extern "C" int vo_pipeline_rewind(vo_pipeline* p) {
   p->prev_frame = p->ckpt_frame;
   p->gate_resync = true;             // (the next tracker waits for that event, not only for its gate)
   return prime(p, false);            // pyramid + detector of that frame, queued on their streams
+}
+
+// ---- lanes: one pipeline, many recordings (vo_hip.h, vo_pipeline_set_camera_seq / _restart_seq / _set_active_seq) ----
+
+int vo_pipeline_set_camera_seq(vo_pipeline* p, int seq, const double* K, const double* Kinv) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S && K, "pipeline_set_camera: bad arguments");
+  VO_REQUIRE(ctx, K[0] != 0.0 && K[4] != 0.0, "pipeline_set_camera: singular intrinsics");
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_set_camera: %d submitted step(s) not collected", p->n_flight);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  p->cams[(size_t)seq] = make_cam(K, Kinv);
+  VO_HIP_TRY(ctx, mcpy(ctx->stream, p->d_cams + seq, &p->cams[(size_t)seq], sizeof(vo_cam), hipMemcpyHostToDevice));
+  return VO_OK;
+}
+
+// An idle lane's control block carries VO_FAULT_IDLE: every kernel of the main chain returns on it as on a sticky fault (the
+// regroup leaves n_p3p = 0, the pose and landmark kernels write a fault record and nothing else), the detector's decision
+// says no, the tracker gets n2 = 0 features, and the pyramid's launches leave the lane out.  The host neither redoes its
+// steps nor moves its generator.
+int vo_pipeline_set_active_seq(vo_pipeline* p, int seq, int active) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_set_active: bad sequence index");
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_set_active: %d submitted step(s) not collected", p->n_flight);
+  VO_REQUIRE(ctx, p->cfg.tracker_mode == 0, "pipeline_set_active: KLT tracker mode only");
+  if (active) {
+    VO_REQUIRE(ctx, !p->idle[seq], "pipeline_set_active: an idle lane is reactivated through vo_pipeline_restart_seq");
+    return VO_OK;
+  }
+  if (p->idle[seq]) return VO_OK;
+  VO_TRY(worker_idle(p));
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  int32_t w[2];
+  VO_HIP_TRY(ctx, mcpy(st, w, &p->d_ctl[seq].fault, 4, hipMemcpyDeviceToHost));
+  w[0] |= VO_FAULT_IDLE;
+  w[1] = 0;
+  VO_HIP_TRY(ctx, mcpy(st, &p->d_ctl[seq].fault, &w[0], 4, hipMemcpyHostToDevice));
+  VO_HIP_TRY(ctx, mcpy(st, &p->d_ctl[seq].n2, &w[1], 4, hipMemcpyHostToDevice));
+  p->idle[seq] = 1;
+  return VO_OK;
+}
+
+// A new recording for lane seq alone (main.py:168-230 per recording: a fresh RANSAC object, its own generator, the
+// bootstrap's Features and poses), at frame slot idx -- the slot the next submit reads as `prev`.  The pyramid and the
+// detection of that frame are made now for this sequence only; the other lanes' Features, control blocks, generators and
+// pyramids are not touched.  Nothing may be in flight (the driver drains first).
+int vo_pipeline_restart_seq(vo_pipeline* p, int seq, int idx, int n, const double* kp, const uint8_t* state,
+                                       const double* landmarks, const double* tracks, const double* poses,
+                                       const double* T_wc, const double* T_cw, const double* T_wc_prev,
+                                       const double* T_cw_prev, int num_features, const vo_pcg64* rng) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_restart: bad sequence index");
+  VO_REQUIRE(ctx, p->cfg.tracker_mode == 0, "pipeline_restart: KLT tracker mode only");
+  VO_REQUIRE(ctx, p->have_state && p->seeded, "pipeline_restart: seed and hand the pipeline's states over first");
+  VO_REQUIRE(ctx, idx == p->prev_frame, "pipeline_restart: frame slot %d is not the one the next step starts from (%d)", idx,
+             p->prev_frame);
+  VO_REQUIRE(ctx, n >= 0 && n <= p->cap, "pipeline_restart: %d features exceed the capacity %d", n, p->cap);
+  VO_REQUIRE(ctx, (n == 0 || (kp && state && landmarks && tracks && poses)) && T_wc && T_cw && T_wc_prev && T_cw_prev,
+             "pipeline_restart: null pointer");
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_restart: %d submitted step(s) not collected", p->n_flight);
+  VO_TRY(worker_idle(p));
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the lane's generator starts over: the device continues at the end of what its ring holds, the look-ahead is dropped
+  const vo_pcg64 g = rng ? *rng : p->seed_rng;
+  p->rng[seq] = g;
+  p->raw_gen[seq] = g;
+  p->pos_known[seq] = p->gen_upto[seq];
+  p->pos_dev[seq] = p->gen_upto[seq];
+  VO_TRY(upload_state(p, seq, n, kp, state, landmarks, tracks, poses, T_wc, T_cw, T_wc_prev, T_cw_prev, num_features, false,
+                      &p->gen_upto[seq]));
+  p->seq_state[seq] = 1;
+  p->gate_resync = true;
+  // a prepared pyramid may hold this lane's old frame (or be read behind a pyramid rebuilt below): it goes
+  p->prepared_idx = p->prepared_slot = -1;
+  if (p->primed) {                     // (else the first submit's prime() makes every sequence's)
+    VO_TRY(enqueue_pyramid(p, idx, p->slot, seq, 1));
+    VO_TRY(enqueue_detection(p, idx, p->slot, true, nullptr, seq, 1));
+    VO_HIP_TRY(ctx, hipStreamSynchronize(p->trk->stream));
+    VO_HIP_TRY(ctx, hipStreamSynchronize(p->det->stream));
+  }
+  return VO_OK;
 }
 
 int vo_pipeline_get_state_seq(vo_pipeline* p, int seq, int32_t* n_out, double* kp, uint8_t* state,
@@ -1848,7 +2018,7 @@ static int recover_step(vo_pipeline* p, const vo_pipeline::flight_t& f, int q, v
   while (!finished) {
     VO_TRY(vo_rng_choice(&g, n, 4, c.hyp, samples.data()));
     VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_samples, samples.data(), samples.size() * 4, hipMemcpyHostToDevice, st));
-    VO_TRY(vo_p3p_hypotheses_dev(ctx, B.land, B.kp64, n, c.K, p->d_samples, c.hyp, c.p3p_thr_sq, dR, dt, dvalid, dcounts,
+    VO_TRY(vo_p3p_hypotheses_dev(ctx, B.land, B.kp64, n, p->cams[q].K, p->d_samples, c.hyp, c.p3p_thr_sq, dR, dt, dvalid, dcounts,
                                  dmasks));
     VO_HIP_TRY(ctx, hipMemcpyAsync(valid.data(), dvalid, (size_t)c.hyp, hipMemcpyDeviceToHost, st));
     VO_HIP_TRY(ctx, hipMemcpyAsync(counts.data(), dcounts, (size_t)c.hyp * 4, hipMemcpyDeviceToHost, st));
@@ -1947,11 +2117,23 @@ int vo_pipeline_collect_all(vo_pipeline* p, vo_step_result* outs) {
   {
     const double t_in = now_s();
     for (int q = 0; q < p->S; ++q)
-      VO_TRY(wait_record(p, f.rslot, q, p->slot_seq[(size_t)f.rslot * p->S + q], p->pos_known[q], &outs[q]));
+      VO_TRY(wait_record(p, f.rslot, q, p->slot_seq[(size_t)f.rslot * p->S + q], p->idle[q] ? 0 : p->pos_known[q], &outs[q]));
     p->dbg_wait += now_s() - t_in;
   }
   for (int q = 0; q < p->S; ++q) {
     vo_step_result* out = &outs[q];
+    if (p->idle[q]) {                    // an idle lane's record (vo_hip.h): nothing was done, nothing is redone
+      const unsigned sh = out->seq_head, st = out->seq_tail;
+      memset(out, 0, sizeof(*out));
+      out->n_features_in = -1;
+      out->best_index = -1;
+      out->refine_iterations = -1;
+      out->fault = VO_FAULT_IDLE;
+      out->raw_pos = p->pos_known[q];
+      out->seq_head = sh;
+      out->seq_tail = st;
+      continue;
+    }
     const bool was_open = out->fault == VO_FAULT_CONTINUE;
     int rc = was_open ? continue_step(p, f, q, out) : VO_OK;
     if (rc != VO_OK) {
@@ -2052,9 +2234,9 @@ int vo_pipeline_bookkeeping(vo_pipeline* p, int phases, const double* new_kp, in
     VO_HIP_TRY(ctx, mcpy(st, p->d_best_mask, bits.data(), bits.size() * 8, hipMemcpyHostToDevice));
   }
   if (phases & 1)
-    VO_TRY(vo_state_candidates(ctx, p->d_ctl, p->F[p->cur], p->d_best_mask, p->cam, p->cfg.bearing_threshold, -1, p->cap));
+    VO_TRY(vo_state_candidates(ctx, p->d_ctl, p->F[p->cur], p->d_best_mask, p->d_cams, p->cfg.bearing_threshold, -1, p->cap));
   if (phases & 2)
-    VO_TRY(vo_state_landmarks(ctx, p->d_ctl, p->F[p->cur], p->cam, -1, p->cap, nullptr, nullptr, 0u));
+    VO_TRY(vo_state_landmarks(ctx, p->d_ctl, p->F[p->cur], p->d_cams, -1, p->cap, nullptr, nullptr, 0u));
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   return VO_OK;
 }

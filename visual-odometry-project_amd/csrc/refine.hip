@@ -403,6 +403,7 @@ __global__ __launch_bounds__(RF_T) void frame_pose_kernel(vo_pose_job job) {
     job.rp.masks += q * (size_t)job.rp.hyp * job.rp.words;
     job.rp.best_mask += q * (size_t)job.rp.words;
     job.B = vo_feat_seq(job.B, q);
+    job.cam += q;
     if (job.res) {
       job.res += q;
       job.seq_word += q;
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(RF_T) void frame_pose_kernel(vo_pose_job job) {
   }
   int it;
   double cost;
-  gauss_newton(cache, X, x, N, nullptr, mask_bits, job.cam.K[0], job.cam.K[4], job.cam.K[2], job.cam.K[5], job.max_iter,
+  gauss_newton(cache, X, x, N, nullptr, mask_bits, job.cam->K[0], job.cam->K[4], job.cam->K[2], job.cam->K[5], job.max_iter,
                1e-9, s_w, s_pose, s_try, &s_state, &it, &cost);
   if (wv == 0) {
     if (lane < 12) ctl->refined[lane] = s_pose[lane];
@@ -509,7 +510,7 @@ __global__ __launch_bounds__(RF_T) void frame_pose_kernel(vo_pose_job job) {
   __syncthreads();
   int count = 0;
   for (int i = tid; i < n2; i += RF_T) {
-    const int c = candidate_feature(job.B, i, n_tri, mask_bits, job.cam, Twc, job.bearing_thr);
+    const int c = candidate_feature(job.B, i, n_tri, mask_bits, *job.cam, Twc, job.bearing_thr);
     count += c;
     if (c && job.tail) {
       const int slot = atomicAdd(&s_nc, 1);
@@ -587,13 +588,13 @@ __global__ __launch_bounds__(RF_T) void frame_pose_kernel(vo_pose_job job) {
     }
     // the candidates: triangulated with their track's own start pose, inserted, checked by the same work item
     double C2[12];
-    k_times(job.cam.K, Tcw, C2);                 // proj2 = K inv(current_pose)[:3] (triangulation.py:53-57)
+    k_times(job.cam->K, Tcw, C2);                 // proj2 = K inv(current_pose)[:3] (triangulation.py:53-57)
     auto triangulate = [&](int i) {
       double Ts[12], Ti[12], C1[12], X[3];
 #pragma unroll
       for (int q = 0; q < 12; ++q) Ts[q] = B.pose[(size_t)q * B.pitch + i];
       rigid_inverse_3x4(Ts, Ti);
-      k_times(job.cam.K, Ti, C1);                // proj1 = K inv(pose_start)[:3]
+      k_times(job.cam->K, Ti, C1);                // proj1 = K inv(pose_start)[:3]
       vo_dlt::triangulate_point(C1, B.track[2 * i], B.track[2 * i + 1], C2, B.kp64[2 * i], B.kp64[2 * i + 1], X);
       B.land[3 * i] = X[0];
       B.land[3 * i + 1] = X[1];

@@ -458,13 +458,15 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
 // use_refined: 1 the refinement's pose, 0 the accepted hypothesis, -1 the pose the host put into ctl->T_in_*.
 __global__ __launch_bounds__(256) void state_candidates_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat B,
                                                                const unsigned long long* __restrict__ best_mask,
-                                                               vo_cam cam, double bearing_thr, int use_refined, int words) {
+                                                               const vo_cam* __restrict__ cams, double bearing_thr, int use_refined,
+                                                               int words) {
   if (blockIdx.y != 0) {               // several sequences per launch: grid.y = sequence
     const size_t q = blockIdx.y;
     ctl += q;
     B = vo_feat_seq(B, q);
     best_mask += q * (size_t)words;
   }
+  const vo_cam& cam = cams[blockIdx.y];
   if (ctl->fault) return;
   const int tid = threadIdx.x;
   const int n2 = ctl->n2, n_tri = ctl->n_tri;
@@ -507,7 +509,7 @@ __global__ __launch_bounds__(256) void state_candidates_kernel(vo_seq_ctl* __res
 // main.py:279-286: triangulate_candidates (triangulation.py:38-86, one start pose per track) ->
 // update_with_world_landmarks (state.py:69-88) -> _check_landmarks (state.py:90-107, only when there was a
 // candidate); the workgroup that finishes last closes the step and writes its result record.
-__global__ __launch_bounds__(256) void state_landmarks_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat B, vo_cam cam,
+__global__ __launch_bounds__(256) void state_landmarks_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat B, const vo_cam* __restrict__ cams,
                                                               int use_refined, vo_step_result* __restrict__ res,
                                                               unsigned* __restrict__ seq_word, unsigned seq) {
   __shared__ int s_cnt[2];
@@ -523,6 +525,7 @@ __global__ __launch_bounds__(256) void state_landmarks_kernel(vo_seq_ctl* __rest
     }
   }
   if (blockIdx.x == 0 && tid == 0) ctl->ts[4] = wall_clock64();
+  const vo_cam& cam = cams[blockIdx.y];
   const int fault = ctl->fault;
   if (fault) {
     if (res && blockIdx.x == 0 && tid == 0) write_fault_record(ctl, fault, res, seq_word, seq);
@@ -611,7 +614,7 @@ __global__ __launch_bounds__(256) void state_landmarks_kernel(vo_seq_ctl* __rest
 // better than the walk on the pose kernel's one compute unit).
 __global__ __launch_bounds__(256) void state_walk_landmarks_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat B,
                                                                    const unsigned long long* __restrict__ best_mask, int words,
-                                                                   vo_cam cam, double bearing_thr, int use_refined,
+                                                                   const vo_cam* __restrict__ cams, double bearing_thr, int use_refined,
                                                                    int* __restrict__ pend, vo_step_result* __restrict__ res,
                                                                    unsigned* __restrict__ seq_word, unsigned seq, int rec_fence) {
   __shared__ int s_cnt[3];             // dropped, landmarks, candidates of this workgroup
@@ -629,6 +632,7 @@ __global__ __launch_bounds__(256) void state_walk_landmarks_kernel(vo_seq_ctl* _
     }
   }
   if (blockIdx.x == 0 && tid == 0) ctl->ts[4] = wall_clock64();
+  const vo_cam& cam = cams[blockIdx.y];
   const int fault = ctl->fault;
   if (fault) {
     if (res && blockIdx.x == 0 && tid == 0) write_fault_record(ctl, fault, res, seq_word, seq);
@@ -825,17 +829,17 @@ int vo_state_regroup_pairs(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, c
   return vo_check_launch(ctx, "state_regroup_kernel");
 }
 
-int vo_state_candidates(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, vo_cam cam,
+int vo_state_candidates(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, const vo_cam* d_cams,
                         double bearing_thr, int use_refined, int cap, int S, int words) {
   {
     vo_prof_scope ps(ctx, VO_K_STATE_CANDIDATES);
     hipLaunchKernelGGL(state_candidates_kernel, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, B,
-                       (const unsigned long long*)d_best_mask, cam, bearing_thr, use_refined, words);
+                       (const unsigned long long*)d_best_mask, d_cams, bearing_thr, use_refined, words);
   }
   return vo_check_launch(ctx, "state_candidates_kernel");
 }
 
-int vo_state_walk_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, int words, vo_cam cam,
+int vo_state_walk_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, int words, const vo_cam* d_cams,
                             double bearing_thr, int use_refined, int cap, int32_t* d_pend, vo_step_result* m_result,
                             unsigned* m_seq, unsigned seq, int S) {
   VO_REQUIRE(ctx, d_pend != nullptr && cap <= B.pitch, "state_walk_landmarks: bad arguments");
@@ -844,17 +848,17 @@ int vo_state_walk_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint6
     // VO_RECORD_FENCE=1: system-scope fences between the record's lines and its closing words (see write_step_record)
     static const int rec_fence = getenv("VO_RECORD_FENCE") ? atoi(getenv("VO_RECORD_FENCE")) : 0;
     hipLaunchKernelGGL(state_walk_landmarks_kernel, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, B,
-                       (const unsigned long long*)d_best_mask, words, cam, bearing_thr, use_refined, (int*)d_pend, m_result,
+                       (const unsigned long long*)d_best_mask, words, d_cams, bearing_thr, use_refined, (int*)d_pend, m_result,
                        m_seq, seq, rec_fence);
   }
   return vo_check_launch(ctx, "state_walk_landmarks_kernel");
 }
 
-int vo_state_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, vo_cam cam, int use_refined, int cap,
+int vo_state_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const vo_cam* d_cams, int use_refined, int cap,
                        vo_step_result* m_result, unsigned* m_seq, unsigned seq, int S) {
   {
     vo_prof_scope ps(ctx, VO_K_STATE_LANDMARKS);
-    hipLaunchKernelGGL(state_landmarks_kernel, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, B, cam,
+    hipLaunchKernelGGL(state_landmarks_kernel, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, B, d_cams,
                        use_refined, m_result, m_seq, seq);
   }
   return vo_check_launch(ctx, "state_landmarks_kernel");

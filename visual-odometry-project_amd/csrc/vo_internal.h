@@ -191,6 +191,8 @@ struct vo_hyp_batch {     // several sequences per launch (grid.y = sequence); t
   size_t X = 0, x = 0;    // doubles between the sequences' landmark / keypoint arrays
   size_t raws = 0;        // words between their generator rings
   size_t ctl = 0;         // bytes between their control blocks (d_n, d_rawpos, d_flag, d_ts point into them)
+  const double* cam = nullptr;   // (optional) per-sequence intrinsics in device memory: sequence q's K (row-major 3x3) at
+  size_t cam_stride = 0;         // cam + q * cam_stride; NULL: the K the call is given, for every sequence
 };
 int vo_p3p_hypotheses_ring_dev(vo_ctx* ctx, const double* d_X, const double* d_x, const int32_t* d_n, int n_cap,
                                const double* K, const uint32_t* d_raws, const uint64_t* d_rawpos, uint32_t raw_mask,

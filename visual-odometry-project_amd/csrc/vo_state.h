@@ -45,6 +45,7 @@ enum {
   VO_FAULT_FORCED = 16,         // test hook (vo_pipeline_config.debug_fault_every)
   VO_FAULT_NO_DETECTION = 32,   // the tracks fell below the re-detect limit on a frame whose detection was skipped
   VO_FAULT_GATE = 128,          // a device-side gate was not opened within two seconds (a kernel it waits for never ran)
+  VO_FAULT_IDLE = 256,          // not an error: the lane is idle (vo_pipeline_set_active_seq); every kernel leaves it alone
   VO_FAULT_CONTINUE = 64        // not an error: the sequential rule is not done after this launch's `hyp` samples; the loop's
                                 // state is in the control block and the host launches the next batch (hypotheses + pose kernel)
 };
@@ -94,6 +95,8 @@ struct vo_seq_ctl {
 struct vo_cam {
   double K[9], Kinv[9];
 };
+// The camera of each sequence lives in a device table vo_cam[S] (vo_pipeline_set_camera_seq): kernels get the table's
+// address and sequence q reads entry q -- never the camera by value (S goes up to 256, the launch arguments would not hold it).
 
 // The re-detect branch (klt.py:207-230) without a copy: when fewer than frac * _num_features features are left,
 // the tracker and the regroup kernel treat the detector's keypoints of the old frame as features n .. n+n_det-1.
@@ -130,7 +133,7 @@ struct vo_pose_job {
   vo_replay_args rp;
   int do_replay;        // 0: ctl->best_pose / best_mask are given (host recovery path)
   vo_feat B;            // the new frame's features: land / kp64 are the P3P population
-  vo_cam cam;
+  const vo_cam* cam;    // device camera table: sequence q (block q) reads cam[q]
   double bearing_thr;
   int max_iter;         // Gauss-Newton steps allowed; 0 = refinement off
   // tail != 0: the same workgroup goes on with what state_landmarks_kernel does (candidate triangulation, landmark
@@ -162,16 +165,16 @@ int vo_state_regroup_pairs(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, c
                            const int32_t* d_n2 = nullptr, int32_t* d_src_row = nullptr);
 // main.py:261-268 + state.py:17-50, 135-219: pose, outliers, bearing-angle candidates
 // S > 1: sequence q uses block q of every array (mask rows of `words` 64-bit words)
-int vo_state_candidates(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, vo_cam cam,
+int vo_state_candidates(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, const vo_cam* d_cams,
                         double bearing_thr, int use_refined, int cap, int S = 1, int words = 0);
 // main.py:279-286 + triangulation.py:38-86 + state.py:69-107: candidate triangulation, landmark insertion,
 // cheirality check, step bookkeeping and the result record
 // vo_state_candidates and vo_state_landmarks in ONE launch (the frame loop's form): a feature's walk, its triangulation and its
 // cheirality test need nothing of another feature but the frame's candidate count being > 0.  d_pend: S x cap int32 of scratch.
-int vo_state_walk_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, int words, vo_cam cam,
+int vo_state_walk_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, int words, const vo_cam* d_cams,
                             double bearing_thr, int use_refined, int cap, int32_t* d_pend, vo_step_result* m_result,
                             unsigned* m_seq, unsigned seq, int S);
-int vo_state_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, vo_cam cam, int use_refined, int cap,
+int vo_state_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const vo_cam* d_cams, int use_refined, int cap,
                        vo_step_result* m_result, unsigned* m_seq, unsigned seq, int S = 1);
 // n_iterations for an outlier ratio through the threshold table (host copy of the device lookup; tests)
 int64_t vo_ransac_table_lookup(const double* table, int table_len, int64_t max_iterations, double outlier_ratio);

@@ -89,6 +89,11 @@ class StepResult(C.Structure):
         """State.curr_pose after the step: camera-to-world, 4x4."""
         return np.vstack([np.array(self.T_wc).reshape(3, 4), [0.0, 0.0, 0.0, 1.0]])
 
+    @property
+    def idle(self):
+        """The record of an idle lane (vo_pipeline_set_active_seq): nothing was computed for it."""
+        return self.n_features_in == -1
+
 
 _vp, _i, _d, _sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
 _SIGS = {
@@ -187,6 +192,9 @@ _SIGS = {
     "vo_pipeline_get_rng_seq": (_i, [_vp, _i, _vp]),
     "vo_pipeline_collect_all": (_i, [_vp, _vp]),
     "vo_pipeline_export_state_post_seq": (_i, [_vp, _i, _vp, _i, _vp]),
+    "vo_pipeline_set_camera_seq": (_i, [_vp, _i, _vp, _vp]),
+    "vo_pipeline_set_active_seq": (_i, [_vp, _i, _i]),
+    "vo_pipeline_restart_seq": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
 

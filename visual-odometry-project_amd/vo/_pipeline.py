@@ -121,9 +121,7 @@ class Pipeline:
         self.ctx._chk(self.ctx._lib.vo_pipeline_get_rng_seq(self._h, int(seq), C.byref(pcg)))
         pcg.to_generator(generator)
 
-    def set_state(self, idx, features, curr_pose, prev_pose=None, num_features=None, seq=0):
-        """Hands over `features` (a vo.primitives.Features: the current frame's, e.g. after the bootstrap) and
-        State's poses (4x4 camera-to-world) for frame slot `idx`."""
+    def _state_args(self, features, curr_pose, prev_pose, num_features):
         n = features.length
         kp = _c(np.asarray(features.keypoints).reshape(n, 2), np.float64)
         state = _c(np.asarray(features.state).reshape(n), np.uint8)
@@ -134,12 +132,45 @@ class Pipeline:
         T_wc_prev = _as_4x4(prev_pose if prev_pose is not None else curr_pose)
         T_cw, T_cw_prev = _c(np.linalg.inv(T_wc), np.float64), _c(np.linalg.inv(T_wc_prev), np.float64)
         nf = int(num_features if num_features is not None else self.cfg.n_keypoints)
-        self.ctx._chk(self.ctx._lib.vo_pipeline_set_state_seq(self._h, int(seq), int(idx), n, _ptr(kp), _ptr(state),
-                                                              _ptr(land), _ptr(tracks), _ptr(poses), _ptr(T_wc),
-                                                              _ptr(T_cw), _ptr(T_wc_prev), _ptr(T_cw_prev), nf))
+        keep = (kp, state, land, tracks, poses, T_wc, T_cw, T_wc_prev, T_cw_prev)     # (alive during the call)
+        return keep, [n] + [_ptr(a) for a in keep] + [nf]
+
+    def set_state(self, idx, features, curr_pose, prev_pose=None, num_features=None, seq=0):
+        """Hands over `features` (a vo.primitives.Features: the current frame's, e.g. after the bootstrap) and
+        State's poses (4x4 camera-to-world) for frame slot `idx`."""
+        n = features.length
+        keep, args = self._state_args(features, curr_pose, prev_pose, num_features)
+        self.ctx._chk(self.ctx._lib.vo_pipeline_set_state_seq(self._h, int(seq), int(idx), *args))
         if self.tracker in ("sift", "harris"):
             desc = _c(np.asarray(features.descriptors).reshape(n, 128 if self.tracker == "sift" else 361), np.float32)
             self.ctx._chk(self.ctx._lib.vo_pipeline_set_descriptors(self._h, _ptr(desc), n))
+
+    # ---- lanes: many recordings through one pipeline ----
+    def set_camera(self, K, seq, Kinv=None):
+        """Lane `seq`'s intrinsics (vo_pipeline_set_camera_seq; nothing in flight).  Kinv: the inverse as the caller
+        forms it; None = np.linalg.inv(K), as the constructor does (src/vo/sensors/camera.py:88)."""
+        K = _c(np.asarray(K, np.float64).reshape(3, 3), np.float64)
+        Ki = _c(np.linalg.inv(K) if Kinv is None else np.asarray(Kinv, np.float64).reshape(3, 3), np.float64)
+        self.ctx._chk(self.ctx._lib.vo_pipeline_set_camera_seq(self._h, int(seq), _ptr(K), _ptr(Ki)))
+
+    def set_active(self, seq, flag):
+        """flag False: lane `seq` goes idle -- no kernel works on it, it draws nothing, its records are marked
+        (StepResult.idle).  An idle lane becomes active again only through restart().  Nothing in flight."""
+        self.ctx._chk(self.ctx._lib.vo_pipeline_set_active_seq(self._h, int(seq), 1 if flag else 0))
+
+    def restart(self, seq, idx, features, curr_pose, prev_pose=None, num_features=None, generator=None, image=None):
+        """A new recording for lane `seq` alone (vo_pipeline_restart_seq; nothing in flight): its bootstrap's Features
+        and poses for frame slot `idx` (the `prev` of the next submit), a fresh RANSAC object and `generator`'s state
+        (None: the state the pipeline was seeded with).  image: the recording's frame for that slot; given, the lane is
+        set idle and the frame uploaded first (a lane's frame in that slot can only be replaced while it is idle)."""
+        from vo import _native
+        if image is not None:
+            self.set_active(seq, False)
+            self.set_frame(idx, image, seq=seq, pinned=False)
+        keep, args = self._state_args(features, curr_pose, prev_pose, num_features)
+        pcg = None if generator is None else _native.Pcg64.from_generator(generator)
+        self.ctx._chk(self.ctx._lib.vo_pipeline_restart_seq(self._h, int(seq), int(idx), *args,
+                                                            C.byref(pcg) if pcg is not None else None))
 
     def checkpoint(self):
         """Keeps a copy of every sequence's Features / State as they are now (nothing in flight) in HBM."""

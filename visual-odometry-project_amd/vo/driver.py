@@ -120,33 +120,16 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     they triangulate against a wrong baseline and can take the estimate with them); "current" starts them at the
     pose of the frame they were found on."""
     from vo import _native
-    from vo.features.klt import KLTTracker
     ctx = context or _native.default_context()
-    saved = (dict(KLTTracker._feature_params), dict(KLTTracker._lk_params))
-
-    def setup():
-        # the bootstrap tracks Shi-Tomasi corners (the reference's find_corners, klt.py:98), as many as the
-        # pipeline's detector keeps per frame
-        KLTTracker._feature_params = dict(saved[0], maxCorners=n_keypoints)
-        # (bootstrap_*: the two bootstrap frames are further apart than consecutive ones; on large frames the loop's own
-        #  window and the reference's 0.25 px epipolar threshold can settle on a wrong model, bench.py: bootstrap_state)
-        bw = bootstrap_win or klt_win
-        KLTTracker._lk_params = dict(saved[1], winSize=(bw, bw),
-                                     maxLevel=klt_max_level if bootstrap_max_level is None else bootstrap_max_level)
-
-    try:
-        state, tracker, _, _ = bootstrap(sequence, "klt", tracker_setup=setup, ransac_threshold=bootstrap_threshold)
-    finally:
-        KLTTracker._feature_params, KLTTracker._lk_params = saved
+    state, tracker = _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level,
+                                       bootstrap_threshold)
     frame = state.curr_frame
     img = _gray(frame.image)
     H, W = img.shape
     K = np.asarray(sequence.get_camera().intrinsic_matrix, np.float64)
     SLOTS = 4
-    pipe = _native.Pipeline(ctx, H, W, SLOTS, K, n_keypoints=n_keypoints, klt_win=klt_win, klt_max_level=klt_max_level,
-                            hyp=hyp, p3p_threshold=1.25 ** 2, outlier_ratio=0.9, confidence=0.9999, max_iterations=10000,
-                            refine_iters=20, bearing_threshold=state._bearing_threshold,
-                            redetect_start_pose=redetect_start_pose)
+    pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp,
+                                                                     redetect_start_pose))
     pipe.set_frame(0, img)
     pipe.set_state(0, frame.features, state.curr_pose, state.prev_pose, num_features=tracker._tracker._num_features)
     trajectory = [np.eye(4), state.get_pose()]
@@ -208,6 +191,255 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     pipe.close()
     return dict(trajectory=np.array(trajectory), n_landmarks=np.array(n_landmarks), frame_seconds=np.array(seconds),
                 results=results, features=features)
+
+
+def _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold):
+    """The host bootstrap (main.py:204-230) of a recording the device-resident pipeline goes on with: (state, tracker)."""
+    from vo.features.klt import KLTTracker
+    saved = (dict(KLTTracker._feature_params), dict(KLTTracker._lk_params))
+
+    def setup():
+        # the bootstrap tracks Shi-Tomasi corners (the reference's find_corners, klt.py:98), as many as the
+        # pipeline's detector keeps per frame
+        KLTTracker._feature_params = dict(saved[0], maxCorners=n_keypoints)
+        # (bootstrap_*: the two bootstrap frames are further apart than consecutive ones; on large frames the loop's own
+        #  window and the reference's 0.25 px epipolar threshold can settle on a wrong model, bench.py: bootstrap_state)
+        bw = bootstrap_win or klt_win
+        KLTTracker._lk_params = dict(saved[1], winSize=(bw, bw),
+                                     maxLevel=klt_max_level if bootstrap_max_level is None else bootstrap_max_level)
+
+    try:
+        state, tracker, _, _ = bootstrap(sequence, "klt", tracker_setup=setup, ransac_threshold=bootstrap_threshold)
+    finally:
+        KLTTracker._feature_params, KLTTracker._lk_params = saved
+    return state, tracker
+
+
+def _pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose):
+    """The pipeline's configuration for the steady state of main.py:194-201 (what run_on_device documents)."""
+    return dict(n_keypoints=n_keypoints, klt_win=klt_win, klt_max_level=klt_max_level, hyp=hyp, p3p_threshold=1.25 ** 2,
+                outlier_ratio=0.9, confidence=0.9999, max_iterations=10000, refine_iters=20,
+                bearing_threshold=state._bearing_threshold, redetect_start_pose=redetect_start_pose)
+
+
+def lane_schedule(lengths, lanes):
+    """Which recording holds which lane at which step of a batch run (run_batch_on_device), host arithmetic only.
+
+    lengths: steady-state steps of each recording (frames after its bootstrap), in queue order; lanes: pipeline
+    sequences.  The first recordings take lanes 0, 1, ...; when a recording has made its last step, its lane takes the
+    next recording of the queue at the following step, or goes idle when the queue is empty.  Recordings without a step
+    hold no lane.  Returns dict(
+        steps:   one tuple per step, entry l = (recording, its step index) held by lane l, or None (idle),
+        starts:  (step, lane, recording) -- the lane starts that recording at that step (step 0: the first hand-over,
+                 later ones: a restart, vo_pipeline_restart_seq),
+        idles:   (step, lane) -- the lane is idle from that step on (set_active(lane, False)) until a start names it,
+        lanes:   the lane count)."""
+    lengths = [int(n) for n in lengths]
+    lanes = int(lanes)
+    if lanes < 1:
+        raise ValueError("lane_schedule: need at least one lane")
+    if any(n < 0 for n in lengths):
+        raise ValueError("lane_schedule: negative recording length")
+    queue = [r for r, n in enumerate(lengths) if n > 0]
+    qi = 0
+    holder, pos = [None] * lanes, [0] * lanes
+    starts, idles, steps = [], [], []
+    for lane in range(lanes):
+        if qi < len(queue):
+            holder[lane] = queue[qi]
+            starts.append((0, lane, queue[qi]))
+            qi += 1
+        else:
+            idles.append((0, lane))
+    while any(h is not None for h in holder):
+        t = len(steps)
+        steps.append(tuple((holder[l], pos[l]) if holder[l] is not None else None for l in range(lanes)))
+        for lane in range(lanes):
+            if holder[lane] is None:
+                continue
+            pos[lane] += 1
+            if pos[lane] < lengths[holder[lane]]:
+                continue
+            pos[lane] = 0
+            if qi < len(queue):
+                holder[lane] = queue[qi]
+                starts.append((t + 1, lane, queue[qi]))
+                qi += 1
+            else:
+                holder[lane] = None
+                idles.append((t + 1, lane))
+    # (a lane that falls idle after the last step does nothing more: only events inside the run are kept)
+    idles = [(t, lane) for t, lane in idles if t < len(steps)]
+    return dict(steps=steps, starts=starts, idles=idles, lanes=lanes)
+
+
+def _steady_frames(sequence):
+    """Frames a recording yields after its bootstrap has taken frames 0..2 (Sequence.__next__)."""
+    inc = 1 if getattr(sequence, "dataset", "synthetic") == "synthetic" else int(getattr(sequence, "increment", 1))
+    return len(range(3 * inc, len(sequence), inc))
+
+
+def _frame_shape(sequence):
+    if getattr(sequence, "dataset", None) == "synthetic":
+        return (int(sequence.H), int(sequence.W))
+    return tuple(_gray(sequence.get_frame(0).image).shape[:2])
+
+
+def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
+                        klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
+                        redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
+                        bootstrap_threshold: float = 0.25):
+    """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
+    16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
+    as run_on_device does it; when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
+    goes idle (vo_pipeline_set_active_seq) -- lane_schedule says when.  Frames go through one pinned ring per lane,
+    uploaded a step ahead.  The steps in flight are drained before a lane changes recording (nothing may be in flight for
+    the three calls), so each such step loses the look-ahead once.  All recordings must have the same frame size.
+
+    Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
+    each step the recording took part in).  Each lane computes what run_on_device computes for its recording alone."""
+    from vo import _native
+    sequences = list(sequences)
+    if not sequences:
+        return []
+    shapes = [_frame_shape(s) for s in sequences]
+    if any(sh != shapes[0] for sh in shapes):
+        raise ValueError("run_batch_on_device: the recordings' frame sizes differ (%s); one pipeline takes one H x W"
+                         % sorted(set(shapes)))
+    H, W = shapes[0]
+    lengths = [_steady_frames(s) for s in sequences]
+    if max_frames is not None:
+        lengths = [min(n, int(max_frames)) for n in lengths]
+    lanes = int(lanes) if lanes else max(1, min(len(sequences), 16))
+    plan = lane_schedule(lengths, lanes)
+    steps = plan["steps"]
+    ctx = context or _native.default_context()
+    boot = {}
+
+    def boot_of(r):
+        if r not in boot:
+            boot[r] = _device_bootstrap(sequences[r], n_keypoints, klt_win, klt_max_level, bootstrap_win,
+                                        bootstrap_max_level, bootstrap_threshold)
+        return boot[r]
+
+    out = [None] * len(sequences)
+
+    def open_result(r):
+        state, tracker = boot_of(r)
+        out[r] = dict(trajectory=[np.eye(4), state.get_pose()],
+                      n_landmarks=[len(state.curr_frame.features.triangulated_inliers_landmarks)], frame_seconds=[],
+                      results=[], features=state.curr_frame.features)
+
+    for r in range(len(sequences)):            # (recordings without a steady-state step: the bootstrap is all there is)
+        if lengths[r] == 0:
+            open_result(r)
+    if steps:
+        first = next(r for (_, _, r) in plan["starts"])
+        state0, _ = boot_of(first)
+        K0 = np.asarray(sequences[first].get_camera().intrinsic_matrix, np.float64)
+        SLOTS = 4
+        pipe = _native.Pipeline(ctx, H, W, SLOTS, K0, sequences=lanes,
+                                **_pipeline_kwargs(state0, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose))
+        ring = [[ctx.pinned_empty((H, W)) for _ in range(SLOTS)] for _ in range(lanes)]
+        taken = [0] * len(sequences)
+
+        def next_frame(r):
+            taken[r] += 1
+            return next(sequences[r])
+
+        def put(lane, s, r):
+            ring[lane][s][...] = _gray(next_frame(r).image)
+            pipe.set_frame(s, ring[lane][s], seq=lane, pinned=True)
+
+        def start(lane, r, t, slot):
+            state, tracker = boot_of(r)
+            open_result(r)
+            frame = state.curr_frame
+            pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
+            args = (frame.features, state.curr_pose, state.prev_pose)
+            nf = tracker._tracker._num_features
+            if t == 0:
+                pipe.set_frame(slot, _gray(frame.image), seq=lane, pinned=False)
+                pipe.set_state(slot, *args, num_features=nf, seq=lane)
+            else:
+                pipe.restart(lane, slot, *args, num_features=nf, image=_gray(frame.image))
+
+        def finish(lane, r):
+            out[r]["features"] = pipe.get_features(lane)
+
+        pending = []
+
+        def collect_one():
+            t = pending.pop(0)
+            rs = pipe.collect_all()
+            for lane, e in enumerate(steps[t]):
+                if e is not None:
+                    o = out[e[0]]
+                    o["results"].append(rs[lane])
+                    o["trajectory"].append(rs[lane].pose_world_cam())
+                    o["n_landmarks"].append(rs[lane].n_landmarks)
+
+        events = {}
+        for t, lane, r in plan["starts"]:
+            events.setdefault(t, []).append((lane, r))
+        for t, lane in plan["idles"]:
+            events.setdefault(t, []).append((lane, None))
+        slot = 0
+        for lane, r in sorted(events.pop(0, [])):
+            if r is None:
+                pipe.set_active(lane, False)
+            else:
+                start(lane, r, 0, slot)
+        for lane, e in enumerate(steps[0]):
+            if e is not None:
+                put(lane, 1, e[0])
+        seconds = []
+        for t, row in enumerate(steps):
+            if t in events:
+                # a lane changes recording: drain, read what ends, then idle / restart (nothing in flight for either)
+                while pending:
+                    collect_one()
+                for lane, r in sorted(events[t]):
+                    prev = steps[t - 1][lane]
+                    if prev is not None:
+                        finish(lane, prev[0])
+                    if r is None:
+                        pipe.set_active(lane, False)
+                    else:
+                        start(lane, r, t, slot)
+                        put(lane, (slot + 1) % SLOTS, r)
+            t0 = time.perf_counter()
+            nxt = (slot + 1) % SLOTS
+            if len(pending) == 2:
+                collect_one()
+            ahead = False
+            if t + 1 < len(steps):                       # the frames of the NEXT step, for lanes that keep their recording
+                for lane, e in enumerate(steps[t + 1]):
+                    if e is not None and e[1] > 0:
+                        put(lane, (slot + 2) % SLOTS, e[0])
+                        ahead = True
+            pipe.submit(slot, nxt)
+            if ahead:
+                pipe.prepare((slot + 2) % SLOTS)
+            pending.append(t)
+            slot = nxt
+            seconds.append(time.perf_counter() - t0)
+            for e in row:
+                if e is not None:
+                    out[e[0]]["frame_seconds"].append(seconds[-1])
+        while pending:
+            collect_one()
+        for lane, e in enumerate(steps[-1]):
+            if e is not None:
+                finish(lane, e[0])
+        pipe.close()
+    for o in out:
+        o["trajectory"] = np.array(o["trajectory"])
+        o["n_landmarks"] = np.array(o["n_landmarks"])
+        o["frame_seconds"] = np.array(o["frame_seconds"])
+        if verbose:
+            print("%d steps, %d landmarks at the end" % (len(o["results"]), o["n_landmarks"][-1]))
+    return out
 
 
 def trajectory_error(result, sequence: Sequence):

@@ -36,7 +36,7 @@ def _imread(path):
 class Sequence:
     def __init__(self, dataset: str = "synthetic", path: str = "./data", camera: int = 0, increment: int = 1,
                  rectified: bool = False, use_lowres: bool = False, n_frames: int = 50, height: int = 480,
-                 width: int = 640, seed: int = 2023, channels: int = 1):
+                 width: int = 640, seed: int = 2023, channels: int = 1, intrinsics=None):
         self.dataset = dataset
         self._rel_data_path = path
         self.data_dir = os.path.abspath(path) if path is not None else None
@@ -48,7 +48,10 @@ class Sequence:
         self._gt = None
         if dataset == "synthetic":
             self.n_frames, self.H, self.W, self.seed, self.channels = n_frames, height, width, seed, channels
-            self.intrinsics = synthetic.intrinsics(height, width)
+            # intrinsics: the synthetic recording's own camera (vo.synthetic.render's K); None = synthetic.intrinsics
+            self._K_given = intrinsics is not None
+            self.intrinsics = (synthetic.intrinsics(height, width) if intrinsics is None
+                               else np.asarray(intrinsics, np.float64).reshape(3, 3).copy())
         elif dataset == "kitti":
             self.images = self._load_kitti()
         elif dataset == "parking":
@@ -106,7 +109,8 @@ class Sequence:
 
     def get_frame(self, idx: int) -> Frame:
         if self.dataset == "synthetic":
-            img, _, _, K = synthetic.render(idx * self.increment, self.H, self.W, self.seed)
+            img, _, _, K = synthetic.render(idx * self.increment, self.H, self.W, self.seed,
+                                            K=self.intrinsics if self._K_given else None)
             if self.channels == 3:
                 img = np.repeat(img[:, :, None], 3, axis=2)
         else:

@@ -40,11 +40,12 @@ def _hash_u8(i, j, surf, seed):
     return (h & np.uint64(0xFF)).astype(np.float32)
 
 
-def render(k, H, W, seed=2023, noise_sigma=2.0, want_depth=True, rows=32):
+def render(k, H, W, seed=2023, noise_sigma=2.0, want_depth=True, rows=32, K=None):
     """Frame k: (image uint8 (H, W), depth float32 (H, W) or None, T_world_cam (4, 4), K (3, 3)).
+    K: the camera the scene is seen through (a recording with its own calibration); None = intrinsics(H, W).
     Evaluated in blocks of `rows` image rows (cache-sized; every pixel's arithmetic and the order of the
     generator's draws are those of the whole-image evaluation, so the frames do not depend on `rows`)."""
-    K = intrinsics(H, W)
+    K = intrinsics(H, W) if K is None else np.asarray(K, np.float64).reshape(3, 3)
     T = pose_world_cam(k)
     R, C = T[:3, :3], T[:3, 3]
     u = (np.arange(W, dtype=np.float64) - K[0, 2]) / K[0, 0]
@@ -94,20 +95,24 @@ def render(k, H, W, seed=2023, noise_sigma=2.0, want_depth=True, rows=32):
 
 
 def _render_image(args):
-    k, H, W, seed = args
-    return render(k, H, W, seed, want_depth=False)[0]
+    k, H, W, seed = args[:4]
+    K = args[4] if len(args) > 4 else None
+    return render(k, H, W, seed, want_depth=False, K=K)[0]
 
 
 def _cache_file(job):
     import os
     d = os.environ.get("VO_SYNTH_CACHE")
-    return os.path.join(d, "synth_%dx%d_seed%d_frame%d.npy" % (job[1], job[2], job[3], job[0])) if d else None
+    if not d:
+        return None
+    tag = "" if len(job) < 5 or job[4] is None else "_K%016x" % (hash(tuple(np.asarray(job[4], np.float64).reshape(9))) & (2**64 - 1))
+    return os.path.join(d, "synth_%dx%d_seed%d_frame%d%s.npy" % (job[1], job[2], job[3], job[0], tag))
 
 
 def render_images(jobs, workers=0):
     """Images of many frames, jobs = [(k, H, W, seed), ...], rendered by `workers` processes (spawned: safe to call
     from a process that holds a GPU context; 0 = in this process).  VO_SYNTH_CACHE=<dir>: frames found there are read
-    instead of rendered, rendered ones are left there (tools/run_profiles.sh renders once for its dozen runs -- and keeps
+    instead of rendered, rendered ones are left there.  A job may carry a fifth entry, the camera K (None: the default) (tools/run_profiles.sh renders once for its dozen runs -- and keeps
     worker processes out of the profiler)."""
     import os
     out = [None] * len(jobs)
@@ -141,14 +146,15 @@ class Stream:
     """n frames of one scene (`seed`), forward from frame `start`.  Frames are rendered when first asked for
     (`prefetch` renders many at once, in worker processes); depth maps only on request."""
 
-    def __init__(self, n_frames, H, W, seed=2023, start=0):
+    def __init__(self, n_frames, H, W, seed=2023, start=0, K=None):
         self.H, self.W, self.n, self.seed, self.start = H, W, n_frames, seed, start
-        self.K = intrinsics(H, W)
+        self._K_given = K is not None
+        self.K = intrinsics(H, W) if K is None else np.asarray(K, np.float64).reshape(3, 3).copy()
         self._img, self._depth = {}, {}
 
     def prefetch(self, frames=None, workers=0):
         todo = [i for i in (range(self.n) if frames is None else frames) if i not in self._img]
-        for i, im in zip(todo, render_images([(self.start + i, self.H, self.W, self.seed) for i in todo], workers)):
+        for i, im in zip(todo, render_images([self._job(i) for i in todo], workers)):
             self._img[i] = im
         return self
 
@@ -156,14 +162,18 @@ class Stream:
         if i not in self._img:
             if not 0 <= i < self.n:
                 raise IndexError(i)
-            self._img[i] = _render_image((self.start + i, self.H, self.W, self.seed))
+            self._img[i] = _render_image(self._job(i))
         return self._img[i]
+
+    def _job(self, i):
+        j = (self.start + i, self.H, self.W, self.seed)
+        return j + (self.K,) if self._K_given else j
 
     def depth(self, i):
         if i not in self._depth:
             if not 0 <= i < self.n:
                 raise IndexError(i)
-            self._depth[i] = render(self.start + i, self.H, self.W, self.seed)[1]
+            self._depth[i] = render(self.start + i, self.H, self.W, self.seed, K=self.K if self._K_given else None)[1]
         return self._depth[i]
 
     def T_world_cam(self, i):
