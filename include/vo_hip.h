@@ -374,7 +374,8 @@ typedef struct vo_pipeline_config {
                                     launches (the sequence is the grid's extra dimension; SURVEY.md 8e: streams
                                     are independent, so they batch).  0 = 1.  Every sequence has its own frame
                                     store, Features, State, RANSAC object and generator; the plain entry points
-                                    address sequence 0, the _seq forms any of them.                      */
+                                    address sequence 0, the _seq forms any of them.  KLT and Harris tracker
+                                    modes: any S; SIFT tracker mode: one.                                */
   int32_t tracker_mode;          /* 0: KLT tracker with the Harris detector (everything above); 1: SIFT
                                     [ref: src/vo/features/tracker.py:60-61, src/vo/features/sift.py:23-56] -- per frame
                                     detect + describe (the sift_cap strongest keypoints; the reference keeps all of them),
@@ -382,11 +383,15 @@ typedef struct vo_pipeline_config {
                                     carry, Matches regroup from the pair list with the descriptors following their
                                     keypoints [ref: src/vo/primitives/matches.py:51-58, 134-141], then the same pose
                                     estimation and State bookkeeping.  One sequence per pipeline; the state handed over
-                                    needs its descriptors too (vo_pipeline_set_descriptors).
+                                    needs its descriptors too (vo_pipeline_set_descriptors).  debug_fault_every > 0 has
+                                    no effect in this mode.
                                     2: Harris [ref: tracker.py:58-59, src/vo/features/harris.py:50-84, 196-264] -- per
                                     frame the detector's n_keypoints keypoints (response + greedy NMS, every frame),
                                     their raw 19x19 patches (descriptor_radius 9) as bytes, 2-NN + 0.85 ratio +
-                                    uniqueness on the matrix cores (361 values padded to 384), then as mode 1.      */
+                                    uniqueness on the matrix cores (361 values padded to 384), then as mode 1.  Any
+                                    number of sequences: patches, matcher, regroup and descriptor gather take all of
+                                    them in one launch each; lanes (vo_pipeline_set_active_seq / _restart_seq) are KLT
+                                    mode only.  debug_fault_every > 0 forces the fault at the pair regroup.          */
   int32_t sift_cap;              /* keypoints kept per frame in SIFT mode (0 = n_keypoints; <= 4000, <= feature_cap) */
   double match_ratio;            /* 0 = the reference's: 0.8 in SIFT mode (sift.py:49), 0.85 in Harris mode (harris.py:255) */
 } vo_pipeline_config;
@@ -462,8 +467,14 @@ int vo_pipeline_set_state(vo_pipeline* p, int idx, int n, const double* kp, cons
  * streams (nothing in flight; no host synchronisation).  What lives on the reference's estimator object across frames
  * (RANSAC.n_iterations / outlier_ratio [ref: src/vo/algorithms/ransac.py:47-56], the generator) is NOT rewound.      */
 /* Descriptor tracker modes: the descriptors (n x 128 float32 in SIFT mode, n x 361 in Harris mode; whole numbers
- * 0..255) of the features handed over by the last vo_pipeline_set_state, in the same order.                      */
+ * 0..255) of the features handed over by the last vo_pipeline_set_state, in the same order.  The plain form is
+ * sequence 0's, the _seq form sequence seq's (the features handed over by vo_pipeline_set_state_seq for it).     */
 int vo_pipeline_set_descriptors(vo_pipeline* p, const float* desc, int n);
+int vo_pipeline_set_descriptors_seq(vo_pipeline* p, int seq, const float* desc, int n);
+/* The inverse: the descriptors the current Features of sequence seq carry (they follow their keypoints through every
+ * regroup), n x 361 (Harris) or n x 128 (SIFT) whole-number float32 in feature order; *n_out = n (desc may be NULL to
+ * ask for n only; desc holds up to vo_pipeline_feature_cap rows).  Nothing may be in flight.                      */
+int vo_pipeline_get_descriptors_seq(vo_pipeline* p, int seq, float* desc, int32_t* n_out);
 int vo_pipeline_checkpoint(vo_pipeline* p);
 int vo_pipeline_rewind(vo_pipeline* p);
 /* Downloads the current Features (arrays sized to the capacity vo_pipeline_feature_cap returns;

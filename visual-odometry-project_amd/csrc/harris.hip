@@ -1464,10 +1464,18 @@ __global__ __launch_bounds__(NT) void patch_desc_kernel(const uint8_t* __restric
 }
 
 // the same patches as bytes, one row of row_bytes (>= (2r+1)^2, the rest zero) per keypoint: what the device-resident
-// harris tracker mode matches on the matrix cores (the values are pixels: whole numbers 0..255 by construction)
+// harris tracker mode matches on the matrix cores (the values are pixels: whole numbers 0..255 by construction).
+// blockIdx.y = sequence: its image, keypoints and descriptor rows at img + y * img_stride, kp_xy + y * kp_stride (doubles),
+// desc + y * desc_stride
 __global__ __launch_bounds__(128) void patch_desc_u8_kernel(const uint8_t* __restrict__ img, int H, int W,
                                                             const double* __restrict__ kp_xy, int N, int r,
-                                                            uint8_t* __restrict__ desc, int row_bytes) {
+                                                            uint8_t* __restrict__ desc, int row_bytes, size_t img_stride = 0,
+                                                            size_t kp_stride = 0, size_t desc_stride = 0) {
+  if (blockIdx.y) {
+    img += blockIdx.y * img_stride;
+    kp_xy += blockIdx.y * kp_stride;
+    desc += blockIdx.y * desc_stride;
+  }
   const int k = blockIdx.x;
   const int d = 2 * r + 1;
   const int x = (int)kp_xy[2 * k], y = (int)kp_xy[2 * k + 1];
@@ -1694,12 +1702,22 @@ int vo_patch_descriptors_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, co
 
 int vo_patch_descriptors_u8_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const double* d_kp_xy, int N, int r,
                                 uint8_t* d_desc, int row_bytes) {
+  return vo_patch_descriptors_u8_batch_dev(ctx, d_img, 0, 1, H, W, d_kp_xy, 0, N, r, d_desc, 0, row_bytes);
+}
+
+// S sequences in one launch (grid (N, S)): sequence q's image at d_img + q * img_stride, its N keypoints at
+// d_kp_xy + q * kp_stride (doubles), its rows at d_desc + q * desc_stride (bytes)
+int vo_patch_descriptors_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_img, size_t img_stride, int S, int H, int W,
+                                      const double* d_kp_xy, size_t kp_stride, int N, int r, uint8_t* d_desc,
+                                      size_t desc_stride, int row_bytes) {
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, d_img && d_kp_xy && d_desc && N >= 1 && r >= 0 && (2 * r + 1) * (2 * r + 1) <= row_bytes,
              "patch_descriptors_u8: bad arguments");
+  VO_REQUIRE(ctx, S >= 1 && S <= 65535 && (S == 1 || desc_stride >= (size_t)N * row_bytes), "patch_descriptors_u8: bad batch");
   {
     vo_prof_scope ps(ctx, VO_K_PATCH_DESC);
-    hipLaunchKernelGGL(patch_desc_u8_kernel, dim3(N), dim3(128), 0, ctx->stream, d_img, H, W, d_kp_xy, N, r, d_desc, row_bytes);
+    hipLaunchKernelGGL(patch_desc_u8_kernel, dim3(N, S), dim3(128), 0, ctx->stream, d_img, H, W, d_kp_xy, N, r, d_desc, row_bytes,
+                       img_stride, kp_stride, desc_stride);
   }
   return vo_check_launch(ctx, "patch_desc_u8_kernel");
 }

@@ -120,13 +120,28 @@ __global__ __launch_bounds__(MT) void knn2_u8_kernel(const uint8_t* __restrict__
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
+// Several sequences per launch (frame pipeline): blockIdx.z = sequence; its query / train rows, device counts, partial
+// lists, arrival counters and outputs are block z of each array (q_stride / t_stride bytes, nq_stride / nt_stride ints;
+// best / d2: 2 * nq entries per sequence).  gridDim.z = 1 is the one-sequence launch.
 template <int KB>   // Dp = 32 * KB bytes per row
 __global__ __launch_bounds__(256) void knn2_mfma_kernel(const uint8_t* __restrict__ q, int nq, const uint8_t* __restrict__ t,
                                                         int nt, unsigned long long* __restrict__ part,
                                                         unsigned* __restrict__ arrived, int* __restrict__ best,
                                                         double* __restrict__ d2, const int* __restrict__ d_nq = nullptr,
-                                                        const int* __restrict__ d_nt = nullptr) {
+                                                        const int* __restrict__ d_nt = nullptr, size_t q_stride = 0,
+                                                        size_t t_stride = 0, int nq_stride = 0, int nt_stride = 0) {
   constexpr int Dp = 32 * KB;
+  if (blockIdx.z) {
+    const size_t z = blockIdx.z;
+    q += z * q_stride;
+    t += z * t_stride;
+    best += z * 2 * (size_t)nq;
+    d2 += z * 2 * (size_t)nq;
+    part += z * gridDim.x * gridDim.y * 64;
+    arrived += z * gridDim.x;
+    if (d_nq) d_nq += z * nq_stride;
+    if (d_nt) d_nt += z * nt_stride;
+  }
   if (d_nq) nq = min(nq, *d_nq);                       // counts that live on the device (frame pipeline): the launch is
   if (d_nt) nt = min(nt, *d_nt);                       // sized for the capacities
   if ((int)blockIdx.x * 32 >= nq || nt <= 0) {         // (every split of a block of queries leaves together)
@@ -317,15 +332,26 @@ __global__ __launch_bounds__(256) void pack_bytes_kernel(const float* __restrict
 }
 
 // ratio test (harris.py:250-258, sift.py:45-52): m.distance < ratio * n.distance on float32 distances, then the
-// train index goes to the first query that asks for it.  One workgroup; pairs come out in query order.
+// train index goes to the first query that asks for it.  One workgroup per sequence (blockIdx.x; block x of best / d2
+// (2 * nq entries), owner (nt_cap), pairs (2 * nq), n_pairs (1) and d_nq (nq_stride)); pairs come out in query order.
 constexpr int RU_T = 1024;
 __global__ __launch_bounds__(RU_T) void ratio_unique_kernel(const int* __restrict__ best, const double* __restrict__ d2, int nq,
                                                             double ratio, int* __restrict__ owner /* nt, preset to INT_MAX */,
                                                             int* __restrict__ pairs, int* __restrict__ n_pairs,
-                                                            const int* __restrict__ d_nq = nullptr) {
+                                                            const int* __restrict__ d_nq = nullptr, int nt_cap = 0,
+                                                            int nq_stride = 0) {
   __shared__ int s_scan[RU_T];
   __shared__ int s_base;
   const int tid = threadIdx.x;
+  if (blockIdx.x) {
+    const size_t z = blockIdx.x;
+    best += z * 2 * (size_t)nq;
+    d2 += z * 2 * (size_t)nq;
+    owner += z * (size_t)nt_cap;
+    pairs += z * 2 * (size_t)nq;
+    n_pairs += z;
+    if (d_nq) d_nq += z * nq_stride;
+  }
   if (d_nq) nq = min(nq, *d_nq);
   for (int i = tid; i < nq; i += RU_T) {
     const int b0 = best[2 * i], b1 = best[2 * i + 1];
@@ -381,45 +407,59 @@ int vo_knn2_dev(vo_ctx* ctx, const float* d_q, int nq, const float* d_t, int nt,
   return vo_check_launch(ctx, "knn2_f32_kernel");
 }
 
-// Frame-pipeline form (SIFT tracker mode, sift.py:38-54): 128-byte descriptor rows already on the device, the two
-// counts too (d_nq, d_nt; the launches are sized for cap_q / cap_t).  Pairs (query, train) in query order -> d_pairs
-// (cap_q x 2), their number -> *d_npairs.  Asynchronous on the context's stream; scratch[10..14] of the context.
-int vo_match_u8_dev(vo_ctx* ctx, const uint8_t* d_q, const int32_t* d_nq, int cap_q, const uint8_t* d_t, const int32_t* d_nt,
-                    int cap_t, double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes) {
+// Frame-pipeline form (SIFT / Harris tracker modes, sift.py:38-54, harris.py:246-262): descriptor rows of row_bytes
+// already on the device, the two counts too (d_nq, d_nt; the launches are sized for cap_q / cap_t).  Pairs (query, train)
+// in query order -> d_pairs (cap_q x 2), their number -> *d_npairs.  Asynchronous on the context's stream;
+// scratch[10..13] and match_arrived of the context.
+// S sequences in one launch each: sequence z's queries at d_q + z * q_stride (bytes), its query count at d_nq + z * nq_stride
+// (ints), its train rows / count likewise, its pairs at d_pairs + z * 2 * cap_q and its pair count at d_npairs[z].  Every
+// sequence is split and merged exactly as a one-sequence call of the same capacities.
+int vo_match_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride, int cap_q,
+                          const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride, int cap_t, int S,
+                          double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes) {
   if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, d_q && d_nq && d_t && d_nt && d_pairs && d_npairs && cap_q >= 1 && cap_t >= 1, "match_u8_dev: bad arguments");
+  VO_REQUIRE(ctx, d_q && d_nq && d_t && d_nt && d_pairs && d_npairs && cap_q >= 1 && cap_t >= 1 && S >= 1 && S <= 65535,
+             "match_u8_dev: bad arguments");
   VO_REQUIRE(ctx, row_bytes == 128 || row_bytes == 384, "match_u8_dev: rows of 128 (SIFT) or 384 (19x19 patches, padded) bytes");
+  VO_REQUIRE(ctx, S == 1 || (q_stride >= (size_t)cap_q * row_bytes && t_stride >= (size_t)cap_t * row_bytes),
+             "match_u8_dev: per-sequence blocks overlap");
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   vo_buf* s = ctx->scratch;
+  const size_t Sz = (size_t)S;
   const int qblocks = vo_cdiv(cap_q, 32), ttiles = vo_cdiv(cap_t, 32);
   int splits = 1;
   while (qblocks * splits < 512 && ttiles / (splits * 2) >= 4) splits *= 2;
-  VO_TRY(vo_ensure(ctx, s[10], (size_t)cap_q * 8));                      // best
-  VO_TRY(vo_ensure(ctx, s[11], (size_t)cap_q * 16));                     // d2
-  VO_TRY(vo_ensure(ctx, s[12], (size_t)cap_t * 4));                      // owner
-  VO_TRY(vo_ensure(ctx, s[13], (size_t)qblocks * splits * 64 * 8));      // partial top-2 lists
-  if (ctx->match_arrived.cap < (size_t)qblocks * 4) {
-    VO_TRY(vo_ensure(ctx, ctx->match_arrived, (size_t)qblocks * 4));
+  VO_TRY(vo_ensure(ctx, s[10], Sz * cap_q * 8));                          // best
+  VO_TRY(vo_ensure(ctx, s[11], Sz * cap_q * 16));                         // d2
+  VO_TRY(vo_ensure(ctx, s[12], Sz * cap_t * 4));                          // owner
+  VO_TRY(vo_ensure(ctx, s[13], Sz * qblocks * splits * 64 * 8));          // partial top-2 lists
+  if (ctx->match_arrived.cap < Sz * qblocks * 4) {                        // (zero once: the kernel leaves them at zero)
+    VO_TRY(vo_ensure(ctx, ctx->match_arrived, Sz * qblocks * 4));
     VO_HIP_TRY(ctx, hipMemsetAsync(ctx->match_arrived.p, 0, ctx->match_arrived.cap, st));
   }
-  VO_HIP_TRY(ctx, hipMemsetAsync(s[12].p, 0x7f, (size_t)cap_t * 4, st));
-  VO_HIP_TRY(ctx, hipMemsetAsync(d_npairs, 0, 4, st));
+  VO_HIP_TRY(ctx, hipMemsetAsync(s[12].p, 0x7f, Sz * cap_t * 4, st));
+  VO_HIP_TRY(ctx, hipMemsetAsync(d_npairs, 0, Sz * 4, st));
   {
     vo_prof_scope ps(ctx, VO_K_MATCH);
     if (row_bytes == 128)
-      hipLaunchKernelGGL(knn2_mfma_kernel<4>, dim3(qblocks, splits), dim3(256), 0, st, d_q, cap_q, d_t, cap_t,
+      hipLaunchKernelGGL(knn2_mfma_kernel<4>, dim3(qblocks, splits, S), dim3(256), 0, st, d_q, cap_q, d_t, cap_t,
                          (unsigned long long*)s[13].p, (unsigned*)ctx->match_arrived.p, (int*)s[10].p, (double*)s[11].p,
-                         (const int*)d_nq, (const int*)d_nt);
+                         (const int*)d_nq, (const int*)d_nt, q_stride, t_stride, nq_stride, nt_stride);
     else
-      hipLaunchKernelGGL(knn2_mfma_kernel<12>, dim3(qblocks, splits), dim3(256), 0, st, d_q, cap_q, d_t, cap_t,
+      hipLaunchKernelGGL(knn2_mfma_kernel<12>, dim3(qblocks, splits, S), dim3(256), 0, st, d_q, cap_q, d_t, cap_t,
                          (unsigned long long*)s[13].p, (unsigned*)ctx->match_arrived.p, (int*)s[10].p, (double*)s[11].p,
-                         (const int*)d_nq, (const int*)d_nt);
+                         (const int*)d_nq, (const int*)d_nt, q_stride, t_stride, nq_stride, nt_stride);
   }
   VO_TRY(vo_check_launch(ctx, "knn2_mfma_kernel"));
-  hipLaunchKernelGGL(ratio_unique_kernel, dim3(1), dim3(RU_T), 0, st, (const int*)s[10].p, (const double*)s[11].p, cap_q,
-                     ratio, (int*)s[12].p, (int*)d_pairs, (int*)d_npairs, (const int*)d_nq);
+  hipLaunchKernelGGL(ratio_unique_kernel, dim3(S), dim3(RU_T), 0, st, (const int*)s[10].p, (const double*)s[11].p, cap_q,
+                     ratio, (int*)s[12].p, (int*)d_pairs, (int*)d_npairs, (const int*)d_nq, cap_t, nq_stride);
   return vo_check_launch(ctx, "ratio_unique_kernel");
+}
+
+int vo_match_u8_dev(vo_ctx* ctx, const uint8_t* d_q, const int32_t* d_nq, int cap_q, const uint8_t* d_t, const int32_t* d_nt,
+                    int cap_t, double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes) {
+  return vo_match_u8_batch_dev(ctx, d_q, 0, d_nq, 0, cap_q, d_t, 0, d_nt, 0, cap_t, 1, ratio, d_pairs, d_npairs, row_bytes);
 }
 
 int vo_match_knn2_ratio(vo_ctx* ctx, const float* q, int nq, const float* t, int nt, int D, double ratio,

@@ -128,21 +128,22 @@ struct vo_pipeline {
   // current Features carry (bytes, regrouped with them: matches.py:51-58, 134-141) on the matrix cores, and regrouped
   // from the explicit pair list -- nothing of it leaves HBM.  One sequence per pipeline in this mode.
   // Harris tracker mode (tracker_mode = 2; tracker.py:58-59, harris.py:50-84): the same with the detector's N keypoints
-  // (every frame), their 19x19 raw patches as 384-byte rows, ratio 0.85.
+  // (every frame), their 19x19 raw patches as 384-byte rows, ratio 0.85 -- for any number of sequences: the detection,
+  // the patches, the matcher, the regroup and the descriptor gather take all S in one launch each (grid's extra dimension).
   int sift_cap = 0;
   int desc_row = 128;                // bytes per descriptor row: 128 (SIFT) or 384 (361 patch bytes, padded)
-  float* d_skp = nullptr;            // [3][sift_cap * 6]   keypoint rows of the frame in slot s
-  uint8_t* d_sdesc = nullptr;        // [3][sift_cap * 128] its descriptors
-  int32_t* d_sn = nullptr;           // [3] its keypoint count; [3]: pairs of the step being enqueued
-  uint8_t* d_fdesc = nullptr;        // [2][cap * 128]      descriptors of the Features buffers F[0], F[1]
-  int32_t* d_srcrow = nullptr;       // [cap]               new keypoint behind every regrouped feature
-  uint8_t* d_ckpt_fdesc = nullptr;
+  float* d_skp = nullptr;            // [3][sift_cap * 6]   keypoint rows of the frame in slot s (SIFT: one sequence)
+  uint8_t* d_sdesc = nullptr;        // [3][S][sift_cap * desc_row] its descriptors
+  int32_t* d_sn = nullptr;           // [3][S] its keypoint count; [S]: pairs of the step being enqueued
+  uint8_t* d_fdesc = nullptr;        // [2][S][cap * desc_row] descriptors of the Features buffers F[0], F[1]
+  int32_t* d_srcrow = nullptr;       // [S][cap]            new keypoint behind every regrouped feature
+  uint8_t* d_ckpt_fdesc = nullptr;   // [S][cap * desc_row]
   // vo_pipeline_checkpoint / _rewind: a copy of one Features buffer (all sequences) and of the control blocks
   char* d_ckpt_feat = nullptr;
   vo_seq_ctl* d_ckpt_ctl = nullptr;
   size_t feat_block = 0;             // bytes of one Features buffer (F[0] and F[1] are consecutive blocks of feat_mem)
   int ckpt_frame = -1;
-  int32_t* d_pairs = nullptr;
+  int32_t* d_pairs = nullptr;        // [cap * 2] ([S][cap * 2] in the descriptor modes)
   long n_recovered = 0, n_continued = 0;
   bool pose_fault_hook = true;       // debug_fault_every < 0 applies to submitted steps, not to what recover_step re-enqueues
   // Detection worker: a second host thread enqueues the detection of every step (6 launches) while the caller's
@@ -184,6 +185,10 @@ struct vo_pipeline {
   double* kp(int q, int s) const { return d_kp + ((size_t)q * 3 + s) * cfg.n_keypoints * 2; }
   size_t det_stride() const { return (size_t)3 * cfg.n_keypoints * 2; }
   vo_step_result* res_h(int rslot, int q) const { return h_res + (size_t)rslot * S + q; }
+  uint8_t* sdesc(int s, int q) const { return d_sdesc + ((size_t)s * S + q) * sift_cap * desc_row; }
+  uint8_t* fdesc(int fb, int q) const { return d_fdesc + ((size_t)fb * S + q) * cap * desc_row; }
+  int32_t* sn(int s, int q) const { return d_sn + (size_t)s * S + q; }             // keypoints of the frame in slot s
+  int32_t* npairs(int q) const { return d_sn + (size_t)3 * S + q; }
   volatile unsigned* seq_h(int rslot, int q) const { return h_seq + (size_t)rslot * S + q; }
 };
 
@@ -257,9 +262,16 @@ __global__ __launch_bounds__(256) void sift_kp_f64_kernel(const float* __restric
 }
 
 // ... and the descriptors of the regrouped frame: row dst of the new Features = the new keypoint src_row[dst]'s
+// (blockIdx.y = sequence: ctl + y, src_row + y * cap, src + y * src_stride, dst + y * dst_stride; bytes)
 __global__ __launch_bounds__(256) void desc_gather_kernel(const uint8_t* __restrict__ src, const int* __restrict__ src_row,
                                                           const vo_seq_ctl* __restrict__ ctl, int cap, uint8_t* __restrict__ dst,
-                                                          int row_words) {
+                                                          int row_words, size_t src_stride, size_t dst_stride) {
+  if (blockIdx.y) {
+    ctl += blockIdx.y;
+    src_row += (size_t)blockIdx.y * cap;
+    src += blockIdx.y * src_stride;
+    dst += blockIdx.y * dst_stride;
+  }
   if (ctl->fault) return;
   const int w = blockIdx.x * 256 + threadIdx.x;        // one 4-byte word of one row
   const int row = w / row_words, k = w - row * row_words;
@@ -570,7 +582,7 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   VO_REQUIRE(ctx, cfg->refine_iters >= 0 && cfg->refine_iters <= 100, "pipeline: refine_iters must be in 0..100");
   VO_REQUIRE(ctx, cfg->sequences >= 0 && cfg->sequences <= 256, "pipeline: sequences must be in 1..256");
   VO_REQUIRE(ctx, cfg->tracker_mode >= 0 && cfg->tracker_mode <= 2, "pipeline: tracker_mode must be 0 (klt), 1 (sift) or 2 (harris)");
-  VO_REQUIRE(ctx, cfg->tracker_mode == 0 || cfg->sequences <= 1, "pipeline: the descriptor tracker modes run one sequence per pipeline");
+  VO_REQUIRE(ctx, cfg->tracker_mode != 1 || cfg->sequences <= 1, "pipeline: the SIFT tracker mode runs one sequence per pipeline");
   const int cap = cfg->feature_cap > 0 ? cfg->feature_cap : 2 * cfg->n_keypoints;
   VO_REQUIRE(ctx, cap >= cfg->n_keypoints && cap <= 32768, "pipeline: feature_cap must be in n_keypoints..32768");
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -704,22 +716,24 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   PA(dev_alloc(ctx, &p->d_best_mask, Sz * p->words));
   PA(dev_alloc(ctx, &p->d_pend, Sz * cap));
   PA(dev_alloc(ctx, &p->d_newkp, (size_t)cap * 2));
-  PA(dev_alloc(ctx, &p->d_pairs, (size_t)cap * 2));
+  PA(dev_alloc(ctx, &p->d_pairs, (size_t)cap * 2 * (cfg->tracker_mode != 0 ? Sz : 1)));
   if (cfg->tracker_mode != 0) {
     p->desc_row = cfg->tracker_mode == 2 ? 384 : 128;
     p->sift_cap = cfg->tracker_mode == 2 ? cfg->n_keypoints : (cfg->sift_cap > 0 ? cfg->sift_cap : cfg->n_keypoints);
     if (rc == VO_OK && (p->sift_cap > cap || p->sift_cap > 4000))
       rc = vo_set_error(ctx, VO_EINVAL, "pipeline: sift_cap %d exceeds the feature capacity %d (or 4000)", p->sift_cap, cap);
     PA(dev_alloc(ctx, &p->d_skp, (size_t)3 * p->sift_cap * 6));
-    PA(dev_alloc(ctx, &p->d_sdesc, (size_t)3 * p->sift_cap * p->desc_row));
-    PA(dev_alloc(ctx, &p->d_sn, 8));
-    PA(dev_alloc(ctx, &p->d_fdesc, (size_t)2 * cap * p->desc_row));
-    PA(dev_alloc(ctx, &p->d_srcrow, (size_t)cap));
-    if (rc == VO_OK && (hipMemset(p->d_sn, 0, 32) != hipSuccess || hipMemset(p->d_fdesc, 0, (size_t)2 * cap * p->desc_row) != hipSuccess))
+    PA(dev_alloc(ctx, &p->d_sdesc, 3 * Sz * p->sift_cap * p->desc_row));
+    PA(dev_alloc(ctx, &p->d_sn, 4 * Sz + 4));
+    PA(dev_alloc(ctx, &p->d_fdesc, 2 * Sz * cap * p->desc_row));
+    PA(dev_alloc(ctx, &p->d_srcrow, Sz * cap));
+    if (rc == VO_OK && (hipMemset(p->d_sn, 0, (4 * Sz + 4) * 4) != hipSuccess ||
+                        hipMemset(p->d_fdesc, 0, 2 * Sz * cap * p->desc_row) != hipSuccess))
       rc = vo_set_error(ctx, VO_EHIP, "pipeline: hipMemset failed");
     if (rc == VO_OK && cfg->tracker_mode == 2) {          // (every frame has exactly N detector keypoints)
-      const int32_t nn[3] = {cfg->n_keypoints, cfg->n_keypoints, cfg->n_keypoints};
-      if (hipMemcpy(p->d_sn, nn, 12, hipMemcpyHostToDevice) != hipSuccess) rc = vo_set_error(ctx, VO_EHIP, "pipeline: hipMemcpy failed");
+      const std::vector<int32_t> nn(3 * Sz, cfg->n_keypoints);
+      if (hipMemcpy(p->d_sn, nn.data(), nn.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        rc = vo_set_error(ctx, VO_EHIP, "pipeline: hipMemcpy failed");
     }
   }
   // n_iterations as a step function of the outlier ratio (state_device.h, table_lookup): a batch of `hyp`
@@ -1252,7 +1266,7 @@ static int enqueue_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, char* er
   if (rc == VO_OK && p->n_pinned[f.next_idx] > 0 && hipStreamWaitEvent(sc->stream, p->evUp[f.next_idx], 0) != hipSuccess) rc = VO_EHIP;
   if (rc == VO_OK)
     rc = vo_sift_dev(sc, p->img(0, f.next_idx), c.H, c.W, p->sift_cap, p->d_skp + (size_t)f.b * p->sift_cap * 6, nullptr,
-                     p->d_sdesc + (size_t)f.b * p->sift_cap * 128, p->d_sn + f.b);
+                     p->sdesc(f.b, 0), p->sn(f.b, 0));
   if (rc == VO_OK && hipEventRecord(p->evPyr[f.b], sc->stream) != hipSuccess) rc = VO_EHIP;
   if (rc != VO_OK) {
     if (err_buf) {
@@ -1265,13 +1279,14 @@ static int enqueue_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, char* er
 }
 
 // Harris tracker mode: the new frame's N keypoints (Harris response + greedy NMS, every frame) and their raw patches as
-// bytes, on the detection stream; slot f.b
+// bytes, on the detection stream; slot f.b.  All sequences: one detection (forced) and one patch launch (grid (N, S)).
 static int enqueue_harris_front(vo_pipeline* p, const vo_pipeline::flight_t& f, char* err_buf = nullptr) {
   const vo_pipeline_config& c = p->cfg;
   int rc = enqueue_detection(p, f.next_idx, f.b, true, err_buf);
   if (rc != VO_OK) return rc;
-  rc = vo_patch_descriptors_u8_dev(p->det, p->img(0, f.next_idx), c.H, c.W, p->kp(0, f.b), c.n_keypoints, 9,
-                                   p->d_sdesc + (size_t)f.b * p->sift_cap * p->desc_row, p->desc_row);
+  rc = vo_patch_descriptors_u8_batch_dev(p->det, p->img(0, f.next_idx), p->img_stride(), p->S, c.H, c.W, p->kp(0, f.b),
+                                         p->det_stride(), c.n_keypoints, 9, p->sdesc(f.b, 0),
+                                         (size_t)p->sift_cap * p->desc_row, p->desc_row);
   if (rc == VO_OK && hipEventRecord(p->evPyr[f.b], p->det->stream) != hipSuccess) rc = VO_EHIP;
   if (rc != VO_OK) {
     if (err_buf) {
@@ -1285,39 +1300,54 @@ static int enqueue_harris_front(vo_pipeline* p, const vo_pipeline::flight_t& f, 
 
 // main-stream chain of a step in SIFT mode: 2-NN + ratio + uniqueness against the current Features' descriptors
 // (sift.py:38-54), Matches regroup from the pair list (matches.py:26-212) with the descriptors following their
-// keypoints, then hypotheses and pose as in the KLT mode
-static int enqueue_chain_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, bool first_half_only, unsigned seq) {
+// keypoints, then hypotheses and pose as in the KLT mode.  (q0, Sn): sequences q0 .. q0 + Sn - 1 (Harris mode: all of
+// them, or one when a step is redone; SIFT mode has one).  debug_fault_every: the test hook of submitted steps (0 for
+// what the host path redoes or enqueues again).
+static int enqueue_chain_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, bool first_half_only, int debug_fault_every,
+                              int q0, int Sn, unsigned seq) {
   vo_ctx* ctx = p->ctx;
   const vo_pipeline_config& c = p->cfg;
   hipStream_t st = ctx->stream;
   const bool harris = c.tracker_mode == 2;
-  const size_t row = (size_t)p->desc_row;
-  const vo_feat A = p->F[f.fcur], B = p->F[1 - f.fcur];
-  const uint8_t* descA = p->d_fdesc + (size_t)f.fcur * p->cap * row;
-  uint8_t* descB = p->d_fdesc + (size_t)(1 - f.fcur) * p->cap * row;
-  const uint8_t* sdesc = p->d_sdesc + (size_t)f.b * p->sift_cap * row;
+  const size_t row = (size_t)p->desc_row, q = (size_t)q0;
+  const vo_feat A = vo_feat_seq(p->F[f.fcur], q), B = vo_feat_seq(p->F[1 - f.fcur], q);
+  const uint8_t* descA = p->fdesc(f.fcur, q0);
+  uint8_t* descB = p->fdesc(1 - f.fcur, q0);
+  const uint8_t* sdesc = p->sdesc(f.b, q0);
   const float* skp = p->d_skp + (size_t)f.b * p->sift_cap * 6;
-  int32_t* n_new = p->d_sn + f.b;
-  int32_t* n_pairs = p->d_sn + 3;
+  int32_t* n_new = p->sn(f.b, q0);
+  int32_t* n_pairs = p->npairs(q0);
+  int32_t* pairs = p->d_pairs + q * p->cap * 2;
+  int32_t* src_row = p->d_srcrow + q * p->cap;
+  vo_seq_ctl* ctl = p->d_ctl + q0;
+  static_assert(sizeof(vo_seq_ctl) % 4 == 0, "control blocks are read as int arrays");
   VO_HIP_TRY(ctx, hipStreamWaitEvent(st, p->evPyr[f.b], 0));
   const double ratio = c.match_ratio > 0.0 ? c.match_ratio : (harris ? 0.85 : 0.8);        // harris.py:255 / sift.py:49
-  VO_TRY(vo_match_u8_dev(ctx, descA, &p->d_ctl->n, p->cap, sdesc, n_new, p->sift_cap, ratio, p->d_pairs, n_pairs, p->desc_row));
+  VO_TRY(vo_match_u8_batch_dev(ctx, descA, (size_t)p->cap * row, &ctl->n, (int)(sizeof(vo_seq_ctl) / 4), p->cap, sdesc,
+                               (size_t)p->sift_cap * row, n_new, 1, p->sift_cap, Sn, ratio, pairs, n_pairs, p->desc_row));
   const double* new_kp = p->d_newkp;
+  vo_pairs_batch bt;
+  bt.pairs = (size_t)p->cap * 2;
+  bt.src_row = (size_t)p->cap;
+  bt.M = 1;
+  bt.n2 = 1;
+  bt.debug_fault_every = debug_fault_every > 0 ? debug_fault_every : 0;
   if (harris) {
-    new_kp = p->kp(0, f.b);            // the detector's keypoints are float64 pairs already
+    new_kp = p->kp(q0, f.b);           // the detector's keypoints are float64 pairs already
+    bt.new_kp = p->det_stride();
   } else {
     hipLaunchKernelGGL(sift_kp_f64_kernel, dim3(vo_cdiv(p->sift_cap, 256)), dim3(256), 0, st, skp, (const int*)n_new, p->sift_cap,
                        p->d_newkp);
     VO_TRY(vo_check_launch(ctx, "sift_kp_f64_kernel"));
   }
-  VO_TRY(vo_state_regroup_pairs(ctx, p->d_ctl, A, B, p->d_pairs, p->cap, new_kp, p->sift_cap, p->cap, n_pairs, n_new,
-                                p->d_srcrow));
-  hipLaunchKernelGGL(desc_gather_kernel, dim3(vo_cdiv(p->cap * (p->desc_row / 4), 256)), dim3(256), 0, st, sdesc,
-                     (const int*)p->d_srcrow, (const vo_seq_ctl*)p->d_ctl, p->cap, descB, p->desc_row / 4);
+  VO_TRY(vo_state_regroup_pairs(ctx, ctl, A, B, pairs, p->cap, new_kp, p->sift_cap, p->cap, n_pairs, n_new, src_row, Sn, &bt));
+  hipLaunchKernelGGL(desc_gather_kernel, dim3(vo_cdiv(p->cap * (p->desc_row / 4), 256), Sn), dim3(256), 0, st, sdesc,
+                     (const int*)src_row, (const vo_seq_ctl*)ctl, p->cap, descB, p->desc_row / 4,
+                     (size_t)p->sift_cap * row, (size_t)p->cap * row);
   VO_TRY(vo_check_launch(ctx, "desc_gather_kernel"));
   VO_HIP_TRY(ctx, hipEventRecord(p->evRegroup[f.k & 1], st));
   if (first_half_only) return VO_OK;
-  return enqueue_pose_half(p, f, 0, 1, seq);
+  return enqueue_pose_half(p, f, q0, Sn, seq);
 }
 
 // ---- detection worker ----
@@ -1472,9 +1502,14 @@ int vo_pipeline_set_state(vo_pipeline* p, int idx, int n, const double* kp, cons
 }
 
 int vo_pipeline_set_descriptors(vo_pipeline* p, const float* desc, int n) {
+  return vo_pipeline_set_descriptors_seq(p, 0, desc, n);
+}
+
+int vo_pipeline_set_descriptors_seq(vo_pipeline* p, int seq, const float* desc, int n) {
   if (!p) return VO_EINVAL;
   vo_ctx* ctx = p->ctx;
   VO_REQUIRE(ctx, p->cfg.tracker_mode != 0, "pipeline_set_descriptors: the pipeline is not in a descriptor tracker mode");
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_set_descriptors: bad sequence index");
   VO_REQUIRE(ctx, p->have_state && p->n_flight == 0, "pipeline_set_descriptors: hand the state over first (nothing in flight)");
   VO_REQUIRE(ctx, n >= 0 && n <= p->cap && (n == 0 || desc), "pipeline_set_descriptors: bad arguments");
   const int D = p->cfg.tracker_mode == 2 ? 361 : 128;     // values per row handed in; rows are padded to desc_row bytes
@@ -1486,8 +1521,29 @@ int vo_pipeline_set_descriptors(vo_pipeline* p, const float* desc, int n) {
       b[(size_t)i * p->desc_row + k] = (uint8_t)v;
     }
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (n > 0)
-    VO_HIP_TRY(ctx, mcpy(ctx->stream, p->d_fdesc + (size_t)p->cur * p->cap * p->desc_row, b.data(), b.size(), hipMemcpyHostToDevice));
+  if (n > 0) VO_HIP_TRY(ctx, mcpy(ctx->stream, p->fdesc(p->cur, seq), b.data(), b.size(), hipMemcpyHostToDevice));
+  return VO_OK;
+}
+
+// the inverse of vo_pipeline_set_descriptors_seq: the current Features' n rows of sequence seq as whole-number floats
+int vo_pipeline_get_descriptors_seq(vo_pipeline* p, int seq, float* desc, int32_t* n_out) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, p->cfg.tracker_mode != 0, "pipeline_get_descriptors: the pipeline is not in a descriptor tracker mode");
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_get_descriptors: bad sequence index");
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_get_descriptors: %d submitted step(s) not collected", p->n_flight);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  int32_t n = 0;
+  VO_HIP_TRY(ctx, mcpy(st, &n, &p->d_ctl[seq].n, 4, hipMemcpyDeviceToHost));
+  n = std::max(0, std::min(n, p->cap));
+  if (n_out) *n_out = n;
+  if (!desc || n == 0) return VO_OK;
+  const int D = p->cfg.tracker_mode == 2 ? 361 : 128;
+  std::vector<uint8_t> b((size_t)n * p->desc_row);
+  VO_HIP_TRY(ctx, mcpy(st, b.data(), p->fdesc(p->cur, seq), b.size(), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < D; ++k) desc[(size_t)i * D + k] = (float)b[(size_t)i * p->desc_row + k];
   return VO_OK;
 }
 
@@ -1525,10 +1581,10 @@ extern "C" int vo_pipeline_checkpoint(vo_pipeline* p) {
   VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_ckpt_feat, (char*)p->feat_mem + (size_t)p->cur * p->feat_block, p->feat_block,
                                  hipMemcpyDeviceToDevice, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_ckpt_ctl, p->d_ctl, (size_t)p->S * sizeof(vo_seq_ctl), hipMemcpyDeviceToDevice, st));
-  if (p->cfg.tracker_mode != 0) {
-    if (!p->d_ckpt_fdesc) VO_TRY(dev_alloc(ctx, &p->d_ckpt_fdesc, (size_t)p->cap * p->desc_row));
-    VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_ckpt_fdesc, p->d_fdesc + (size_t)p->cur * p->cap * p->desc_row, (size_t)p->cap * p->desc_row,
-                                   hipMemcpyDeviceToDevice, st));
+  if (p->cfg.tracker_mode != 0) {      // (every sequence's descriptors: S consecutive blocks)
+    const size_t bytes = (size_t)p->S * p->cap * p->desc_row;
+    if (!p->d_ckpt_fdesc) VO_TRY(dev_alloc(ctx, &p->d_ckpt_fdesc, bytes));
+    VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_ckpt_fdesc, p->fdesc(p->cur, 0), bytes, hipMemcpyDeviceToDevice, st));
   }
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   p->ckpt_frame = p->prev_frame;
@@ -1547,8 +1603,8 @@ extern "C" int vo_pipeline_rewind(vo_pipeline* p) {
   VO_HIP_TRY(ctx, hipMemcpyAsync((char*)p->feat_mem + (size_t)p->cur * p->feat_block, p->d_ckpt_feat, p->feat_block,
                                  hipMemcpyDeviceToDevice, st));
   if (p->cfg.tracker_mode != 0)
-    VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_fdesc + (size_t)p->cur * p->cap * p->desc_row, p->d_ckpt_fdesc,
-                                   (size_t)p->cap * p->desc_row, hipMemcpyDeviceToDevice, st));
+    VO_HIP_TRY(ctx, hipMemcpyAsync(p->fdesc(p->cur, 0), p->d_ckpt_fdesc, (size_t)p->S * p->cap * p->desc_row,
+                                   hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(ctl_rewind_kernel, dim3(vo_cdiv(p->S, 64)), dim3(64), 0, st, p->d_ctl, p->d_ckpt_ctl, p->S);
   VO_TRY(vo_check_launch(ctx, "ctl_rewind_kernel"));
   // the next step's tracker waits for "the previous step's regroup": that event now stands for the restored state
@@ -1733,8 +1789,9 @@ static int sift_flush_chains(vo_pipeline* p, int must_reach = -1) {
       wait_until(50e-6, [&] { return (int)(p->job_done.load(std::memory_order_acquire) - want) >= 0; });
     }
     VO_TRY(worker_check(p));
-    VO_TRY(ensure_raws(p, 0));
-    VO_TRY(enqueue_chain_sift(p, f, false, f.seq));
+    for (int q = 0; q < p->S; ++q) VO_TRY(ensure_raws(p, q));
+    // (the test hook in the Harris mode only: the SIFT mode's chain never had it)
+    VO_TRY(enqueue_chain_sift(p, f, false, p->cfg.tracker_mode == 2 ? p->cfg.debug_fault_every : 0, 0, p->S, f.seq));
     --p->sift_chain_pending;
   }
   return VO_OK;
@@ -1800,7 +1857,7 @@ int vo_pipeline_submit(vo_pipeline* p, int prev_idx, int next_idx) {
         VO_TRY(enqueue_sift(p, f));
       }
     }
-    p->slot_seq[(size_t)f.rslot] = f.seq;
+    for (int q = 0; q < p->S; ++q) p->slot_seq[(size_t)f.rslot * p->S + q] = f.seq;
     p->flight[p->n_flight++] = f;
     ++p->sift_chain_pending;
     VO_TRY(sift_flush_chains(p));
@@ -1974,7 +2031,7 @@ static int recover_step(vo_pipeline* p, const vo_pipeline::flight_t& f, int q, v
       VO_HIP_TRY(ctx, mcpy(st, p->d_det_go + (size_t)f.a * p->S + q, &one, 4, hipMemcpyHostToDevice));
     }
     if (c.tracker_mode != 0) {
-      VO_TRY(enqueue_chain_sift(p, f, true, 0u));      // (the frame's keypoints and descriptors are still in their slot)
+      VO_TRY(enqueue_chain_sift(p, f, true, 0, q, 1, 0u));   // (the frame's keypoints and descriptors are still in their slot)
     } else {
       VO_TRY(enqueue_tracker(p, f, false, q, 1));
       VO_TRY(enqueue_chain(p, f, true, 0, q, 1, 0u));
@@ -2135,20 +2192,18 @@ int vo_pipeline_collect_all(vo_pipeline* p, vo_step_result* outs) {
       continue;
     }
     const bool was_open = out->fault == VO_FAULT_CONTINUE;
-    int rc = was_open ? continue_step(p, f, q, out) : VO_OK;
+    int rc = VO_OK;
+    // Descriptor modes: every flight has its chain before anything is enqueued for this sequence again -- a chain enqueued
+    // only behind the next batch of hypotheses (or the host path) would find the step closed and run the next step once
+    // more for this sequence, from a generator position already moved on.
+    if ((out->fault || was_open) && p->cfg.tracker_mode != 0) rc = sift_flush_chains(p, p->n_flight - 1);
+    if (rc == VO_OK && was_open) rc = continue_step(p, f, q, out);
     if (rc != VO_OK) {
       p->n_flight = 0;
       return rc;
     }
     if (out->fault || was_open) {
       p->gate_resync = true;             // (what is enqueued again below is ordered by events, and so is the next submit)
-      if (p->cfg.tracker_mode != 0) {    // (every flight has its chain before any is enqueued again)
-        rc = sift_flush_chains(p, p->n_flight - 1);
-        if (rc != VO_OK) {
-          p->n_flight = 0;
-          return rc;
-        }
-      }
       rc = out->fault ? recover_step(p, f, q, out) : VO_OK;
       // steps submitted behind it saw the fault and did nothing for this sequence: their main-stream chains are
       // enqueued again for it alone (pyramids and detections are done and still in place)
@@ -2157,7 +2212,7 @@ int vo_pipeline_collect_all(vo_pipeline* p, vo_step_result* outs) {
         p->slot_seq[(size_t)p->flight[k].rslot * p->S + q] = seq;
         rc = ensure_raws(p, q);
         if (p->cfg.tracker_mode != 0) {
-          if (rc == VO_OK) rc = enqueue_chain_sift(p, p->flight[k], false, seq);
+          if (rc == VO_OK) rc = enqueue_chain_sift(p, p->flight[k], false, 0, q, 1, seq);
           continue;
         }
         if (rc == VO_OK) rc = enqueue_tracker(p, p->flight[k], false, q, 1);

@@ -94,6 +94,8 @@ constexpr int RG_MAX_PER = 32;   // items per thread: capacity 32768
 //                 (klt.py:244-278): the new frame holds the kept ones only.
 // PAIRS == true : items are the rows of an explicit (index in frame 1, index among the new keypoints) list;
 //                 new keypoints without a match follow as the unmatched group.
+// PAIRS: one workgroup per sequence (blockIdx.x): its control block, Features blocks, pair list, new keypoints, counts and
+// src_row at the strides of `bt` (vo_state.h, vo_pairs_batch)
 template <bool PAIRS>
 __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat A, vo_feat B,
                                                              const float* __restrict__ next_xy,
@@ -103,11 +105,33 @@ __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restr
                                                              const double* __restrict__ new_kp, int n2_in, int cap,
                                                              const int* __restrict__ d_M = nullptr,
                                                              const int* __restrict__ d_n2 = nullptr,
-                                                             int* __restrict__ src_row = nullptr) {
+                                                             int* __restrict__ src_row = nullptr, vo_pairs_batch bt = {}) {
   __shared__ unsigned long long s_wave[RG_T / 64 + 1];
   __shared__ unsigned s_matched[PAIRS ? 1024 : 1];   // bit per new keypoint (capacity 32768)
+  if (PAIRS && blockIdx.x) {
+    const size_t z = blockIdx.x;
+    ctl += z;
+    A = vo_feat_seq(A, z);
+    B = vo_feat_seq(B, z);
+    pairs += z * bt.pairs;
+    new_kp += z * bt.new_kp;
+    if (d_M) d_M += z * bt.M;
+    if (d_n2) d_n2 += z * bt.n2;
+    if (src_row) src_row += z * bt.src_row;
+  }
   if (ctl->fault) return;
   const int tid = threadIdx.x;
+  if (PAIRS && bt.debug_fault_every > 0 && (ctl->step % bt.debug_fault_every) == bt.debug_fault_every - 1) {
+    __syncthreads();                   // (every thread has read the fault word)
+    if (tid == 0) {                    // test hook: this step leaves the device-only path here (as the KLT regroup's)
+      ctl->fault = VO_FAULT_FORCED;
+      ctl->n_in = 0;
+      ctl->redetected = 0;
+      ctl->few = 0;
+      ctl->n_p3p = 0;
+    }
+    return;
+  }
   if (PAIRS && d_M) {                  // counts that live on the device (SIFT tracker mode of the frame pipeline)
     M = *d_M;
     n2_in = min(*d_n2, cap);
@@ -818,13 +842,15 @@ int vo_state_regroup_klt(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, con
 
 int vo_state_regroup_pairs(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, const int32_t* d_pairs, int M,
                            const double* d_new_kp, int n2_in, int cap, const int32_t* d_M, const int32_t* d_n2,
-                           int32_t* d_src_row) {
+                           int32_t* d_src_row, int S, const vo_pairs_batch* batch) {
   VO_REQUIRE(ctx, cap <= RG_T * RG_MAX_PER && n2_in <= cap && M <= cap, "state_regroup: capacity exceeded");
+  VO_REQUIRE(ctx, S >= 1 && (S == 1 || batch), "state_regroup: several sequences need their strides");
+  const vo_pairs_batch bt = batch ? *batch : vo_pairs_batch{};
   {
     vo_prof_scope ps(ctx, VO_K_STATE_REGROUP);
-    hipLaunchKernelGGL(state_regroup_kernel<true>, dim3(1), dim3(RG_T), 0, ctx->stream, ctl, A, B, (const float*)nullptr,
+    hipLaunchKernelGGL(state_regroup_kernel<true>, dim3(S), dim3(RG_T), 0, ctx->stream, ctl, A, B, (const float*)nullptr,
                        (const uint8_t*)nullptr, (const float*)nullptr, 0.f, d_pairs, M, d_new_kp, n2_in, cap,
-                       (const int*)d_M, (const int*)d_n2, (int*)d_src_row);
+                       (const int*)d_M, (const int*)d_n2, (int*)d_src_row, bt);
   }
   return vo_check_launch(ctx, "state_regroup_kernel");
 }

@@ -204,9 +204,20 @@ int vo_p3p_hypotheses_ring_dev(vo_ctx* ctx, const double* d_X, const double* d_x
 extern "C" int vo_match_u8_dev(vo_ctx* ctx, const uint8_t* d_q, const int32_t* d_nq, int cap_q, const uint8_t* d_t,
                                const int32_t* d_nt, int cap_t, double ratio, int32_t* d_pairs, int32_t* d_npairs,
                                int row_bytes = 128);
+// ... for S sequences in one launch (blockIdx.z = sequence): sequence z's query / train rows at + z * q_stride / t_stride
+// bytes, its counts at d_nq + z * nq_stride / d_nt + z * nt_stride, its pairs at d_pairs + z * 2 * cap_q, its pair count
+// at d_npairs[z]
+extern "C" int vo_match_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride,
+                                     int cap_q, const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride,
+                                     int cap_t, int S, double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes);
 // raw (2r+1)^2 patches of the zero-padded image as BYTES, rows padded with zeros to row_bytes (harris.hip)
 extern "C" int vo_patch_descriptors_u8_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const double* d_kp_xy, int N,
                                            int r, uint8_t* d_desc, int row_bytes);
+// ... for S sequences in one launch: sequence q's image, keypoints and rows at + q * img_stride / kp_stride (doubles) /
+// desc_stride (bytes)
+extern "C" int vo_patch_descriptors_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_img, size_t img_stride, int S, int H, int W,
+                                                 const double* d_kp_xy, size_t kp_stride, int N, int r, uint8_t* d_desc,
+                                                 size_t desc_stride, int row_bytes);
 // the next `count` 32-bit outputs of NumPy's PCG64 Generator (ransac_host.hip); advances *rng
 void vo_rng_raw32(vo_pcg64* rng, int count, uint32_t* out);
 // DLT with a device-resident point count (dlt.hip)

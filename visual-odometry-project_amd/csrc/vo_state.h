@@ -160,9 +160,18 @@ int vo_state_regroup_klt(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, con
 // matches.py:26-212 for an explicit match list (harris / sift trackers, tests)
 // d_M / d_n2 (optional): the pair count and the new frame's keypoint count read on the device (M and n2_in are then the
 // capacities); d_src_row (optional, cap ints): for every feature written to B, the new keypoint it is
+// S > 1: one workgroup per sequence; sequence q uses ctl + q, block q of A / B and the blocks of `batch`
+struct vo_pairs_batch {
+  size_t pairs = 0;              // d_pairs + q * pairs (ints)
+  size_t new_kp = 0;             // d_new_kp + q * new_kp (doubles)
+  size_t src_row = 0;            // d_src_row + q * src_row
+  int M = 0, n2 = 0;             // d_M + q * M, d_n2 + q * n2
+  int debug_fault_every = 0;     // test hook (vo_pipeline_config.debug_fault_every): the step faults here (VO_FAULT_FORCED)
+};
 int vo_state_regroup_pairs(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, const int32_t* d_pairs, int M,
                            const double* d_new_kp, int n2_in, int cap, const int32_t* d_M = nullptr,
-                           const int32_t* d_n2 = nullptr, int32_t* d_src_row = nullptr);
+                           const int32_t* d_n2 = nullptr, int32_t* d_src_row = nullptr, int S = 1,
+                           const vo_pairs_batch* batch = nullptr);
 // main.py:261-268 + state.py:17-50, 135-219: pose, outliers, bearing-angle candidates
 // S > 1: sequence q uses block q of every array (mask rows of `words` 64-bit words)
 int vo_state_candidates(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint64_t* d_best_mask, const vo_cam* d_cams,

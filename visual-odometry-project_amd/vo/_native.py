@@ -159,6 +159,8 @@ _SIGS = {
     "vo_record_check": (_i, [_vp, C.c_uint]),
     "vo_pipeline_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
     "vo_pipeline_set_descriptors": (_i, [_vp, _vp, _i]),
+    "vo_pipeline_set_descriptors_seq": (_i, [_vp, _i, _vp, _i]),
+    "vo_pipeline_get_descriptors_seq": (_i, [_vp, _i, _vp, _vp]),
     "vo_pipeline_checkpoint": (_i, [_vp]),
     "vo_pipeline_rewind": (_i, [_vp]),
     "vo_pipeline_destroy": (None, [_vp]),

@@ -142,8 +142,11 @@ class Pipeline:
         keep, args = self._state_args(features, curr_pose, prev_pose, num_features)
         self.ctx._chk(self.ctx._lib.vo_pipeline_set_state_seq(self._h, int(seq), int(idx), *args))
         if self.tracker in ("sift", "harris"):
-            desc = _c(np.asarray(features.descriptors).reshape(n, 128 if self.tracker == "sift" else 361), np.float32)
-            self.ctx._chk(self.ctx._lib.vo_pipeline_set_descriptors(self._h, _ptr(desc), n))
+            desc = _c(np.asarray(features.descriptors).reshape(n, self._desc_len()), np.float32)
+            self.ctx._chk(self.ctx._lib.vo_pipeline_set_descriptors_seq(self._h, int(seq), _ptr(desc), n))
+
+    def _desc_len(self):
+        return 128 if self.tracker == "sift" else 361
 
     # ---- lanes: many recordings through one pipeline ----
     def set_camera(self, K, seq, Kinv=None):
@@ -206,6 +209,15 @@ class Pipeline:
                     tracks=tracks[:n].reshape(n, 2, 1).copy(), poses=poses[:n].copy(), curr_pose=T, prev_pose=Tp,
                     n_iterations=int(rs.n_iterations), outlier_ratio=float(rs.outlier_ratio),
                     num_features=nf.value)
+
+    def get_descriptors(self, seq=0):
+        """The descriptors the current Features of sequence `seq` carry (descriptor tracker modes; nothing in flight):
+        n x 361 (Harris) or n x 128 (SIFT) float32, whole numbers, in feature order -- what set_state handed over, regrouped
+        with the keypoints since."""
+        n = C.c_int32()
+        desc = np.empty((self.cap, self._desc_len()), np.float32)
+        self.ctx._chk(self.ctx._lib.vo_pipeline_get_descriptors_seq(self._h, int(seq), _ptr(desc), C.byref(n)))
+        return desc[:n.value].copy()
 
     def get_features(self, seq=0):
         """The current frame's features as a vo.primitives.Features object."""
