@@ -285,6 +285,21 @@ int vo_sift(vo_ctx* ctx, const uint8_t* img, int H, int W, int cap, float* kp, f
  * on the device too (one workgroup sorts the cap + ties described rows).                                          */
 int vo_sift_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap, float* d_kp, float* d_desc, uint8_t* d_desc_u8,
                 int32_t* d_n);
+/* [ref: src/vo/features/sift.py:10,17]  detectAndCompute on S images of one size in one set of launches (the image is
+ * the grid's extra dimension; every image has its own scale space, lists and counters).  Image q's results are those of
+ * vo_sift_dev / vo_sift on that image alone, bit for bit.  _dev: image q at d_imgs + q * img_stride bytes; its keypoints
+ * at d_kp + q * kp_stride * 6, its descriptors at d_desc / d_desc_u8 + q * desc_stride * 128 (either may be NULL), its
+ * count in d_n[q]; d_over[q] = 1 when image q's candidate / keypoint lists overflowed (d_over may be NULL).
+ * vo_sift_batch: as vo_sift per image, imgs S*H*W; image q's rows at kp + q * R * 6, desc + q * R * 128 with R = cap,
+ * or R = vo_sift_capacity(H, W) when cap <= 0; an overflow in any image is VO_ECAPACITY naming the image.  Device
+ * memory grows linearly in S (about 295 MB per 1376x1241 image).                                                     */
+/* S images of one size; results are those of S calls of vo_sift_dev / vo_sift. */
+int vo_sift_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride /* bytes, >= H*W */, int S, int H, int W,
+                      int cap /* 1..4000 */, float* d_kp, size_t kp_stride /* rows, >= cap */, float* d_desc,
+                      uint8_t* d_desc_u8, size_t desc_stride /* rows, >= cap */, int32_t* d_n /* S */,
+                      int32_t* d_over /* S, nullable: 1 = candidate / keypoint list overflow */);
+int vo_sift_batch(vo_ctx* ctx, const uint8_t* imgs /* S*H*W */, int S, int H, int W, int cap, float* kp, float* desc,
+                  int32_t* n /* S */);
 
 /* ---- RANSAC control (host-side, bit-compatible with the reference) --------------
  * [ref: src/vo/algorithms/ransac.py:52, 92-94]  the sample stream of

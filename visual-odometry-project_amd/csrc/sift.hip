@@ -36,6 +36,16 @@ struct skp_t {   // one keypoint row on the device
   int oct, layer;
 };
 
+// A batch of S images of one size (vo_sift_batch_dev; one image is the batch S = 1): every image has blocks of its own,
+// image q's behind image q - 1's at these strides -- its scale space (`arena` floats), its counter block (`cnt` words:
+// C_WORDS counters, then sift_finalize_kernel's row order), its lists of survivors, keypoints, selected rows and
+// described rows (`list` rows each; its EX_SUB candidate lists: EX_SUB * `list` entries) and its hash table (`table`
+// entries).  The octave pointer tables (oct_t, octs_t, pyr_ptrs) describe image 0; a kernel adds q * stride itself.
+struct sift_stride_t {
+  size_t arena;
+  unsigned cnt, list, table;
+};
+
 __device__ __forceinline__ int refl(int c, int n) {
   if (n == 1) return 0;
   while (c < 0 || c >= n) c = c < 0 ? -c : 2 * (n - 1) - c;
@@ -75,8 +85,11 @@ __device__ __forceinline__ float sift_atan2(float y, float x) {
 }
 
 // ---------------- scale space ----------------
-__global__ __launch_bounds__(256) void upsample2_kernel(const uint8_t* __restrict__ img, int H, int W,
-                                                        float* __restrict__ out) {
+// (image blockIdx.z of the batch in this kernel and the other image-wide ones)
+__global__ __launch_bounds__(256) void upsample2_kernel(const uint8_t* __restrict__ img, size_t img_stride, int H, int W,
+                                                        float* __restrict__ out, size_t out_stride) {
+  img += blockIdx.z * img_stride;
+  out += blockIdx.z * out_stride;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int W0 = 2 * W, H0 = 2 * H;
   if (x >= W0 || y >= H0) return;
@@ -112,8 +125,10 @@ struct blur_geom {
 };
 template <int R>
 __global__ __launch_bounds__(256) void blur2d_rb_kernel(const float* __restrict__ src, int H, int W, taps_t k,
-                                                        float* __restrict__ dst) {
+                                                        float* __restrict__ dst, size_t stride) {
   typedef blur_geom<R> G;
+  src += blockIdx.z * stride;
+  dst += blockIdx.z * stride;
   extern __shared__ __align__(16) float blur_smem[];
   float* s_in = blur_smem;                  // RH x PI
   float* s_mid = blur_smem + G::RH * G::PI; // RH x BR_W
@@ -191,8 +206,10 @@ __global__ __launch_bounds__(256) void blur2d_rb_kernel(const float* __restrict_
 
 // any radius (run-time trip counts: every tap waits for its own LDS read)
 __global__ __launch_bounds__(256) void blur2d_kernel(const float* __restrict__ src, int H, int W, taps_t k,
-                                                     float* __restrict__ dst) {
+                                                     float* __restrict__ dst, size_t stride) {
   extern __shared__ __align__(16) float blur_smem[];
+  src += blockIdx.z * stride;
+  dst += blockIdx.z * stride;
   const int r = k.r, PI = BT_W + 2 * r, RH = BT_H + 2 * r;
   float* s_in = blur_smem;                 // RH x PI
   float* s_mid = blur_smem + RH * PI;      // RH x BT_W
@@ -235,7 +252,9 @@ __global__ __launch_bounds__(256) void blur2d_kernel(const float* __restrict__ s
 }
 
 __global__ __launch_bounds__(256) void decimate_kernel(const float* __restrict__ src, int pw, int H, int W,
-                                                       float* __restrict__ dst) {
+                                                       float* __restrict__ dst, size_t stride) {
+  src += blockIdx.z * stride;
+  dst += blockIdx.z * stride;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x < W && y < H) dst[(size_t)y * W + x] = src[(size_t)(2 * y) * pw + 2 * x];
 }
@@ -251,7 +270,7 @@ struct dog_t {
   const float *a, *b;
   __device__ __forceinline__ float operator[](size_t p) const { return b[p] - a[p]; }
 };
-__device__ __forceinline__ dog_t dog_layer(const oct_t& O, int l) { return dog_t{O.g[l], O.g[l + 1]}; }
+__device__ __forceinline__ dog_t dog_layer(const oct_t& O, int l, size_t off) { return dog_t{O.g[l] + off, O.g[l + 1] + off}; }
 struct octs_t {
   oct_t o[MAX_OCT];
 };
@@ -272,9 +291,12 @@ constexpr int EX_SUB = 32, C_SUB = 16, C_WORDS = C_SUB + 32 * EX_SUB;
 // octave 0: 0.6 TB/s for 164 MB.)
 constexpr int EX_W = 64, EX_H = 16, EX_PW = EX_W + 2, EX_PH = EX_H + 2;
 __global__ __launch_bounds__(256) void extrema_kernel(oct_t O, float threshold, int4* __restrict__ cand,
-                                                      unsigned* __restrict__ sub_cnt, unsigned subcap) {
+                                                      unsigned* __restrict__ sub_cnt, unsigned subcap, sift_stride_t ss) {
   __shared__ float s_d[NG - 1][EX_PH][EX_PW];
   const int tid = threadIdx.x;
+  const size_t off = blockIdx.z * ss.arena;
+  cand += (size_t)blockIdx.z * EX_SUB * ss.list;
+  sub_cnt += blockIdx.z * ss.cnt;
   const unsigned tile = vo_xcd_tile(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
   const int x0 = (int)(tile % gridDim.x) * EX_W, y0 = (int)(tile / gridDim.x) * EX_H;
   unsigned* n_cand = sub_cnt + 32u * (tile % (unsigned)EX_SUB);
@@ -289,7 +311,7 @@ __global__ __launch_bounds__(256) void extrema_kernel(oct_t O, float threshold, 
       const int gy = min(max(y0 - 1 + ly, 0), O.H - 1), gx = min(max(x0 - 1 + lx, 0), O.W - 1);   // (clamped entries are never a
       const size_t p = (size_t)gy * O.W + gx;                                                     //  neighbour of a tested centre)
 #pragma unroll
-      for (int l = 0; l < NG; ++l) gv[u][l] = O.g[l][p];
+      for (int l = 0; l < NG; ++l) gv[u][l] = O.g[l][p + off];
     }
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
@@ -412,7 +434,15 @@ __global__ __launch_bounds__(256) void refine_kernel(octs_t OS, const int4* __re
                                                      float contrast_thr, float edge_thr, float sigma,
                                                      unsigned long long* __restrict__ table, unsigned table_mask,
                                                      surv_t* __restrict__ out, unsigned* __restrict__ n_out,
-                                                     unsigned cap_out) {
+                                                     unsigned cap_out, sift_stride_t ss) {
+  // (image blockIdx.y of the batch, here and in the other fixed-grid and per-image kernels)
+  const unsigned im = blockIdx.y;
+  const size_t off = im * ss.arena;
+  cand += (size_t)im * EX_SUB * ss.list;
+  sub_cnt += im * ss.cnt;
+  table += (size_t)im * ss.table;
+  out += (size_t)im * ss.list;
+  n_out += im * ss.cnt;
   // candidate v of the EX_SUB lists taken one behind the other
   unsigned first[EX_SUB + 1];
   first[0] = 0;
@@ -433,7 +463,7 @@ __global__ __launch_bounds__(256) void refine_kernel(octs_t OS, const int4* __re
     int i;
     bool dead = false;
     for (i = 0; i < 5; ++i) {
-      const dog_t img = dog_layer(O, layer), prv = dog_layer(O, layer - 1), nxt = dog_layer(O, layer + 1);
+      const dog_t img = dog_layer(O, layer, off), prv = dog_layer(O, layer - 1, off), nxt = dog_layer(O, layer + 1, off);
       const size_t p = (size_t)r * W + c;
       float dD[3] = {(img[p + 1] - img[p - 1]) * deriv_scale, (img[p + W] - img[p - W]) * deriv_scale,
                      (nxt[p] - prv[p]) * deriv_scale};
@@ -468,7 +498,7 @@ __global__ __launch_bounds__(256) void refine_kernel(octs_t OS, const int4* __re
     if (dead || i >= 5) continue;
     surv_t sv;
     {
-      const dog_t img = dog_layer(O, layer), prv = dog_layer(O, layer - 1), nxt = dog_layer(O, layer + 1);
+      const dog_t img = dog_layer(O, layer, off), prv = dog_layer(O, layer - 1, off), nxt = dog_layer(O, layer + 1, off);
       const size_t p = (size_t)r * W + c;
       const float d0 = (img[p + 1] - img[p - 1]) * deriv_scale, d1 = (img[p + W] - img[p - W]) * deriv_scale,
                   d2 = (nxt[p] - prv[p]) * deriv_scale;
@@ -555,7 +585,7 @@ constexpr int ORI_WAVES = 4, ORI_BUF = 96;
 __global__ __launch_bounds__(64 * ORI_WAVES) void orient_kernel(octs_t OS, const surv_t* __restrict__ surv,
                                                                 const unsigned* __restrict__ n_surv, unsigned cap_surv,
                                                                 skp_t* __restrict__ out, unsigned* __restrict__ n_out,
-                                                                unsigned cap_out) {
+                                                                unsigned cap_out, sift_stride_t ss) {
   __shared__ float s_add_w[ORI_WAVES][64];
   __shared__ float s_tmp_w[ORI_WAVES][36];
   __shared__ float s_patch_w[ORI_WAVES][(2 * ORI_RMAX + 3) * (2 * ORI_RMAX + 3)];
@@ -565,6 +595,12 @@ __global__ __launch_bounds__(64 * ORI_WAVES) void orient_kernel(octs_t OS, const
   float* s_add = s_add_w[wv];
   float* s_tmp = s_tmp_w[wv];
   float* s_patch = s_patch_w[wv];
+  const unsigned im = blockIdx.y;
+  const size_t off = im * ss.arena;
+  surv += (size_t)im * ss.list;
+  n_surv += im * ss.cnt;
+  out += (size_t)im * ss.list;
+  n_out += im * ss.cnt;
   if (threadIdx.x == 0) s_nbuf = 0;
   __syncthreads();
   const unsigned n = min(*n_surv, cap_surv);
@@ -575,7 +611,7 @@ __global__ __launch_bounds__(64 * ORI_WAVES) void orient_kernel(octs_t OS, const
     const float scl_octv = sv.kp.size * 0.5f / (float)(1 << O.o);
     const int radius = (int)rintf(4.5f * scl_octv);
     const float osig = 1.5f * scl_octv;
-    const float* g = O.g[sv.kp.layer];
+    const float* g = O.g[sv.kp.layer] + off;
     const float expf_scale = -1.f / (2.f * osig * osig);
     const int side = 2 * radius + 1, total = side * side;
     const bool staged = radius <= ORI_RMAX;
@@ -677,10 +713,15 @@ __global__ __launch_bounds__(64 * ORI_WAVES) void orient_kernel(octs_t OS, const
 // workgroup: three radix passes over the response bits (positive floats order like their bit patterns).
 __global__ __launch_bounds__(1024) void select_kernel(const skp_t* __restrict__ kps, const unsigned* __restrict__ n_kp,
                                                       unsigned cap_kp, unsigned cap, unsigned* __restrict__ sel,
-                                                      unsigned* __restrict__ n_sel) {
+                                                      unsigned* __restrict__ n_sel, sift_stride_t ss) {
   __shared__ unsigned s_hist[2048], s_scan[1024];
   __shared__ unsigned s_prefix, s_need, s_cnt;
   const int tid = threadIdx.x;
+  const unsigned im = blockIdx.y;
+  kps += (size_t)im * ss.list;
+  n_kp += im * ss.cnt;
+  sel += (size_t)im * ss.list;
+  n_sel += im * ss.cnt;
   const unsigned n = min(*n_kp, cap_kp);
   unsigned thr_bits = 0u;
   if (n > cap) {
@@ -754,12 +795,18 @@ constexpr int DESC_T = 256, DESC_VP = 9;           // work items; pitch of a sam
 __global__ __launch_bounds__(DESC_T) void descriptor_kernel(pyr_ptrs P, const skp_t* __restrict__ kps,
                                                             const unsigned* __restrict__ sel,
                                                             const unsigned* __restrict__ n_sel,
-                                                            float* __restrict__ rows /* n x 134 */) {
+                                                            float* __restrict__ rows /* n x 134 */, sift_stride_t ss) {
   __shared__ float s_v[DESC_T * DESC_VP];
   __shared__ unsigned long long s_m[DESC_T / 64][18];   // per wave: 5 row ballots, 5 column ballots, 8 orientation ballots
   __shared__ float s_hist[16][10];
   __shared__ float s_patch[(2 * DESC_RMAX + 3) * (2 * DESC_RMAX + 3)];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const unsigned im = blockIdx.y;
+  const size_t off = im * ss.arena;
+  kps += (size_t)im * ss.list;
+  sel += (size_t)im * ss.list;
+  n_sel += im * ss.cnt;
+  rows += (size_t)im * ss.list * 134;
   const unsigned n = *n_sel;
   const int d = 4, n8 = 8;
   // the bin work item tid < 144 owns: inner cell (cr, cc) in 1..4, orientation bin ob in 0..8
@@ -767,7 +814,7 @@ __global__ __launch_bounds__(DESC_T) void descriptor_kernel(pyr_ptrs P, const sk
   const int cr = 1 + (ci >> 2), cc = 1 + (ci & 3);
   for (unsigned k = blockIdx.x; k < n; k += gridDim.x) {
     const skp_t q = kps[sel[k]];
-    const float* g = P.g[q.oct][q.layer];
+    const float* g = P.g[q.oct][q.layer] + off;
     const int H = P.H[q.oct], W = P.W[q.oct];
     float* row = rows + (size_t)k * 134;
     const float scl = q.size * 0.5f / (float)(1 << q.oct);
@@ -963,7 +1010,9 @@ __global__ __launch_bounds__(DESC_T) void descriptor_kernel(pyr_ptrs P, const sk
   }
 }
 
-__global__ void overflow_kernel(const unsigned* cnt, unsigned subcap, unsigned cap_kp, unsigned* flag) {
+__global__ void overflow_kernel(unsigned* cnt, unsigned subcap, unsigned cap_kp, unsigned cnt_stride) {
+  cnt += blockIdx.y * cnt_stride;
+  unsigned* flag = cnt + C_OVER;
   bool over = cnt[C_SURV] > cap_kp || cnt[C_KP] > cap_kp;
   for (int j = 0; j < EX_SUB; ++j) over = over || cnt[C_SUB + 32 * j] > subcap;
   if (over) *flag = 1u;
@@ -1028,8 +1077,14 @@ __device__ __forceinline__ unsigned block_scan4(const unsigned (&f)[4], unsigned
 
 __global__ __launch_bounds__(FIN_T) void sift_finalize_kernel(const float* __restrict__ rows, const unsigned* __restrict__ n_rows,
                                                               int cap, unsigned* __restrict__ src_out, int* __restrict__ n_out,
-                                                              unsigned* __restrict__ overflow) {
+                                                              unsigned* __restrict__ overflow, sift_stride_t ss) {
   extern __shared__ __align__(16) unsigned s_fin[];
+  const unsigned im = blockIdx.y;                // (n_out: one int per image)
+  rows += (size_t)im * ss.list * 134;
+  n_rows += im * ss.cnt;
+  src_out += im * ss.cnt;
+  overflow += im * ss.cnt;
+  n_out += im;
   unsigned* s_key = s_fin;                       // [FIN_MAX][4]
   unsigned* s_row = s_key + 4 * FIN_MAX;         // [FIN_MAX] row number at this sorted position
   __shared__ unsigned s_wave[FIN_T / 64];
@@ -1152,14 +1207,30 @@ __global__ __launch_bounds__(FIN_T) void sift_finalize_kernel(const float* __res
 
 __global__ __launch_bounds__(128) void sift_gather_kernel(const float* __restrict__ rows, const unsigned* __restrict__ src,
                                                           const int* __restrict__ n_out, float* __restrict__ kp_out,
-                                                          float* __restrict__ desc_out, uint8_t* __restrict__ desc_bytes) {
-  const unsigned d = blockIdx.x, c = threadIdx.x;
+                                                          float* __restrict__ desc_out, uint8_t* __restrict__ desc_bytes,
+                                                          sift_stride_t ss, size_t kp_stride, size_t desc_stride) {
+  const unsigned d = blockIdx.x, c = threadIdx.x, im = blockIdx.y;
+  rows += (size_t)im * ss.list * 134;
+  src += im * ss.cnt;
+  n_out += im;
+  kp_out += im * kp_stride * 6;
+  if (desc_out) desc_out += im * desc_stride * 128;
+  if (desc_bytes) desc_bytes += im * desc_stride * 128;
   if ((int)d >= *n_out) return;
   const float* r = rows + (size_t)src[d] * 134;
   const float v = r[6 + c];
   if (desc_out) desc_out[(size_t)d * 128 + c] = v;
   if (desc_bytes) desc_bytes[(size_t)d * 128 + c] = (uint8_t)v;     // (whole numbers 0..255 by construction)
   if (c < 6) kp_out[(size_t)d * 6 + c] = r[c];
+}
+
+// per image of a batch: its overflow flag -> over[q] (nullable), its described-row count -> n_sel[q] (nullable)
+__global__ __launch_bounds__(256) void sift_counts_kernel(const unsigned* __restrict__ cnt, unsigned cnt_stride, int S,
+                                                          int32_t* __restrict__ over, unsigned* __restrict__ n_sel) {
+  for (int q = threadIdx.x; q < S; q += 256) {
+    if (over) over[q] = (int32_t)cnt[(size_t)q * cnt_stride + C_OVER];
+    if (n_sel) n_sel[q] = cnt[(size_t)q * cnt_stride + C_SEL];
+  }
 }
 
 taps_t make_taps(double sigma) {
@@ -1199,12 +1270,14 @@ int vo_sift_capacity(int H, int W) {
   return (int)(c < 65536 ? 65536 : (c > (1 << 20) ? (1 << 20) : c));
 }
 
-// Everything up to the described rows, enqueued on the context's stream (no host synchronisation): d_img is the frame in
-// device memory; the rows (134 floats each: x, y, size, angle, response, octave, 128 descriptor values) are left in the
-// context's scratch[3], their count in scratch[2][C_SEL], an overflow flag in scratch[2][C_OVER].
-static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap) {
-  hipStream_t st = ctx->stream;
-  const float sigma = 1.6f, contrast_thr = 0.04f, edge_thr = 10.f;
+// The octave count and the per-image block sizes (sift_stride_t) of an H x W image.
+struct sift_geom {
+  int n_oct;
+  unsigned cap_kp, table_len;
+  sift_stride_t ss;
+};
+static sift_geom sift_geometry(int H, int W) {
+  sift_geom g;
   const int W0 = 2 * W, H0 = 2 * H;
   int n_oct = (int)std::lrint(std::log((double)std::min(W0, H0)) / std::log(2.0) - 2);
   n_oct = std::min(n_oct, MAX_OCT);
@@ -1227,20 +1300,42 @@ static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap
       h /= 2;
     }
   }
-  const unsigned cap_kp = (unsigned)vo_sift_capacity(H, W), subcap = cap_kp, cap_cand = (unsigned)EX_SUB * subcap;
-  VO_TRY(vo_ensure(ctx, ctx->sift_arena, total * 4));
+  g.n_oct = n_oct;
+  g.cap_kp = (unsigned)vo_sift_capacity(H, W);
   unsigned table_len = 1;
-  while (table_len < 4u * cap_kp) table_len <<= 1;
-  VO_TRY(vo_ensure(ctx, ctx->scratch[0], (size_t)cap_cand * 16));
-  VO_TRY(vo_ensure(ctx, ctx->scratch[1], (size_t)cap_kp * sizeof(skp_t)));
-  VO_TRY(vo_ensure(ctx, ctx->scratch[2], ((size_t)C_WORDS + FIN_MAX) * 4));   // counters, then sift_finalize's row order
-  VO_TRY(vo_ensure(ctx, ctx->scratch[3], (size_t)cap_kp * 134 * 4));
-  VO_TRY(vo_ensure(ctx, ctx->scratch[4], (size_t)cap_kp * sizeof(surv_t)));
-  VO_TRY(vo_ensure(ctx, ctx->scratch[5], (size_t)table_len * 8));
-  VO_TRY(vo_ensure(ctx, ctx->scratch[6], (size_t)cap_kp * 4));
+  while (table_len < 4u * g.cap_kp) table_len <<= 1;
+  g.table_len = table_len;
+  g.ss.arena = total;
+  g.ss.cnt = C_WORDS + FIN_MAX;   // counters, then sift_finalize's row order
+  g.ss.list = g.cap_kp;
+  g.ss.table = table_len;
+  return g;
+}
+
+// Everything up to the described rows of S images of one size (image q at d_imgs + q * img_stride), enqueued on the
+// context's stream (no host synchronisation).  Image q's rows (134 floats each: x, y, size, angle, response, octave, 128
+// descriptor values) are left in the context's scratch[3] at q * list rows, its count in its counter block (scratch[2] at
+// q * cnt words) at C_SEL, an overflow flag at C_OVER.  S = 1 is the one-image launch sequence.
+static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, int cap) {
+  hipStream_t st = ctx->stream;
+  const float sigma = 1.6f, contrast_thr = 0.04f, edge_thr = 10.f;
+  const int W0 = 2 * W, H0 = 2 * H;
+  const sift_geom gm = sift_geometry(H, W);
+  const int n_oct = gm.n_oct;
+  const sift_stride_t ss = gm.ss;
+  const unsigned cap_kp = gm.cap_kp, subcap = cap_kp, cap_cand = (unsigned)EX_SUB * subcap, table_len = gm.table_len;
+  const size_t Sz = (size_t)S;
+  VO_TRY(vo_ensure(ctx, ctx->sift_arena, Sz * ss.arena * 4));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[0], Sz * cap_cand * 16));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[1], Sz * cap_kp * sizeof(skp_t)));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[2], Sz * ss.cnt * 4));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[3], Sz * cap_kp * 134 * 4));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[4], Sz * cap_kp * sizeof(surv_t)));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[5], Sz * table_len * 8));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[6], Sz * cap_kp * 4));
   unsigned* d_cnt = (unsigned*)ctx->scratch[2].p;   // counters of this call, see C_CAND ..
-  VO_HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, (size_t)C_WORDS * 4, st));
-  VO_HIP_TRY(ctx, hipMemsetAsync(ctx->scratch[5].p, 0, (size_t)table_len * 8, st));
+  VO_HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, ((Sz - 1) * ss.cnt + C_WORDS) * 4, st));
+  VO_HIP_TRY(ctx, hipMemsetAsync(ctx->scratch[5].p, 0, Sz * table_len * 8, st));
 
   float* arena = (float*)ctx->sift_arena.p;
   float* cur = arena;
@@ -1273,24 +1368,26 @@ static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap
       taps[i] = make_taps(std::sqrt(s2 * s2 - sp * sp));
     }
   }
-  auto grid2 = [](int w, int h) { return dim3(vo_cdiv(w, 64), vo_cdiv(h, 4)); };
+  const size_t as = ss.arena;
+  auto grid2 = [S](int w, int h) { return dim3(vo_cdiv(w, 64), vo_cdiv(h, 4), S); };
   auto blur = [&](hipStream_t on, const float* src, int h, int w, const taps_t& t, float* dst) {
-    const dim3 grid(vo_cdiv(w, BR_W), vo_cdiv(h, BR_H));
+    const dim3 grid(vo_cdiv(w, BR_W), vo_cdiv(h, BR_H), S);
     switch (t.r) {   // the radii of cv2.SIFT_create()'s default sigma
-      case 5: hipLaunchKernelGGL(blur2d_rb_kernel<5>, grid, dim3(256), blur_geom<5>::lds, on, src, h, w, t, dst); break;
-      case 6: hipLaunchKernelGGL(blur2d_rb_kernel<6>, grid, dim3(256), blur_geom<6>::lds, on, src, h, w, t, dst); break;
-      case 8: hipLaunchKernelGGL(blur2d_rb_kernel<8>, grid, dim3(256), blur_geom<8>::lds, on, src, h, w, t, dst); break;
-      case 10: hipLaunchKernelGGL(blur2d_rb_kernel<10>, grid, dim3(256), blur_geom<10>::lds, on, src, h, w, t, dst); break;
-      case 13: hipLaunchKernelGGL(blur2d_rb_kernel<13>, grid, dim3(256), blur_geom<13>::lds, on, src, h, w, t, dst); break;
+      case 5: hipLaunchKernelGGL(blur2d_rb_kernel<5>, grid, dim3(256), blur_geom<5>::lds, on, src, h, w, t, dst, as); break;
+      case 6: hipLaunchKernelGGL(blur2d_rb_kernel<6>, grid, dim3(256), blur_geom<6>::lds, on, src, h, w, t, dst, as); break;
+      case 8: hipLaunchKernelGGL(blur2d_rb_kernel<8>, grid, dim3(256), blur_geom<8>::lds, on, src, h, w, t, dst, as); break;
+      case 10: hipLaunchKernelGGL(blur2d_rb_kernel<10>, grid, dim3(256), blur_geom<10>::lds, on, src, h, w, t, dst, as); break;
+      case 13: hipLaunchKernelGGL(blur2d_rb_kernel<13>, grid, dim3(256), blur_geom<13>::lds, on, src, h, w, t, dst, as); break;
       default:
-        hipLaunchKernelGGL(blur2d_kernel, dim3(vo_cdiv(w, BT_W), vo_cdiv(h, BT_H)), dim3(256),
-                           (size_t)(BT_H + 2 * t.r) * (2 * BT_W + 2 * t.r) * 4, on, src, h, w, t, dst);
+        hipLaunchKernelGGL(blur2d_kernel, dim3(vo_cdiv(w, BT_W), vo_cdiv(h, BT_H), S), dim3(256),
+                           (size_t)(BT_H + 2 * t.r) * (2 * BT_W + 2 * t.r) * 4, on, src, h, w, t, dst, as);
         break;
     }
   };
   // Octave o + 1 starts from layer NOL of octave o: the chain  base -> g1..g3 -> decimate -> g1..g3 -> ...  is the
   // critical path (the small octaves are a launch latency each); the last two layers of every octave and its extrema
-  // search run beside it: octave 0's (two thirds of that work) on one stream, the smaller octaves' on another.
+  // search run beside it: octave 0's (two thirds of that work) on one stream, the smaller octaves' on another.  Every
+  // launch covers the S images of the batch (grid z).
   if (!ctx->aux_stream) VO_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
   if (!ctx->aux_stream2) VO_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream2, hipStreamNonBlocking));
   while ((int)ctx->aux_events.size() < MAX_OCT + 2) {
@@ -1303,7 +1400,7 @@ static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap
     vo_prof_scope ps(ctx, VO_K_SIFT_SCALESPACE);
     // base image: doubled, blurred to sigma
     float* up = const_cast<float*>(oct[0].g[1]);   // scratch until g[1] is produced
-    hipLaunchKernelGGL(upsample2_kernel, grid2(W0, H0), dim3(256), 0, st, d_img, H, W, up);
+    hipLaunchKernelGGL(upsample2_kernel, grid2(W0, H0), dim3(256), 0, st, d_imgs, img_stride, H, W, up, as);
     blur(st, up, H0, W0, taps[0], const_cast<float*>(oct[0].g[0]));
     // the dependent chain first, the side work behind it.  (The host's launch rate, ~6 us per call, is what the small
     // octaves wait for; the same ~75 launches captured once and replayed with hipGraphLaunch were no faster: 552
@@ -1312,7 +1409,7 @@ static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap
       const int w = oct[o].W, h = oct[o].H;
       if (o > 0)
         hipLaunchKernelGGL(decimate_kernel, grid2(w, h), dim3(256), 0, st, oct[o - 1].g[NOL], oct[o - 1].W, h, w,
-                           const_cast<float*>(oct[o].g[0]));
+                           const_cast<float*>(oct[o].g[0]), as);
       for (int i = 1; i <= NOL; ++i) blur(st, oct[o].g[i - 1], h, w, taps[i], const_cast<float*>(oct[o].g[i]));
       VO_HIP_TRY(ctx, hipEventRecord(ctx->aux_events[o], st));
     }
@@ -1321,8 +1418,8 @@ static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap
       hipStream_t sb = o == 0 ? ctx->aux_stream : ctx->aux_stream2;
       VO_HIP_TRY(ctx, hipStreamWaitEvent(sb, ctx->aux_events[o], 0));
       for (int i = NOL + 1; i < NG; ++i) blur(sb, oct[o].g[i - 1], h, w, taps[i], const_cast<float*>(oct[o].g[i]));
-      hipLaunchKernelGGL(extrema_kernel, dim3(vo_cdiv(w, EX_W), vo_cdiv(h, EX_H)), dim3(256), 0, sb, oct[o], threshold, (int4*)ctx->scratch[0].p,
-                         d_cnt + C_SUB, subcap);
+      hipLaunchKernelGGL(extrema_kernel, dim3(vo_cdiv(w, EX_W), vo_cdiv(h, EX_H), S), dim3(256), 0, sb, oct[o], threshold,
+                         (int4*)ctx->scratch[0].p, d_cnt + C_SUB, subcap, ss);
     }
     VO_HIP_TRY(ctx, hipEventRecord(ctx->aux_events[MAX_OCT], ctx->aux_stream));
     VO_HIP_TRY(ctx, hipEventRecord(ctx->aux_events[MAX_OCT + 1], ctx->aux_stream2));
@@ -1337,29 +1434,34 @@ static int sift_enqueue(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap
   octs_t OS;
   memset(&OS, 0, sizeof(OS));
   for (int o = 0; o < n_oct; ++o) OS.o[o] = oct[o];
+  // workgroups per image of the fixed-grid stages: the one-image grids at S = 1, shared out among the images above
+  // (the order of a list before finalize is arbitrary and finalize sorts on the whole row: the grid cannot change results)
+  const int g_fix = std::max(1024 / S, 64), g_desc = std::max(2048 / S, 128);
   {
     vo_prof_scope ps(ctx, VO_K_SIFT_DETECT);
     // counts stay on the device: fixed grids, every kernel strides over what the one before it produced
-    hipLaunchKernelGGL(refine_kernel, dim3(1024), dim3(256), 0, st, OS, (const int4*)ctx->scratch[0].p, d_cnt + C_SUB,
+    hipLaunchKernelGGL(refine_kernel, dim3(g_fix, S), dim3(256), 0, st, OS, (const int4*)ctx->scratch[0].p, d_cnt + C_SUB,
                        subcap, contrast_thr, edge_thr, sigma, (unsigned long long*)ctx->scratch[5].p, table_len - 1,
-                       d_surv, d_cnt + C_SURV, cap_kp);
-    hipLaunchKernelGGL(orient_kernel, dim3(1024), dim3(64 * ORI_WAVES), 0, st, OS, d_surv, d_cnt + C_SURV, cap_kp, d_kps, d_cnt + C_KP,
-                       cap_kp);
-    hipLaunchKernelGGL(overflow_kernel, dim3(1), dim3(1), 0, st, d_cnt, subcap, cap_kp, d_cnt + C_OVER);
-    hipLaunchKernelGGL(select_kernel, dim3(1), dim3(1024), 0, st, d_kps, d_cnt + C_KP, cap_kp, (unsigned)cap, d_sel,
-                       d_cnt + C_SEL);
+                       d_surv, d_cnt + C_SURV, cap_kp, ss);
+    hipLaunchKernelGGL(orient_kernel, dim3(g_fix, S), dim3(64 * ORI_WAVES), 0, st, OS, d_surv, d_cnt + C_SURV, cap_kp, d_kps,
+                       d_cnt + C_KP, cap_kp, ss);
+    hipLaunchKernelGGL(overflow_kernel, dim3(1, S), dim3(1), 0, st, d_cnt, subcap, cap_kp, ss.cnt);
+    hipLaunchKernelGGL(select_kernel, dim3(1, S), dim3(1024), 0, st, d_kps, d_cnt + C_KP, cap_kp, (unsigned)cap, d_sel,
+                       d_cnt + C_SEL, ss);
   }
   VO_TRY(vo_check_launch(ctx, "sift detection"));
   {
     vo_prof_scope ps(ctx, VO_K_SIFT_DESCRIBE);
-    hipLaunchKernelGGL(descriptor_kernel, dim3(2048), dim3(DESC_T), 0, st, P, d_kps, d_sel, d_cnt + C_SEL, d_rows);
+    hipLaunchKernelGGL(descriptor_kernel, dim3(g_desc, S), dim3(DESC_T), 0, st, P, d_kps, d_sel, d_cnt + C_SEL, d_rows, ss);
   }
   return vo_check_launch(ctx, "sift descriptor_kernel");
 }
 
-// the final order on the device (sift_finalize_kernel): rows -> d_kp (cap x 6), d_desc (cap x 128 float, nullable),
-// d_desc_u8 (cap x 128 bytes, nullable), d_n
-static int sift_finalize(vo_ctx* ctx, int cap, float* d_kp, float* d_desc, uint8_t* d_desc_u8, int* d_n) {
+// the final order on the device (sift_finalize_kernel), image q of the S enqueued by sift_enqueue: its rows ->
+// d_kp + q * kp_stride rows (6 floats), d_desc / d_desc_u8 + q * desc_stride rows (128 float / bytes, either nullable),
+// d_n[q]
+static int sift_finalize(vo_ctx* ctx, int H, int W, int S, int cap, float* d_kp, size_t kp_stride, float* d_desc,
+                         uint8_t* d_desc_u8, size_t desc_stride, int* d_n) {
   static const size_t lds = (size_t)FIN_MAX * 20;
   static bool opted[64] = {false};
   if (ctx->device >= 0 && ctx->device < 64 && !opted[ctx->device]) {
@@ -1367,73 +1469,22 @@ static int sift_finalize(vo_ctx* ctx, int cap, float* d_kp, float* d_desc, uint8
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     opted[ctx->device] = true;
   }
+  const sift_stride_t ss = sift_geometry(H, W).ss;
   unsigned* d_cnt = (unsigned*)ctx->scratch[2].p;
   unsigned* d_src = d_cnt + C_WORDS;                  // sorted position -> row (FIN_MAX words behind the counters)
-  hipLaunchKernelGGL(sift_finalize_kernel, dim3(1), dim3(FIN_T), lds, ctx->stream, (const float*)ctx->scratch[3].p,
-                     d_cnt + C_SEL, cap, d_src, d_n, d_cnt + C_OVER);
+  hipLaunchKernelGGL(sift_finalize_kernel, dim3(1, S), dim3(FIN_T), lds, ctx->stream, (const float*)ctx->scratch[3].p,
+                     d_cnt + C_SEL, cap, d_src, d_n, d_cnt + C_OVER, ss);
   VO_TRY(vo_check_launch(ctx, "sift_finalize_kernel"));
-  hipLaunchKernelGGL(sift_gather_kernel, dim3(cap > 0 ? cap : FIN_MAX), dim3(128), 0, ctx->stream, (const float*)ctx->scratch[3].p,
-                     (const unsigned*)d_src, (const int*)d_n, d_kp, d_desc, d_desc_u8);
+  hipLaunchKernelGGL(sift_gather_kernel, dim3(cap > 0 ? cap : FIN_MAX, S), dim3(128), 0, ctx->stream,
+                     (const float*)ctx->scratch[3].p, (const unsigned*)d_src, (const int*)d_n, d_kp, d_desc, d_desc_u8, ss,
+                     kp_stride, desc_stride);
   return vo_check_launch(ctx, "sift_gather_kernel");
 }
 
-int vo_sift_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap, float* d_kp, float* d_desc, uint8_t* d_desc_u8,
-                int32_t* d_n) {
-  if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, d_img && d_kp && d_n && (d_desc || d_desc_u8), "sift_dev: null pointer");
-  VO_REQUIRE(ctx, H >= 16 && W >= 16, "sift_dev: bad arguments");
-  VO_REQUIRE(ctx, cap >= 1 && cap <= FIN_MAX - 96, "sift_dev: cap must be in 1..%d", FIN_MAX - 96);
-  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  VO_TRY(sift_enqueue(ctx, d_img, H, W, cap));
-  return sift_finalize(ctx, cap, d_kp, d_desc, d_desc_u8, d_n);
-}
-
-int vo_sift(vo_ctx* ctx, const uint8_t* img, int H, int W, int cap, float* kp_out, float* desc_out, int32_t* n_out) {
-  if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, img && kp_out && desc_out && n_out, "sift: null pointer");
-  VO_REQUIRE(ctx, H >= 16 && W >= 16, "sift: bad arguments");
-  const bool capped = cap > 0 && cap <= FIN_MAX - 96;      // the order, duplicates and cap on the device (rows: cap + ties)
-  if (cap <= 0) cap = vo_sift_capacity(H, W);   // keep every keypoint, as cv2.SIFT_create() (nfeatures = 0) does
-  *n_out = 0;
-  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  // through the context's pinned staging buffer: a DMA each way instead of the runtime's pageable-memory path
-  VO_TRY(vo_ensure(ctx, ctx->img, (size_t)H * W));
-  VO_TRY(vo_ensure_pinned(ctx, (size_t)H * W));
-  memcpy(ctx->h_pin, img, (size_t)H * W);
-  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, ctx->h_pin, (size_t)H * W, hipMemcpyHostToDevice, st));
-  VO_TRY(sift_enqueue(ctx, (const uint8_t*)ctx->img.p, H, W, cap));
-  unsigned* d_cnt = (unsigned*)ctx->scratch[2].p;
-  float* d_rows = (float*)ctx->scratch[3].p;
-  if (capped) {
-    // final rows made on the device: [n | kp cap x 6 | desc cap x 128] come back in one transfer
-    const size_t out_bytes = 16 + (size_t)cap * 134 * 4;
-    VO_TRY(vo_ensure(ctx, ctx->scratch[7], out_bytes));
-    char* d_out = (char*)ctx->scratch[7].p;
-    VO_TRY(sift_finalize(ctx, cap, (float*)(d_out + 16), (float*)(d_out + 16 + (size_t)cap * 24), nullptr, (int*)d_out));
-    VO_HIP_TRY(ctx, hipMemcpyAsync(d_out + 4, d_cnt + C_OVER, 4, hipMemcpyDeviceToDevice, st));
-    VO_TRY(vo_ensure_pinned(ctx, out_bytes));
-    VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-    VO_HIP_TRY(ctx, hipStreamSynchronize(st));
-    const int* head = (const int*)ctx->h_pin;
-    if (head[1]) return vo_set_error(ctx, VO_ECAPACITY, "sift: candidate / keypoint list overflow");
-    const int n = head[0];
-    memcpy(kp_out, (const char*)ctx->h_pin + 16, (size_t)n * 24);
-    memcpy(desc_out, (const char*)ctx->h_pin + 16 + (size_t)cap * 24, (size_t)n * 512);
-    *n_out = n;
-    return VO_OK;
-  }
-  unsigned cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  VO_HIP_TRY(ctx, hipMemcpyAsync(cnt, d_cnt, 32, hipMemcpyDeviceToHost, st));
-  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
-  if (cnt[C_OVER]) return vo_set_error(ctx, VO_ECAPACITY, "sift: candidate / keypoint list overflow");
-  const unsigned n_all = cnt[C_SEL];      // rows described: all keypoints, or those at or above the cap's response bound
-  if (n_all == 0) return VO_OK;
-  VO_TRY(vo_ensure_pinned(ctx, (size_t)n_all * 134 * 4));
-  const float* rows = (const float*)ctx->h_pin;
-  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_rows, (size_t)n_all * 134 * 4, hipMemcpyDeviceToHost, st));
-  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
-  // order, duplicates, optional cap (KeyPointsFilter::removeDuplicatedSorted / retainBest)
+// vo_sift's host tail for the n_all described rows of one image: order, duplicates, optional cap
+// (KeyPointsFilter::removeDuplicatedSorted / retainBest); returns the rows written
+static int sift_host_order(const float* rows, unsigned n_all, int cap, float* kp_out, float* desc_out) {
+  if (n_all == 0) return 0;
   std::vector<unsigned> order(n_all);
   for (unsigned i = 0; i < n_all; ++i) order[i] = i;
   std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) {
@@ -1472,7 +1523,161 @@ int vo_sift(vo_ctx* ctx, const uint8_t* img, int H, int W, int cap, float* kp_ou
     memcpy(kp_out + i * 6, r, 24);
     memcpy(desc_out + i * 128, r + 6, 512);
   }
-  *n_out = (int32_t)keep.size();
+  return (int)keep.size();
+}
+
+int vo_sift_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int cap, float* d_kp, float* d_desc, uint8_t* d_desc_u8,
+                int32_t* d_n) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, d_img && d_kp && d_n && (d_desc || d_desc_u8), "sift_dev: null pointer");
+  VO_REQUIRE(ctx, H >= 16 && W >= 16, "sift_dev: bad arguments");
+  VO_REQUIRE(ctx, cap >= 1 && cap <= FIN_MAX - 96, "sift_dev: cap must be in 1..%d", FIN_MAX - 96);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  VO_TRY(sift_enqueue(ctx, d_img, (size_t)H * W, 1, H, W, cap));
+  return sift_finalize(ctx, H, W, 1, cap, d_kp, (size_t)cap, d_desc, d_desc_u8, (size_t)cap, d_n);
+}
+
+int vo_sift(vo_ctx* ctx, const uint8_t* img, int H, int W, int cap, float* kp_out, float* desc_out, int32_t* n_out) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, img && kp_out && desc_out && n_out, "sift: null pointer");
+  VO_REQUIRE(ctx, H >= 16 && W >= 16, "sift: bad arguments");
+  const bool capped = cap > 0 && cap <= FIN_MAX - 96;      // the order, duplicates and cap on the device (rows: cap + ties)
+  if (cap <= 0) cap = vo_sift_capacity(H, W);   // keep every keypoint, as cv2.SIFT_create() (nfeatures = 0) does
+  *n_out = 0;
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // through the context's pinned staging buffer: a DMA each way instead of the runtime's pageable-memory path
+  VO_TRY(vo_ensure(ctx, ctx->img, (size_t)H * W));
+  VO_TRY(vo_ensure_pinned(ctx, (size_t)H * W));
+  memcpy(ctx->h_pin, img, (size_t)H * W);
+  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, ctx->h_pin, (size_t)H * W, hipMemcpyHostToDevice, st));
+  VO_TRY(sift_enqueue(ctx, (const uint8_t*)ctx->img.p, (size_t)H * W, 1, H, W, cap));
+  unsigned* d_cnt = (unsigned*)ctx->scratch[2].p;
+  float* d_rows = (float*)ctx->scratch[3].p;
+  if (capped) {
+    // final rows made on the device: [n | kp cap x 6 | desc cap x 128] come back in one transfer
+    const size_t out_bytes = 16 + (size_t)cap * 134 * 4;
+    VO_TRY(vo_ensure(ctx, ctx->scratch[7], out_bytes));
+    char* d_out = (char*)ctx->scratch[7].p;
+    VO_TRY(sift_finalize(ctx, H, W, 1, cap, (float*)(d_out + 16), (size_t)cap, (float*)(d_out + 16 + (size_t)cap * 24),
+                         nullptr, (size_t)cap, (int*)d_out));
+    VO_HIP_TRY(ctx, hipMemcpyAsync(d_out + 4, d_cnt + C_OVER, 4, hipMemcpyDeviceToDevice, st));
+    VO_TRY(vo_ensure_pinned(ctx, out_bytes));
+    VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+    const int* head = (const int*)ctx->h_pin;
+    if (head[1]) return vo_set_error(ctx, VO_ECAPACITY, "sift: candidate / keypoint list overflow");
+    const int n = head[0];
+    memcpy(kp_out, (const char*)ctx->h_pin + 16, (size_t)n * 24);
+    memcpy(desc_out, (const char*)ctx->h_pin + 16 + (size_t)cap * 24, (size_t)n * 512);
+    *n_out = n;
+    return VO_OK;
+  }
+  unsigned cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  VO_HIP_TRY(ctx, hipMemcpyAsync(cnt, d_cnt, 32, hipMemcpyDeviceToHost, st));
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (cnt[C_OVER]) return vo_set_error(ctx, VO_ECAPACITY, "sift: candidate / keypoint list overflow");
+  const unsigned n_all = cnt[C_SEL];      // rows described: all keypoints, or those at or above the cap's response bound
+  if (n_all == 0) return VO_OK;
+  VO_TRY(vo_ensure_pinned(ctx, (size_t)n_all * 134 * 4));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_rows, (size_t)n_all * 134 * 4, hipMemcpyDeviceToHost, st));
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  *n_out = (int32_t)sift_host_order((const float*)ctx->h_pin, n_all, cap, kp_out, desc_out);
+  return VO_OK;
+}
+
+int vo_sift_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, int cap, float* d_kp,
+                      size_t kp_stride, float* d_desc, uint8_t* d_desc_u8, size_t desc_stride, int32_t* d_n,
+                      int32_t* d_over) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, d_imgs && d_kp && d_n && (d_desc || d_desc_u8), "sift_batch_dev: null pointer");
+  VO_REQUIRE(ctx, S >= 1 && S <= 65535 && H >= 16 && W >= 16, "sift_batch_dev: bad arguments (S %d, H %d, W %d)", S, H, W);
+  VO_REQUIRE(ctx, cap >= 1 && cap <= FIN_MAX - 96, "sift_batch_dev: cap must be in 1..%d", FIN_MAX - 96);
+  VO_REQUIRE(ctx, img_stride >= (size_t)H * W, "sift_batch_dev: img_stride %zu is below H * W = %zu", img_stride,
+             (size_t)H * W);
+  VO_REQUIRE(ctx, kp_stride >= (size_t)cap && desc_stride >= (size_t)cap,
+             "sift_batch_dev: kp_stride %zu / desc_stride %zu below cap %d", kp_stride, desc_stride, cap);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  VO_TRY(sift_enqueue(ctx, d_imgs, img_stride, S, H, W, cap));
+  VO_TRY(sift_finalize(ctx, H, W, S, cap, d_kp, kp_stride, d_desc, d_desc_u8, desc_stride, d_n));
+  if (d_over) {
+    hipLaunchKernelGGL(sift_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, (const unsigned*)ctx->scratch[2].p,
+                       sift_geometry(H, W).ss.cnt, S, d_over, (unsigned*)nullptr);
+    VO_TRY(vo_check_launch(ctx, "sift_counts_kernel"));
+  }
+  return VO_OK;
+}
+
+int vo_sift_batch(vo_ctx* ctx, const uint8_t* imgs, int S, int H, int W, int cap, float* kp_out, float* desc_out,
+                  int32_t* n_out) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, imgs && kp_out && desc_out && n_out, "sift_batch: null pointer");
+  VO_REQUIRE(ctx, S >= 1 && S <= 65535 && H >= 16 && W >= 16, "sift_batch: bad arguments (S %d, H %d, W %d)", S, H, W);
+  const bool capped = cap > 0 && cap <= FIN_MAX - 96;      // as vo_sift: order, duplicates and cap on the device
+  if (cap <= 0) cap = vo_sift_capacity(H, W);
+  for (int q = 0; q < S; ++q) n_out[q] = 0;
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t px = (size_t)H * W, Sz = (size_t)S;
+  VO_TRY(vo_ensure(ctx, ctx->img, Sz * px));
+  VO_TRY(vo_ensure_pinned(ctx, Sz * px));
+  memcpy(ctx->h_pin, imgs, Sz * px);
+  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, ctx->h_pin, Sz * px, hipMemcpyHostToDevice, st));
+  VO_TRY(sift_enqueue(ctx, (const uint8_t*)ctx->img.p, px, S, H, W, cap));
+  const sift_stride_t ss = sift_geometry(H, W).ss;
+  const unsigned* d_cnt = (const unsigned*)ctx->scratch[2].p;
+  // [n S | overflow S | rows S] head, 16-byte aligned
+  const size_t head = (Sz * 12 + 15) & ~size_t(15);
+  if (capped) {
+    // final rows of every image made on the device: [head | kp S x cap x 6 | desc S x cap x 128] in one transfer
+    const size_t kp_bytes = Sz * cap * 24, out_bytes = head + Sz * cap * 134 * 4;
+    VO_TRY(vo_ensure(ctx, ctx->scratch[7], out_bytes));
+    char* d_out = (char*)ctx->scratch[7].p;
+    VO_TRY(sift_finalize(ctx, H, W, S, cap, (float*)(d_out + head), (size_t)cap, (float*)(d_out + head + kp_bytes), nullptr,
+                         (size_t)cap, (int*)d_out));
+    hipLaunchKernelGGL(sift_counts_kernel, dim3(1), dim3(256), 0, st, d_cnt, ss.cnt, S, (int32_t*)d_out + S,
+                       (unsigned*)nullptr);
+    VO_TRY(vo_check_launch(ctx, "sift_counts_kernel"));
+    VO_TRY(vo_ensure_pinned(ctx, out_bytes));
+    VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+    const int* n = (const int*)ctx->h_pin;
+    for (int q = 0; q < S; ++q)
+      if (n[S + q]) return vo_set_error(ctx, VO_ECAPACITY, "sift_batch: candidate / keypoint list overflow in image %d", q);
+    const char* h = (const char*)ctx->h_pin + head;
+    for (int q = 0; q < S; ++q) {
+      memcpy(kp_out + (size_t)q * cap * 6, h + (size_t)q * cap * 24, (size_t)n[q] * 24);
+      memcpy(desc_out + (size_t)q * cap * 128, h + kp_bytes + (size_t)q * cap * 512, (size_t)n[q] * 512);
+      n_out[q] = n[q];
+    }
+    return VO_OK;
+  }
+  // every image's overflow flag and described-row count, then its rows, then vo_sift's host tail per image
+  VO_TRY(vo_ensure(ctx, ctx->scratch[7], head));
+  int32_t* d_head = (int32_t*)ctx->scratch[7].p;
+  hipLaunchKernelGGL(sift_counts_kernel, dim3(1), dim3(256), 0, st, d_cnt, ss.cnt, S, d_head + S, (unsigned*)(d_head + 2 * S));
+  VO_TRY(vo_check_launch(ctx, "sift_counts_kernel"));
+  VO_TRY(vo_ensure_pinned(ctx, head));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pin, d_head, head, hipMemcpyDeviceToHost, st));
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  std::vector<int32_t> over((const int32_t*)ctx->h_pin + S, (const int32_t*)ctx->h_pin + 2 * S);
+  std::vector<unsigned> n_all((const unsigned*)ctx->h_pin + 2 * S, (const unsigned*)ctx->h_pin + 3 * S);
+  for (int q = 0; q < S; ++q)
+    if (over[q]) return vo_set_error(ctx, VO_ECAPACITY, "sift_batch: candidate / keypoint list overflow in image %d", q);
+  std::vector<size_t> at(Sz + 1, 0);                    // image q's rows at rows [at[q], at[q + 1]) of the staging buffer
+  for (int q = 0; q < S; ++q) at[q + 1] = at[q] + n_all[q];
+  if (at[S] == 0) return VO_OK;
+  VO_TRY(vo_ensure_pinned(ctx, at[S] * 134 * 4));
+  float* rows = (float*)ctx->h_pin;
+  const float* d_rows = (const float*)ctx->scratch[3].p;
+  for (int q = 0; q < S; ++q)
+    if (n_all[q])
+      VO_HIP_TRY(ctx, hipMemcpyAsync(rows + at[q] * 134, d_rows + (size_t)q * ss.list * 134, (size_t)n_all[q] * 134 * 4,
+                                     hipMemcpyDeviceToHost, st));
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  for (int q = 0; q < S; ++q)
+    n_out[q] = (int32_t)sift_host_order(rows + at[q] * 134, n_all[q], cap, kp_out + (size_t)q * cap * 6,
+                                        desc_out + (size_t)q * cap * 128);
   return VO_OK;
 }
 

@@ -142,6 +142,8 @@ _SIGS = {
     "vo_sift": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "vo_sift_capacity": (_i, [_i, _i]),
     "vo_sift_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "vo_sift_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "vo_sift_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vo_fundamental_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
     "vo_fundamental_fit": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "vo_essential_decompose": (_i, [_vp, _vp, _vp]),
@@ -419,6 +421,22 @@ class Context:
         n = C.c_int32(0)
         self._chk(self._lib.vo_sift(self._h, _ptr(img), H, W, int(cap) if cap else 0, _ptr(kp), _ptr(desc), C.byref(n)))
         return kp[: n.value].copy(), desc[: n.value].copy()
+
+    def sift_batch(self, images, cap=None):
+        """SIFT on S images of one size in one set of launches (vo_sift_batch): `images` is an (S, H, W) uint8 array or a
+        list of equal-shape 2-D arrays.  Returns a list of S (kp, desc) pairs, each what sift(image, cap) returns."""
+        shapes = {np.shape(a) for a in images}
+        if len(shapes) != 1 or len(next(iter(shapes))) != 2:
+            raise ValueError("sift_batch: images must be 2-D and of one shape, got %s" % sorted(shapes))
+        imgs = _c(np.stack([np.asarray(a) for a in images]), np.uint8)
+        S, H, W = imgs.shape
+        rows = int(cap) if cap else self._lib.vo_sift_capacity(H, W)
+        kp = np.empty((S, rows, 6), np.float32)
+        desc = np.empty((S, rows, 128), np.float32)
+        n = np.zeros(S, np.int32)
+        self._chk(self._lib.vo_sift_batch(self._h, _ptr(imgs), S, H, W, int(cap) if cap else 0, _ptr(kp), _ptr(desc),
+                                          _ptr(n)))
+        return [(kp[q, : n[q]].copy(), desc[q, : n[q]].copy()) for q in range(S)]
 
     def min_eigen_map(self, img, block_size=7):
         img = _c(img, np.uint8)
