@@ -300,6 +300,16 @@ int vo_sift_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride /* b
                       int32_t* d_over /* S, nullable: 1 = candidate / keypoint list overflow */);
 int vo_sift_batch(vo_ctx* ctx, const uint8_t* imgs /* S*H*W */, int S, int H, int W, int cap, float* kp, float* desc,
                   int32_t* n /* S */);
+/* [ref: src/vo/features/sift.py:10,17]  cv2.SIFT_create() (nfeatures = 0: every keypoint) .detectAndCompute on S images of
+ * one size with the final order made on the device for any count: image q's keypoints are those of vo_sift(cap <= 0) on
+ * that image alone, in its order, bit for bit.  Layout as vo_sift_batch_dev with `rows` output rows per image
+ * (1 <= rows <= vo_sift_capacity(H, W)).  d_over[q] = 0: image q succeeded; 1: its candidate / keypoint lists
+ * overflowed; 2: it has more than `rows` keypoints.  When d_over[q] != 0, d_n[q] = 0 and nothing of image q is written
+ * (never a truncated list).  Counts stay on the device: a fixed launch sequence, no host synchronisation.            */
+int vo_sift_all_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride /* bytes, >= H*W */, int S, int H, int W,
+                          int rows, float* d_kp, size_t kp_stride /* rows, >= rows */, float* d_desc, uint8_t* d_desc_u8,
+                          size_t desc_stride /* rows, >= rows */, int32_t* d_n /* S */,
+                          int32_t* d_over /* S, nullable: 0 ok, 1 list overflow, 2 more than `rows` keypoints */);
 
 /* ---- RANSAC control (host-side, bit-compatible with the reference) --------------
  * [ref: src/vo/algorithms/ransac.py:52, 92-94]  the sample stream of
@@ -393,7 +403,8 @@ typedef struct vo_pipeline_config {
                                     modes: any S; SIFT tracker mode: one.                                */
   int32_t tracker_mode;          /* 0: KLT tracker with the Harris detector (everything above); 1: SIFT
                                     [ref: src/vo/features/tracker.py:60-61, src/vo/features/sift.py:23-56] -- per frame
-                                    detect + describe (the sift_cap strongest keypoints; the reference keeps all of them),
+                                    detect + describe (every keypoint with sift_cap = -1, as the reference keeps; else
+                                    the sift_cap strongest),
                                     2-NN + ratio + first-come uniqueness against the descriptors the current Features
                                     carry, Matches regroup from the pair list with the descriptors following their
                                     keypoints [ref: src/vo/primitives/matches.py:51-58, 134-141], then the same pose
@@ -407,7 +418,10 @@ typedef struct vo_pipeline_config {
                                     number of sequences: patches, matcher, regroup and descriptor gather take all of
                                     them in one launch each; lanes (vo_pipeline_set_active_seq / _restart_seq) are KLT
                                     mode only.  debug_fault_every > 0 forces the fault at the pair regroup.          */
-  int32_t sift_cap;              /* keypoints kept per frame in SIFT mode (0 = n_keypoints; <= 4000, <= feature_cap) */
+  int32_t sift_cap;              /* keypoints kept per frame in SIFT mode: 1..4000 (<= feature_cap) the strongest;
+                                    0 = n_keypoints; -1 = every keypoint [ref: src/vo/features/sift.py:10, nfeatures = 0]
+                                    up to feature_cap -- a frame with more, or whose SIFT lists overflow, fails its step
+                                    with VO_ECAPACITY (never a truncated list).  Below -1: refused.                   */
   double match_ratio;            /* 0 = the reference's: 0.8 in SIFT mode (sift.py:49), 0.85 in Harris mode (harris.py:255) */
 } vo_pipeline_config;
 typedef struct vo_step_result {

@@ -130,9 +130,14 @@ struct vo_pipeline {
   // Harris tracker mode (tracker_mode = 2; tracker.py:58-59, harris.py:50-84): the same with the detector's N keypoints
   // (every frame), their 19x19 raw patches as 384-byte rows, ratio 0.85 -- for any number of sequences: the detection,
   // the patches, the matcher, the regroup and the descriptor gather take all S in one launch each (grid's extra dimension).
+  // sift_cap = -1 (sift_all): every keypoint of the frame, sift_cap = feature_cap rows per frame; a frame that has more, or
+  // whose SIFT lists overflow, is a VO_FAULT_CAPACITY step (d_sover says which and how many).
   int sift_cap = 0;
+  bool sift_all = false;
   int desc_row = 128;                // bytes per descriptor row: 128 (SIFT) or 384 (361 patch bytes, padded)
   float* d_skp = nullptr;            // [3][sift_cap * 6]   keypoint rows of the frame in slot s (SIFT: one sequence)
+  int32_t* d_sover = nullptr;        // [3][2] sift_all: the frame in slot s -- its verdict (vo_sift_all_batch_dev's d_over),
+                                     //        its keypoint count (-1: list overflow)
   uint8_t* d_sdesc = nullptr;        // [3][S][sift_cap * desc_row] its descriptors
   int32_t* d_sn = nullptr;           // [3][S] its keypoint count; [S]: pairs of the step being enqueued
   uint8_t* d_fdesc = nullptr;        // [2][S][cap * desc_row] descriptors of the Features buffers F[0], F[1]
@@ -259,6 +264,19 @@ __global__ __launch_bounds__(256) void sift_kp_f64_kernel(const float* __restric
   if (i >= min(*n, cap)) return;
   out[2 * i] = (double)rows[6 * i];
   out[2 * i + 1] = (double)rows[6 * i + 1];
+}
+
+// SIFT tracker mode, every keypoint (sift_cap = -1): a frame whose SIFT lists overflowed or that has more keypoints than the
+// feature capacity (vo_sift_all_batch_dev's verdict != 0: its count is 0, its rows unwritten) makes the step a capacity
+// fault before the matcher -- the regroup, the descriptor gather and the pose chain leave a faulted sequence alone.  (A
+// fault of an earlier step, still open, stays: this step is enqueued again when that one is done, as at the regroup.)
+__global__ void sift_fit_kernel(const int32_t* __restrict__ verdict, vo_seq_ctl* __restrict__ ctl) {
+  if (threadIdx.x != 0 || ctl->fault || *verdict == 0) return;
+  ctl->fault = VO_FAULT_CAPACITY;
+  ctl->n_in = 0;
+  ctl->redetected = 0;
+  ctl->few = 0;
+  ctl->n_p3p = 0;
 }
 
 // ... and the descriptors of the regrouped frame: row dst of the new Features = the new keypoint src_row[dst]'s
@@ -541,7 +559,7 @@ void vo_pipeline_destroy(vo_pipeline* p) {
   void* dev[] = {p->d_det_go, p->d_img, p->d_pyr, p->d_kp, p->d_scores[0], p->d_scores[1], p->feat_mem, p->d_ctl, p->d_next, p->d_err,
                  p->d_status, p->d_R, p->d_t, p->d_valid, p->d_counts, p->d_samples, p->d_masks, p->d_best_mask, p->d_table,
                  p->d_raws, p->d_newkp, p->d_pairs, p->d_ckpt_feat, p->d_ckpt_ctl, p->d_skp, p->d_sdesc, p->d_sn, p->d_fdesc,
-                 p->d_srcrow, p->d_ckpt_fdesc, p->d_pend, p->d_cams};
+                 p->d_sover, p->d_srcrow, p->d_ckpt_fdesc, p->d_pend, p->d_cams};
   for (void* q : dev)
     if (q) (void)hipFree(q);
   void* pin[] = {p->h_stage, p->h_res, (void*)p->h_seq};
@@ -583,6 +601,8 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   VO_REQUIRE(ctx, cfg->sequences >= 0 && cfg->sequences <= 256, "pipeline: sequences must be in 1..256");
   VO_REQUIRE(ctx, cfg->tracker_mode >= 0 && cfg->tracker_mode <= 2, "pipeline: tracker_mode must be 0 (klt), 1 (sift) or 2 (harris)");
   VO_REQUIRE(ctx, cfg->tracker_mode != 1 || cfg->sequences <= 1, "pipeline: the SIFT tracker mode runs one sequence per pipeline");
+  VO_REQUIRE(ctx, cfg->tracker_mode != 1 || cfg->sift_cap >= -1,
+             "pipeline: sift_cap must be -1 (every keypoint), 0 (n_keypoints) or 1..4000, got %d", cfg->sift_cap);
   const int cap = cfg->feature_cap > 0 ? cfg->feature_cap : 2 * cfg->n_keypoints;
   VO_REQUIRE(ctx, cap >= cfg->n_keypoints && cap <= 32768, "pipeline: feature_cap must be in n_keypoints..32768");
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -719,10 +739,14 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   PA(dev_alloc(ctx, &p->d_pairs, (size_t)cap * 2 * (cfg->tracker_mode != 0 ? Sz : 1)));
   if (cfg->tracker_mode != 0) {
     p->desc_row = cfg->tracker_mode == 2 ? 384 : 128;
-    p->sift_cap = cfg->tracker_mode == 2 ? cfg->n_keypoints : (cfg->sift_cap > 0 ? cfg->sift_cap : cfg->n_keypoints);
-    if (rc == VO_OK && (p->sift_cap > cap || p->sift_cap > 4000))
+    p->sift_all = cfg->tracker_mode == 1 && cfg->sift_cap == -1;
+    p->sift_cap = cfg->tracker_mode == 2 ? cfg->n_keypoints
+                  : p->sift_all          ? cap
+                                         : (cfg->sift_cap > 0 ? cfg->sift_cap : cfg->n_keypoints);
+    if (rc == VO_OK && !p->sift_all && (p->sift_cap > cap || p->sift_cap > 4000))
       rc = vo_set_error(ctx, VO_EINVAL, "pipeline: sift_cap %d exceeds the feature capacity %d (or 4000)", p->sift_cap, cap);
     PA(dev_alloc(ctx, &p->d_skp, (size_t)3 * p->sift_cap * 6));
+    if (p->sift_all) PA(dev_alloc(ctx, &p->d_sover, (size_t)3 * 2));
     PA(dev_alloc(ctx, &p->d_sdesc, 3 * Sz * p->sift_cap * p->desc_row));
     PA(dev_alloc(ctx, &p->d_sn, 4 * Sz + 4));
     PA(dev_alloc(ctx, &p->d_fdesc, 2 * Sz * cap * p->desc_row));
@@ -1264,7 +1288,11 @@ static int enqueue_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, char* er
   int rc = VO_OK;
   if (sc != p->trk && hipStreamWaitEvent(sc->stream, p->evImg[f.next_idx], 0) != hipSuccess) rc = VO_EHIP;   // (the upload)
   if (rc == VO_OK && p->n_pinned[f.next_idx] > 0 && hipStreamWaitEvent(sc->stream, p->evUp[f.next_idx], 0) != hipSuccess) rc = VO_EHIP;
-  if (rc == VO_OK)
+  if (rc == VO_OK && p->sift_all)
+    rc = vo_sift_all_found_dev(sc, p->img(0, f.next_idx), p->img_stride(), 1, c.H, c.W, p->sift_cap,
+                               p->d_skp + (size_t)f.b * p->sift_cap * 6, (size_t)p->sift_cap, nullptr, p->sdesc(f.b, 0),
+                               (size_t)p->sift_cap, p->sn(f.b, 0), p->d_sover + 2 * f.b, p->d_sover + 2 * f.b + 1);
+  else if (rc == VO_OK)
     rc = vo_sift_dev(sc, p->img(0, f.next_idx), c.H, c.W, p->sift_cap, p->d_skp + (size_t)f.b * p->sift_cap * 6, nullptr,
                      p->sdesc(f.b, 0), p->sn(f.b, 0));
   if (rc == VO_OK && hipEventRecord(p->evPyr[f.b], sc->stream) != hipSuccess) rc = VO_EHIP;
@@ -1322,6 +1350,10 @@ static int enqueue_chain_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, bo
   vo_seq_ctl* ctl = p->d_ctl + q0;
   static_assert(sizeof(vo_seq_ctl) % 4 == 0, "control blocks are read as int arrays");
   VO_HIP_TRY(ctx, hipStreamWaitEvent(st, p->evPyr[f.b], 0));
+  if (p->sift_all) {            // (a frame that does not fit: the step's first kernel raises the fault, nothing else runs)
+    hipLaunchKernelGGL(sift_fit_kernel, dim3(1), dim3(64), 0, st, (const int32_t*)p->d_sover + 2 * f.b, ctl);
+    VO_TRY(vo_check_launch(ctx, "sift_fit_kernel"));
+  }
   const double ratio = c.match_ratio > 0.0 ? c.match_ratio : (harris ? 0.85 : 0.8);        // harris.py:255 / sift.py:49
   VO_TRY(vo_match_u8_batch_dev(ctx, descA, (size_t)p->cap * row, &ctl->n, (int)(sizeof(vo_seq_ctl) / 4), p->cap, sdesc,
                                (size_t)p->sift_cap * row, n_new, 1, p->sift_cap, Sn, ratio, pairs, n_pairs, p->desc_row));
@@ -2004,6 +2036,15 @@ static int recover_step(vo_pipeline* p, const vo_pipeline::flight_t& f, int q, v
   vo_seq_ctl h;
   VO_HIP_TRY(ctx, mcpy(st, &h, ctl, sizeof(h), hipMemcpyDeviceToHost));
   const int fault_reason = h.fault;
+  if ((h.fault & VO_FAULT_CAPACITY) && p->sift_all) {     // (sift_fit_kernel: the frame's keypoints do not fit)
+    int32_t v[2] = {0, 0};
+    VO_HIP_TRY(ctx, mcpy(st, v, p->d_sover + 2 * f.b, sizeof(v), hipMemcpyDeviceToHost));
+    if (v[0] == 1)
+      return vo_set_error(ctx, VO_ECAPACITY, "pipeline: the SIFT candidate / keypoint lists of frame %d overflowed", f.next_idx);
+    if (v[0] == 2)
+      return vo_set_error(ctx, VO_ECAPACITY, "pipeline: frame %d has %d SIFT keypoints, more than the feature capacity %d",
+                          f.next_idx, v[1], p->cap);
+  }
   if (h.fault & VO_FAULT_CAPACITY)
     return vo_set_error(ctx, VO_ECAPACITY, "pipeline: %d features + %d new keypoints exceed the capacity %d", h.n,
                         c.n_keypoints, p->cap);

@@ -12,8 +12,9 @@
 //   refinement    one lane per candidate: <= 5 quadratic-fit steps, contrast / edge tests,
 //                 36-bin orientation histogram, one keypoint per accepted peak
 //   description   one lane per keypoint, 4x4x8 trilinear histogram
-// Ordering (by x, y, ...), duplicate removal and the optional strongest-N cap are applied on
-// the host to the few thousand resulting rows.
+// Ordering (by x, y, ...), duplicate removal and the optional strongest-N cap: on the device in one
+// workgroup for a cap, on the device in tiles and merge passes for every keypoint (vo_sift_all_batch_dev),
+// or on the host (vo_sift with cap <= 0).
 #include <algorithm>
 #include <cmath>
 
@@ -1075,6 +1076,62 @@ __device__ __forceinline__ unsigned block_scan4(const unsigned (&f)[4], unsigned
   return total;
 }
 
+// the strict total order of the final rows: (128-bit key, row number) pairs -- the key
+// (order_bits(x), order_bits(y), ~order_bits(size), order_bits(angle)), on a full key tie row_tie_less
+__device__ __forceinline__ bool sorted_less(const float* __restrict__ rows, uint4 ka, unsigned ra, uint4 kb, unsigned rb) {
+  if (ka.x != kb.x) return ka.x < kb.x;
+  if (ka.y != kb.y) return ka.y < kb.y;
+  if (ka.z != kb.z) return ka.z < kb.z;
+  if (ka.w != kb.w) return ka.w < kb.w;
+  if (ra == 0xffffffffu || rb == 0xffffffffu) return ra < rb;     // (padding: never before a row)
+  return row_tie_less(rows, ra, rb);
+}
+
+// Rows row0 .. row0 + m - 1 sorted in LDS by one workgroup of FIN_T work items (m <= FIN_MAX; s_key [FIN_MAX][4],
+// s_row [FIN_MAX]): their keys and row numbers, padded to N = the power of two >= m (>= 2), then a bitonic sort.  On return
+// sorted position i < m holds key s_key[4 i ..] and row s_row[i].
+__device__ void fin_sort_lds(const float* __restrict__ rows, unsigned row0, unsigned m, unsigned* s_key, unsigned* s_row) {
+  const int tid = threadIdx.x;
+  unsigned N = 1;
+  while (N < m) N <<= 1;
+  if (N < 2) N = 2;
+  for (unsigned i = tid; i < N; i += FIN_T) {
+    if (i < m) {
+      const float* r = rows + (size_t)(row0 + i) * 134;
+      s_key[4 * i] = order_bits(r[0]);
+      s_key[4 * i + 1] = order_bits(r[1]);
+      s_key[4 * i + 2] = ~order_bits(r[2]);
+      s_key[4 * i + 3] = order_bits(r[3]);
+      s_row[i] = row0 + i;
+    } else {
+      s_key[4 * i] = s_key[4 * i + 1] = s_key[4 * i + 2] = s_key[4 * i + 3] = 0xffffffffu;
+      s_row[i] = 0xffffffffu;                   // padding: behind every row
+    }
+  }
+  __syncthreads();
+  auto less = [&](unsigned a, unsigned b) -> bool {      // sorted positions a, b
+    return sorted_less(rows, *reinterpret_cast<const uint4*>(s_key + 4 * a), s_row[a],
+                       *reinterpret_cast<const uint4*>(s_key + 4 * b), s_row[b]);
+  };
+  for (unsigned k = 2; k <= N; k <<= 1) {
+    for (unsigned j = k >> 1; j > 0; j >>= 1) {
+      for (unsigned t = tid; t < N / 2; t += FIN_T) {
+        const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+        const bool up = (i & k) == 0;
+        if (less(p, i) == up) {
+          const uint4 ki = *reinterpret_cast<const uint4*>(s_key + 4 * i), kp2 = *reinterpret_cast<const uint4*>(s_key + 4 * p);
+          *reinterpret_cast<uint4*>(s_key + 4 * i) = kp2;
+          *reinterpret_cast<uint4*>(s_key + 4 * p) = ki;
+          const unsigned ri = s_row[i];
+          s_row[i] = s_row[p];
+          s_row[p] = ri;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 __global__ __launch_bounds__(FIN_T) void sift_finalize_kernel(const float* __restrict__ rows, const unsigned* __restrict__ n_rows,
                                                               int cap, unsigned* __restrict__ src_out, int* __restrict__ n_out,
                                                               unsigned* __restrict__ overflow, sift_stride_t ss) {
@@ -1098,50 +1155,7 @@ __global__ __launch_bounds__(FIN_T) void sift_finalize_kernel(const float* __res
     }
     return;
   }
-  unsigned N = 1;
-  while (N < n) N <<= 1;
-  if (N < 2) N = 2;
-  for (unsigned i = tid; i < N; i += FIN_T) {
-    if (i < n) {
-      const float* r = rows + (size_t)i * 134;
-      s_key[4 * i] = order_bits(r[0]);
-      s_key[4 * i + 1] = order_bits(r[1]);
-      s_key[4 * i + 2] = ~order_bits(r[2]);
-      s_key[4 * i + 3] = order_bits(r[3]);
-      s_row[i] = i;
-    } else {
-      s_key[4 * i] = s_key[4 * i + 1] = s_key[4 * i + 2] = s_key[4 * i + 3] = 0xffffffffu;
-      s_row[i] = 0xffffffffu;                   // padding: behind every row
-    }
-  }
-  __syncthreads();
-  auto less = [&](unsigned a, unsigned b) -> bool {      // sorted positions a, b
-    const uint4 ka = *reinterpret_cast<const uint4*>(s_key + 4 * a), kb = *reinterpret_cast<const uint4*>(s_key + 4 * b);
-    if (ka.x != kb.x) return ka.x < kb.x;
-    if (ka.y != kb.y) return ka.y < kb.y;
-    if (ka.z != kb.z) return ka.z < kb.z;
-    if (ka.w != kb.w) return ka.w < kb.w;
-    const unsigned ra = s_row[a], rb = s_row[b];
-    if (ra == 0xffffffffu || rb == 0xffffffffu) return ra < rb;     // (padding: never before a row)
-    return row_tie_less(rows, ra, rb);
-  };
-  for (unsigned k = 2; k <= N; k <<= 1) {
-    for (unsigned j = k >> 1; j > 0; j >>= 1) {
-      for (unsigned t = tid; t < N / 2; t += FIN_T) {
-        const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
-        const bool up = (i & k) == 0;
-        if (less(p, i) == up) {
-          const uint4 ki = *reinterpret_cast<const uint4*>(s_key + 4 * i), kp2 = *reinterpret_cast<const uint4*>(s_key + 4 * p);
-          *reinterpret_cast<uint4*>(s_key + 4 * i) = kp2;
-          *reinterpret_cast<uint4*>(s_key + 4 * p) = ki;
-          const unsigned ri = s_row[i];
-          s_row[i] = s_row[p];
-          s_row[p] = ri;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  fin_sort_lds(rows, 0u, n, s_key, s_row);
   // sorted: position 4 * tid + k.  kept = not a repeat of the previous row's four leading fields
   unsigned keep[4], pos[4];
   float resp[4];
@@ -1222,6 +1236,124 @@ __global__ __launch_bounds__(128) void sift_gather_kernel(const float* __restric
   if (desc_out) desc_out[(size_t)d * 128 + c] = v;
   if (desc_bytes) desc_bytes[(size_t)d * 128 + c] = (uint8_t)v;     // (whole numbers 0..255 by construction)
   if (c < 6) kp_out[(size_t)d * 6 + c] = r[c];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The final order of EVERY described row on the device (vo_sift_all_batch_dev: vo_sift's host tail without a cap, for any
+// count up to the row list's capacity).  The counts are known on the device only, so the launches are fixed by the
+// capacity and the workgroups past an image's count return at once:
+//   sift_all_tile_kernel     tiles of FIN_MAX rows sorted in LDS (fin_sort_lds: the capped path's bitonic sort)
+//   sift_all_merge_kernel    ceil(log2(capacity / FIN_MAX)) passes, each merging pairs of sorted runs of w positions
+//   sift_all_compact_kernel  duplicate flags, scan, destination -> row; the count and the verdict per image
+//   sift_gather_kernel       the rows themselves
+// Sorted runs live in the context's scratch[9] (keys, ping-pong) and scratch[10] (row numbers, ping-pong, then the
+// compacted destination -> row list), `list` entries per image each.
+
+// tile blockIdx.x of image blockIdx.y: its rows [t FIN_MAX, min(n, (t + 1) FIN_MAX)) sorted -> the same positions of
+// keys / row_of
+__global__ __launch_bounds__(FIN_T) void sift_all_tile_kernel(const float* __restrict__ rows, const unsigned* __restrict__ n_rows,
+                                                              uint4* __restrict__ keys, unsigned* __restrict__ row_of,
+                                                              sift_stride_t ss) {
+  extern __shared__ __align__(16) unsigned s_fin[];
+  const unsigned im = blockIdx.y;
+  rows += (size_t)im * ss.list * 134;
+  n_rows += im * ss.cnt;
+  keys += (size_t)im * ss.list;
+  row_of += (size_t)im * ss.list;
+  const unsigned n = min(*n_rows, ss.list), row0 = blockIdx.x * (unsigned)FIN_MAX;
+  if (row0 >= n) return;
+  const unsigned m = min(n - row0, (unsigned)FIN_MAX);
+  unsigned* s_key = s_fin;
+  unsigned* s_row = s_key + 4 * FIN_MAX;
+  fin_sort_lds(rows, row0, m, s_key, s_row);
+  for (unsigned i = threadIdx.x; i < m; i += FIN_T) {
+    keys[row0 + i] = *reinterpret_cast<const uint4*>(s_key + 4 * i);
+    row_of[row0 + i] = s_row[i];
+  }
+}
+
+// One merge pass: the sorted runs [2 j w, 2 j w + w) and [2 j w + w, 2 j w + 2 w) (clipped to the count) become one.  A
+// position's destination is its index in its own run plus the number of positions of the other run before it -- a binary
+// search there.  The order is strict and total (no two positions compare equal), so the destinations are a permutation
+// and no work item needs another's result: one work item per position, no merge-path partition.
+__global__ __launch_bounds__(256) void sift_all_merge_kernel(const float* __restrict__ rows, const unsigned* __restrict__ n_rows,
+                                                             const uint4* __restrict__ k_in, const unsigned* __restrict__ r_in,
+                                                             uint4* __restrict__ k_out, unsigned* __restrict__ r_out,
+                                                             unsigned w, sift_stride_t ss) {
+  const unsigned im = blockIdx.y;
+  rows += (size_t)im * ss.list * 134;
+  n_rows += im * ss.cnt;
+  const size_t off = (size_t)im * ss.list;
+  k_in += off;
+  r_in += off;
+  k_out += off;
+  r_out += off;
+  const unsigned n = min(*n_rows, ss.list), i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned base = i & ~(2 * w - 1), mid = min(base + w, n), end = min(base + 2 * w, n);
+  const uint4 k = k_in[i];
+  const unsigned r = r_in[i];
+  // the other run: [mid, end) for a position of the first, [base, mid) for one of the second
+  unsigned lo = i < mid ? mid : base, hi = i < mid ? end : mid;
+  while (lo < hi) {
+    const unsigned h = (lo + hi) >> 1;
+    if (sorted_less(rows, k_in[h], r_in[h], k, r)) lo = h + 1;
+    else hi = h;
+  }
+  // first run: base + (i - base) + (lo - mid); second run: base + (i - mid) + (lo - base) -- both i + lo - mid
+  const unsigned dst = i + lo - mid;
+  k_out[dst] = k;
+  r_out[dst] = r;
+}
+
+// One workgroup per image: a sorted position is kept unless its key repeats the previous position's
+// (removeDuplicatedSorted), the kept ones are numbered by a scan in FIN_MAX-position chunks and src[number] = row.  Then
+// the verdict: over = 1 when the image's candidate / keypoint lists overflowed, 2 when more than `cap_rows` rows are kept,
+// else 0; n_out = the kept count when over = 0, else 0 (the gather behind this launch writes nothing of that image).
+// found (nullable) = the kept count, -1 on a list overflow.
+__global__ __launch_bounds__(FIN_T) void sift_all_compact_kernel(const uint4* __restrict__ keys, const unsigned* __restrict__ row_of,
+                                                                 const unsigned* __restrict__ cnt, int cap_rows,
+                                                                 unsigned* __restrict__ src, int* __restrict__ n_out,
+                                                                 int32_t* __restrict__ over_out, int32_t* __restrict__ found,
+                                                                 sift_stride_t ss) {
+  __shared__ unsigned s_wave[FIN_T / 64];
+  const unsigned im = blockIdx.y;
+  const size_t off = (size_t)im * ss.list;
+  keys += off;
+  row_of += off;
+  src += off;
+  cnt += im * ss.cnt;
+  const unsigned n = min(cnt[C_SEL], ss.list);
+  const int tid = threadIdx.x;
+  unsigned kept = 0;
+  for (unsigned c0 = 0; c0 < n; c0 += 4 * FIN_T) {
+    unsigned keep[4], pos[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned sidx = c0 + 4u * tid + k;
+      keep[k] = 0;
+      if (sidx < n) {
+        bool dup = false;
+        if (sidx > 0) {
+          const uint4 a = keys[sidx], b = keys[sidx - 1];
+          dup = a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
+        }
+        keep[k] = dup ? 0u : 1u;
+      }
+    }
+    const unsigned total = block_scan4(keep, pos, s_wave);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (keep[k]) src[kept + pos[k]] = row_of[c0 + 4u * tid + k];
+    kept += total;
+  }
+  if (tid == 0) {
+    const bool lists = cnt[C_OVER] != 0u;
+    const int verdict = lists ? 1 : (kept > (unsigned)cap_rows ? 2 : 0);
+    n_out[im] = verdict ? 0 : (int)kept;
+    if (over_out) over_out[im] = verdict;
+    if (found) found[im] = lists ? -1 : (int)kept;
+  }
 }
 
 // per image of a batch: its overflow flag -> over[q] (nullable), its described-row count -> n_sel[q] (nullable)
@@ -1481,6 +1613,67 @@ static int sift_finalize(vo_ctx* ctx, int H, int W, int S, int cap, float* d_kp,
   return vo_check_launch(ctx, "sift_gather_kernel");
 }
 
+// the final order of every described row on the device (sift_all_tile_kernel ..), images 0 .. S - 1 enqueued by sift_enqueue:
+// image q's kept rows -> d_kp + q * kp_stride rows, d_desc / d_desc_u8 + q * desc_stride rows when at most `rows` are kept;
+// d_n[q], d_over[q] and d_found[q] (both nullable) as sift_all_compact_kernel leaves them.  A fixed launch sequence: no
+// host synchronisation.
+static int sift_sort_all(vo_ctx* ctx, int H, int W, int S, int rows, float* d_kp, size_t kp_stride, float* d_desc,
+                         uint8_t* d_desc_u8, size_t desc_stride, int* d_n, int32_t* d_over, int32_t* d_found) {
+  static const size_t lds = (size_t)FIN_MAX * 20;
+  static bool opted[64] = {false};
+  if (ctx->device >= 0 && ctx->device < 64 && !opted[ctx->device]) {
+    VO_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&sift_all_tile_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    opted[ctx->device] = true;
+  }
+  hipStream_t st = ctx->stream;
+  const sift_stride_t ss = sift_geometry(H, W).ss;
+  const size_t per = (size_t)S * ss.list;
+  VO_TRY(vo_ensure(ctx, ctx->scratch[9], 2 * per * sizeof(uint4)));
+  VO_TRY(vo_ensure(ctx, ctx->scratch[10], 3 * per * 4));
+  uint4* keys[2] = {(uint4*)ctx->scratch[9].p, (uint4*)ctx->scratch[9].p + per};
+  unsigned* row_of[2] = {(unsigned*)ctx->scratch[10].p, (unsigned*)ctx->scratch[10].p + per};
+  unsigned* d_src = (unsigned*)ctx->scratch[10].p + 2 * per;
+  const float* d_rows = (const float*)ctx->scratch[3].p;
+  const unsigned* d_cnt = (const unsigned*)ctx->scratch[2].p;
+  hipLaunchKernelGGL(sift_all_tile_kernel, dim3(vo_cdiv((int)ss.list, FIN_MAX), S), dim3(FIN_T), lds, st, d_rows,
+                     d_cnt + C_SEL, keys[0], row_of[0], ss);
+  VO_TRY(vo_check_launch(ctx, "sift_all_tile_kernel"));
+  int cur = 0;
+  for (unsigned w = FIN_MAX; w < ss.list; w <<= 1, cur ^= 1)
+    hipLaunchKernelGGL(sift_all_merge_kernel, dim3(vo_cdiv((int)ss.list, 256), S), dim3(256), 0, st, d_rows, d_cnt + C_SEL,
+                       (const uint4*)keys[cur], (const unsigned*)row_of[cur], keys[cur ^ 1], row_of[cur ^ 1], w, ss);
+  VO_TRY(vo_check_launch(ctx, "sift_all_merge_kernel"));
+  hipLaunchKernelGGL(sift_all_compact_kernel, dim3(1, S), dim3(FIN_T), 0, st, (const uint4*)keys[cur],
+                     (const unsigned*)row_of[cur], d_cnt, rows, d_src, d_n, d_over, d_found, ss);
+  VO_TRY(vo_check_launch(ctx, "sift_all_compact_kernel"));
+  sift_stride_t gs = ss;                              // (the gather finds image q's destination list at q * gs.cnt)
+  gs.cnt = ss.list;
+  hipLaunchKernelGGL(sift_gather_kernel, dim3(rows, S), dim3(128), 0, st, d_rows, (const unsigned*)d_src, (const int*)d_n,
+                     d_kp, d_desc, d_desc_u8, gs, kp_stride, desc_stride);
+  return vo_check_launch(ctx, "sift_gather_kernel");
+}
+
+int vo_sift_all_found_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, int rows, float* d_kp,
+                          size_t kp_stride, float* d_desc, uint8_t* d_desc_u8, size_t desc_stride, int32_t* d_n,
+                          int32_t* d_over, int32_t* d_found) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, d_imgs && d_kp && d_n && (d_desc || d_desc_u8), "sift_all_batch_dev: null pointer");
+  VO_REQUIRE(ctx, S >= 1 && S <= 65535 && H >= 16 && W >= 16, "sift_all_batch_dev: bad arguments (S %d, H %d, W %d)", S, H,
+             W);
+  const int capacity = vo_sift_capacity(H, W);
+  VO_REQUIRE(ctx, rows >= 1 && rows <= capacity, "sift_all_batch_dev: rows must be in 1..%d (vo_sift_capacity), got %d",
+             capacity, rows);
+  VO_REQUIRE(ctx, img_stride >= (size_t)H * W, "sift_all_batch_dev: img_stride %zu is below H * W = %zu", img_stride,
+             (size_t)H * W);
+  VO_REQUIRE(ctx, kp_stride >= (size_t)rows && desc_stride >= (size_t)rows,
+             "sift_all_batch_dev: kp_stride %zu / desc_stride %zu below rows %d", kp_stride, desc_stride, rows);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // cap = the list capacity: select_kernel takes every keypoint, as vo_sift's uncapped path does
+  VO_TRY(sift_enqueue(ctx, d_imgs, img_stride, S, H, W, capacity));
+  return sift_sort_all(ctx, H, W, S, rows, d_kp, kp_stride, d_desc, d_desc_u8, desc_stride, d_n, d_over, d_found);
+}
+
 // vo_sift's host tail for the n_all described rows of one image: order, duplicates, optional cap
 // (KeyPointsFilter::removeDuplicatedSorted / retainBest); returns the rows written
 static int sift_host_order(const float* rows, unsigned n_all, int cap, float* kp_out, float* desc_out) {
@@ -1606,6 +1799,13 @@ int vo_sift_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int
     VO_TRY(vo_check_launch(ctx, "sift_counts_kernel"));
   }
   return VO_OK;
+}
+
+int vo_sift_all_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, int rows,
+                          float* d_kp, size_t kp_stride, float* d_desc, uint8_t* d_desc_u8, size_t desc_stride,
+                          int32_t* d_n, int32_t* d_over) {
+  return vo_sift_all_found_dev(ctx, d_imgs, img_stride, S, H, W, rows, d_kp, kp_stride, d_desc, d_desc_u8, desc_stride, d_n,
+                               d_over, nullptr);
 }
 
 int vo_sift_batch(vo_ctx* ctx, const uint8_t* imgs, int S, int H, int W, int cap, float* kp_out, float* desc_out,

@@ -210,6 +210,11 @@ extern "C" int vo_match_u8_dev(vo_ctx* ctx, const uint8_t* d_q, const int32_t* d
 extern "C" int vo_match_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride,
                                      int cap_q, const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride,
                                      int cap_t, int S, double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes);
+// vo_sift_all_batch_dev (sift.hip) with d_found[q] (nullable): image q's keypoint count whether or not it fits `rows`, -1
+// when its candidate / keypoint lists overflowed -- what the SIFT tracker mode names when a frame does not fit
+extern "C" int vo_sift_all_found_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, int rows,
+                                     float* d_kp, size_t kp_stride, float* d_desc, uint8_t* d_desc_u8, size_t desc_stride,
+                                     int32_t* d_n, int32_t* d_over, int32_t* d_found);
 // raw (2r+1)^2 patches of the zero-padded image as BYTES, rows padded with zeros to row_bytes (harris.hip)
 extern "C" int vo_patch_descriptors_u8_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const double* d_kp_xy, int N,
                                            int r, uint8_t* d_desc, int row_bytes);

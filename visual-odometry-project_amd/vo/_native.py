@@ -144,6 +144,7 @@ _SIGS = {
     "vo_sift_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "vo_sift_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
     "vo_sift_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vo_sift_all_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
     "vo_fundamental_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
     "vo_fundamental_fit": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "vo_essential_decompose": (_i, [_vp, _vp, _vp]),
@@ -628,6 +629,15 @@ class Context:
     def patch_descriptors_dev(self, d_img, H, W, d_kp, N, r, d_desc):
         self._chk(self._lib.vo_patch_descriptors_dev(self._h, C.c_void_p(d_img), H, W, C.c_void_p(d_kp), int(N),
                                                      int(r), C.c_void_p(d_desc)))
+
+    def sift_all_batch_dev(self, d_imgs, img_stride, S, H, W, rows, d_kp, kp_stride, d_desc, d_desc_u8, desc_stride, d_n,
+                           d_over=None):
+        """Every SIFT keypoint of S images on the device (vo_sift_all_batch_dev); d_desc / d_desc_u8 / d_over may be
+        None.  Image q's count lands in d_n[q], 0 when d_over[q] != 0 (1: list overflow, 2: more than `rows`)."""
+        self._chk(self._lib.vo_sift_all_batch_dev(self._h, C.c_void_p(d_imgs), int(img_stride), int(S), H, W, int(rows),
+                                                  C.c_void_p(d_kp), int(kp_stride), C.c_void_p(d_desc),
+                                                  C.c_void_p(d_desc_u8), int(desc_stride), C.c_void_p(d_n),
+                                                  C.c_void_p(d_over)))
 
 
 class Comm:

@@ -52,7 +52,7 @@ class Pipeline:
         c.debug_never_detect = int(debug_never_detect)
         c.detect_losses = float(detect_losses)
         c.tracker_mode = {"klt": 0, "sift": 1, "harris": 2}[tracker]         # src/vo/features/tracker.py:54-63
-        c.sift_cap = int(sift_cap)
+        c.sift_cap = int(sift_cap)   # SIFT mode: -1 every keypoint (<= feature_cap), 0 n_keypoints, 1..4000 the strongest
         c.match_ratio = float(match_ratio)
         self.tracker = tracker
         self.sequences = int(sequences)
