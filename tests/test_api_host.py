@@ -133,6 +133,35 @@ def test_library_exports_every_declared_symbol():
     assert bound <= names, sorted(bound - names)
 
 
+def _undefined_dynamic_symbols(path):
+    """Names of the undefined symbols in an ELF64 little-endian shared object's .dynsym."""
+    import struct
+    data = open(path, "rb").read()
+    assert data[:6] == b"\x7fELF\x02\x01", "not an ELF64 little-endian file"
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + k * shentsize) for k in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
+        if sh_type != 11:                          # SHT_DYNSYM
+            continue
+        stroff = sections[link][4]
+        for o in range(off, off + size, entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", data, o)
+            if st_shndx == 0 and st_name:          # SHN_UNDEF
+                names.add(data[stroff + st_name:data.index(b"\0", stroff + st_name)].decode())
+    return names
+
+
+def test_library_never_changes_the_environment():
+    """The library only reads environment variables: changing them while another thread reads them is undefined, and a
+    process may hold several pipelines.  libvo_hip.so imports none of setenv / unsetenv / putenv."""
+    from vo import _native
+    undefined = _undefined_dynamic_symbols(_native.lib_path())
+    assert "getenv" in undefined                   # (the parser sees the library's imports)
+    assert not undefined & {"setenv", "unsetenv", "putenv"}, sorted(undefined & {"setenv", "unsetenv", "putenv"})
+
+
 def test_inlier_limit_on_the_sum_of_squares_is_the_reference_decision():
     """p3p.py:81-108 / ransac.py:104-106: inlier <=> norm(dx, dy)**2 < thr.  The hypothesis kernel compares the sum of
     squares with vo_inlier_sum_sq_limit(thr): the limit is the last double that is an inlier, the next one is not, and

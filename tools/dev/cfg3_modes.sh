@@ -13,4 +13,3 @@ export VO_DEBUG_TIMING=1
 run "default"
 GPU_MAX_HW_QUEUES=8 run "8 hw queues"
 VO_HOST_THREADS_BUDGET=1 run "budget 1"
-GPU_MAX_HW_QUEUES=8 VO_SIFT_ONE_CONTEXT=1 run "8 hw queues, one context"

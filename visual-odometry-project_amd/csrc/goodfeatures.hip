@@ -546,10 +546,9 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
   float* d_xy = (float*)s[7].p;
   int n = 0;
   if (min_dist >= 1) {
-    static const bool walk_only = getenv("VO_GREEDY_WALK") != nullptr;      // (measurements: the one-workgroup walk)
     const unsigned n_wg = (nc + GC_T - 1) / GC_T;
     bool done = false;
-    if (!walk_only && n_wg <= (unsigned)GC_WG) {
+    if (n_wg <= (unsigned)GC_WG) {
       VO_TRY(vo_ensure(ctx, s[8], cells * GC_CCAP * 4));
       VO_TRY(vo_ensure(ctx, s[9], (size_t)nc * 4));
       VO_TRY(vo_ensure(ctx, s[10], (size_t)nc * GC_NB * 4));

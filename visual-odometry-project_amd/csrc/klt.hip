@@ -836,9 +836,9 @@ __device__ __forceinline__ void stage16(const uint8_t* __restrict__ img, int pit
 }
 
 template <int WIN, int LPK>
-__device__ __forceinline__ void klt_track16_body(pyr_t P, const float* __restrict__ prev_xy, int N, const int* __restrict__ d_n, vo_klt_source src, vo_klt_batch B, int max_iter,
-                                                 double eps2, float min_eig_thr, float* __restrict__ next_xy,
-                                                 uint8_t* __restrict__ status, float* __restrict__ err) {
+__global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* __restrict__ prev_xy, int N, const int* __restrict__ d_n, vo_klt_source src, vo_klt_batch B, int max_iter,
+                                                         double eps2, float min_eig_thr, float* __restrict__ next_xy,
+                                                         uint8_t* __restrict__ status, float* __restrict__ err) {
   typedef klt_rows<WIN> G;
   constexpr int win = WIN, ww = WIN * WIN, RS = G::RS, n1 = G::n1, n3 = G::n3, K16_PITCH = G::PITCH;
   constexpr int KPW = 64 / LPK;                        // keypoints per wave
@@ -867,9 +867,8 @@ __device__ __forceinline__ void klt_track16_body(pyr_t P, const float* __restric
   if (d_n) N = min(N, *d_n);                           // keypoint count read on the device (frame pipeline)
   int n_own = N;                                       // points 0 .. n_own-1 are prev_xy's, the rest the detector's
   if (src.ts && blockIdx.x == 0 && threadIdx.x == 0) *src.ts = wall_clock64();
-  const bool byp = src.gate_mode == 2 && src.gate_wait != nullptr;   // the regroup's outputs / this kernel's: agent-scope accesses
   if (src.n) {
-    n_own = byp ? vo_ld_agent(src.n) : *src.n;
+    n_own = *src.n;
     const bool redetect = (double)n_own < (double)*src.num_features * src.frac && (!src.det_go || *src.det_go != 0);
     N = min(N, n_own + (redetect ? src.n_det : 0));
   }
@@ -886,9 +885,6 @@ __device__ __forceinline__ void klt_track16_body(pyr_t P, const float* __restric
   if (i >= n_own) {
     p0x = (float)src.det_kp[2 * (i - n_own)];
     p0y = (float)src.det_kp[2 * (i - n_own) + 1];
-  } else if (byp) {
-    p0x = vo_ld_agent(&prev_xy[2 * i]);
-    p0y = vo_ld_agent(&prev_xy[2 * i + 1]);
   } else {
     p0x = prev_xy[2 * i];
     p0y = prev_xy[2 * i + 1];
@@ -1108,41 +1104,10 @@ __device__ __forceinline__ void klt_track16_body(pyr_t P, const float* __restric
     }
   }
   if (r == 0) {
-    if (byp) {
-      vo_st_agent(&next_xy[2 * i], nx);
-      vo_st_agent(&next_xy[2 * i + 1], ny);
-      vo_st_agent(&status[i], (uint8_t)(ok ? 1 : 0));
-      vo_st_agent(&err[i], e_out);
-    } else {
-      next_xy[2 * i] = nx;
-      next_xy[2 * i + 1] = ny;
-      status[i] = ok ? 1 : 0;
-      err[i] = e_out;
-    }
-  }
-}
-
-// The kernel: (optionally) a device-side gate in front of the body -- the previous flight's regroup has published the
-// features this launch tracks -- and an arrival behind it, so that this flight's regroup can poll for the tracker's end
-// instead of waiting for a stream event.
-template <int WIN, int LPK>
-__global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* __restrict__ prev_xy, int N, const int* __restrict__ d_n, vo_klt_source src, vo_klt_batch B, int max_iter,
-                                                         double eps2, float min_eig_thr, float* __restrict__ next_xy,
-                                                         uint8_t* __restrict__ status, float* __restrict__ err) {
-  const size_t coff = (size_t)blockIdx.y * B.ctl;
-  if (src.gate_wait && src.gate_want) {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(src.gate_wait) + coff);
-    if (!vo_gate_wait(w, src.gate_want, src.gate_mode != 2) && threadIdx.x == 0 && src.gate_fault)
-      atomicOr(reinterpret_cast<int*>(reinterpret_cast<char*>(src.gate_fault) + coff), (int)VO_FAULT_GATE_BIT);
-  }
-  klt_track16_body<WIN, LPK>(P, prev_xy, N, d_n, src, B, max_iter, eps2, min_eig_thr, next_xy, status, err);
-  if (src.gate_set) {
-    if (src.gate_mode == 2) vo_stores_done();          // (one wave per workgroup)
-    else __threadfence();
-    if (threadIdx.x == 0)
-      vo_gate_arrive(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(src.gate_cnt) + coff), gridDim.x,
-                     reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(src.gate_set) + coff), src.gate_set_to,
-                     src.gate_mode != 2);
+    next_xy[2 * i] = nx;
+    next_xy[2 * i + 1] = ny;
+    status[i] = ok ? 1 : 0;
+    err[i] = e_out;
   }
 }
 
@@ -1318,19 +1283,13 @@ int vo_klt_track_ndev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_
     const float me = (float)min_eig;
     const dim3 kgrid(vo_cdiv(N, KLT_WAVES), S), kblock(64 * KLT_WAVES);
     switch (win) {
-      case 15: {
-        // 16 lanes per keypoint (four per wave).  VO_KLT_LPK=32: two per wave, the upper half of each group idle in the row
-        // loops, the 18 rows of the template block in one pass instead of two -- measured slower (round 3: step 87.6 ->
-        // 91.3 us at one sequence, the kernel 199 -> 351 us at 16), kept as the measurement's knob.
-        static const int lpk_env = getenv("VO_KLT_LPK") ? atoi(getenv("VO_KLT_LPK")) : 0;
-        if (lpk_env == 32)
-          vo_launch_stop(ctx, klt_track16_kernel<15, 32>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
-                         max_iter, eps * eps, me, d_next_xy, d_status, d_err);
-        else
-          vo_launch_stop(ctx, klt_track16_kernel<15, 16>, dim3(vo_cdiv(N, 4), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
-                         max_iter, eps * eps, me, d_next_xy, d_status, d_err);
+      case 15:
+        // 16 lanes per keypoint (four per wave).  32 lanes per keypoint (two per wave, the upper half of each group idle in
+        // the row loops, the 18 rows of the template block in one pass instead of two) measured slower: round 3, step 87.6 ->
+        // 91.3 us at one sequence, the kernel 199 -> 351 us at 16.
+        vo_launch_stop(ctx, klt_track16_kernel<15, 16>, dim3(vo_cdiv(N, 4), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
+                       max_iter, eps * eps, me, d_next_xy, d_status, d_err);
         break;
-      }
       case 17:   // the reference's default window (klt.py:29)
         vo_launch_stop(ctx, klt_track16_kernel<17, 32>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
                        max_iter, eps * eps, me, d_next_xy, d_status, d_err);

@@ -165,14 +165,7 @@ struct vo_pipeline {
   std::atomic<bool> quit{false};
   int threads_budget = 2;
   double spin_s = 150e-6;
-  // Device-side gates instead of stream events between the tracker's stream and the main stream (vo_seq_ctl): used for
-  // the launches of vo_pipeline_submit when the side streams keep off some compute units (one or two sequences), so
-  // that a polling kernel can never keep the kernel it waits for from running.  After anything was enqueued again for
-  // one sequence (host path, a continuing RANSAC loop, a rewind) the next submit also waits for the events.
-  std::string det_key, trk_key;      // what the side contexts' streams were created with (side_pool)
-  bool gates = false, gate_resync = false;
-  int gate_mode = 1;                 // vo_internal.h, vo_gate_wait
-  bool ext_events = true;            // see enqueue_tracker
+  vo_stream_cfg side_cfg;            // what the side contexts' streams were created with (side_pool)
   int sift_chain_pending = 0;        // SIFT mode: flights whose main-stream chain is not enqueued yet (their SIFT launches are
                                      // being made by the worker; the chain follows at the next submit or at collect)
   flight_t jobs[4];
@@ -242,10 +235,6 @@ __global__ __launch_bounds__(64) void ctl_rewind_kernel(vo_seq_ctl* __restrict__
   c.outlier_ratio = ctl[q].outlier_ratio;
   c.raw_pos = ctl[q].raw_pos;
   c.step = ctl[q].step;
-  c.gate_regroup = ctl[q].gate_regroup;
-  c.gate_regroup_cnt = ctl[q].gate_regroup_cnt;
-  c.gate_klt = ctl[q].gate_klt;
-  c.gate_klt_cnt = ctl[q].gate_klt_cnt;
   ctl[q] = c;
 }
 
@@ -436,7 +425,7 @@ void sync_prof(vo_pipeline* p) {
 // VO_SIDE_POOL=0: off.
 struct side_entry {
   int device;
-  std::string key;
+  vo_stream_cfg key;
   vo_ctx* c;
 };
 static std::mutex g_side_mu;
@@ -459,18 +448,14 @@ static bool side_pool_evicts() {
   static const bool on = !(getenv("VO_SIDE_POOL_EVICT") && getenv("VO_SIDE_POOL_EVICT")[0] == '0');
   return on;
 }
-static std::string side_key() {      // of a context created NOW (vo_create reads the same variables)
-  const char* cus = getenv("VO_STREAM_CUS");
-  const char* pr = getenv("VO_STREAM_PRIORITY");
-  return std::string("cus=") + (cus ? cus : "") + ";prio=" + (pr ? pr : "");
-}
-static void side_evict_except(int device, const std::string& ka, const std::string& kb) {
+// device < 0: every context goes
+static void side_evict_except(int device, const vo_stream_cfg& keep) {
   std::vector<vo_ctx*> gone;
   {
     std::lock_guard<std::mutex> lk(g_side_mu);
     auto& v = side_pool();
     for (size_t i = 0; i < v.size();) {
-      if (device < 0 || (v[i].device == device && v[i].key != ka && v[i].key != kb)) {
+      if (device < 0 || (v[i].device == device && !(v[i].key == keep))) {
         gone.push_back(v[i].c);
         v.erase(v.begin() + (long)i);
       } else {
@@ -480,7 +465,7 @@ static void side_evict_except(int device, const std::string& ka, const std::stri
   }
   for (vo_ctx* c : gone) vo_destroy(c);
 }
-static int side_take(int device, const std::string& key, vo_ctx** out) {
+static int side_take(int device, const vo_stream_cfg& key, vo_ctx** out) {
   if (side_pool_on()) {
     std::lock_guard<std::mutex> lk(g_side_mu);
     auto& v = side_pool();
@@ -491,9 +476,9 @@ static int side_take(int device, const std::string& key, vo_ctx** out) {
         return VO_OK;
       }
   }
-  return vo_create(device, nullptr, out);
+  return vo_create_stream(device, nullptr, key, out);
 }
-static void side_give(vo_ctx* c, const std::string& key) {
+static void side_give(vo_ctx* c, const vo_stream_cfg& key) {
   if (!c) return;
   if (side_pool_on() && c->own_stream) {
     c->prof_on = false;
@@ -507,7 +492,7 @@ static void side_give(vo_ctx* c, const std::string& key) {
     // the profiler they are left alone: a process about to end gains nothing from a call that stalls once in a few hundred.
     // VO_SIDE_POOL_ATEXIT=1 / 0 overrides.
     static const bool at_exit = (std::atexit([] {
-                                   if (side_pool_destroy_at_exit()) side_evict_except(-1, "", "");
+                                   if (side_pool_destroy_at_exit()) side_evict_except(-1, {});
                                  }),
                                  true);
     (void)at_exit;
@@ -577,8 +562,8 @@ void vo_pipeline_destroy(vo_pipeline* p) {
                        p->evKlt[0], p->evKlt[1], p->evRegroup[0], p->evRegroup[1]})
     if (e) (void)hipEventDestroy(e);
   dbg_stage("destroy: events destroyed");
-  if (p->det) (p->det->own_stream ? side_give(p->det, p->det_key) : vo_destroy(p->det));
-  if (p->trk) (p->trk->own_stream ? side_give(p->trk, p->trk_key) : vo_destroy(p->trk));
+  if (p->det) (p->det->own_stream ? side_give(p->det, p->side_cfg) : vo_destroy(p->det));
+  if (p->trk) (p->trk->own_stream ? side_give(p->trk, p->side_cfg) : vo_destroy(p->trk));
   dbg_stage("destroy: side contexts handed back");
   if (getenv("VO_DEBUG_TIMING") && p->dbg_steps > 0)
     fprintf(stderr, "[vo_pipeline] %ld steps x %d sequence(s): host %.1f us enqueueing (worker wait %.1f, tracker %.1f, raws %.1f, "
@@ -622,7 +607,6 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   p->detect_losses = p->cfg.detect_losses;
   p->detect_limit = p->cfg.detect_margin < 0.0 ? -1.0 : p->cfg.redetect_fraction + p->cfg.detect_margin;
   if (p->cfg.debug_never_detect) p->detect_limit = 0.0;     // test hook: only forced detections (state hand-over, host path)
-  if (const char* e = getenv("VO_DETECT_LOSSES")) p->detect_losses = atof(e);
   {
     bool given = false;
     for (double v : cfg->Kinv) given |= v != 0.0;
@@ -640,62 +624,26 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   // kernel's duration without the others running beside it)
   void* side = getenv("VO_ONE_STREAM") ? (void*)ctx->stream : nullptr;
   {
-    // VO_SIDE_PRIORITY=low: tracker and detection streams at the device's least priority (measurement knob)
-    const char* sp = getenv("VO_SIDE_PRIORITY");
-    const char* saved = getenv("VO_STREAM_PRIORITY");
-    std::string keep = saved ? saved : "";
-    if (sp) setenv("VO_STREAM_PRIORITY", sp, 1);
     // Tracker and detection streams keep off the first 32 compute units when the pipeline runs one or two sequences with
     // the detector gated: the next frame's pyramid (858 workgroups) reaches the GPU beside the hypothesis kernel's 144,
     // and that kernel then takes 44 us instead of 23 -- its workgroups wait for a place behind the pyramid's -- unless
     // some compute units stay out of the side streams' reach (measured: 32 of the 256 are enough, 16 are not; step period
     // 122 -> 102 us).  With many sequences, or the detector on every frame, the side streams' kernels are the throughput and
     // the mask costs more than it gives (16 sequences: -5 %).  VO_SIDE_CUS="lo-hi" overrides, "all" switches it off.
+    // VO_STREAM_PRIORITY applies to the side streams as to vo_create; VO_STREAM_CUS does not.
     const char* sc = getenv("VO_SIDE_CUS");
-    std::string auto_mask;
+    p->side_cfg = vo_stream_cfg_parse(sc, getenv("VO_STREAM_PRIORITY"));
     if (!sc && p->S <= 2 && p->detect_limit >= 0.0 && !side && cfg->tracker_mode == 0) {   // (KLT mode only)
       hipDeviceProp_t prop;
       if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount >= 128) {
-        auto_mask = "32-" + std::to_string(prop.multiProcessorCount - 1);
-        sc = auto_mask.c_str();
+        p->side_cfg.cu_lo = 32;
+        p->side_cfg.cu_hi = prop.multiProcessorCount - 1;
       }
     }
-    if (sc && !strcmp(sc, "all")) sc = nullptr;
-    {
-      const int w = cfg->klt_win;
-      const char* g = getenv("VO_GATES");
-      // Off unless VO_GATES=1.  Measured: the two event waits they replace cost 17-19 us each, but every polling
-      // workgroup needs an acquire at agent scope when its gate opens and a release before it arrives, and on this part
-      // those are an invalidate / a write-back of the XCD's L2: with ~1000 tracker workgroups per frame the hypothesis and
-      // pose kernels running beside them lose their cached population over and over (hypotheses -> pose 23 -> 40 us,
-      // pose 34 -> 45, step 103 -> 133 us).  The gates would need the gated data to bypass L2 altogether.
-      p->ext_events = !(getenv("VO_EXT_EVENTS") && getenv("VO_EXT_EVENTS")[0] == '0');
-      p->gates = sc != nullptr && p->S <= 2 && !side && (w == 15 || w == 17 || w == 21) && g && (g[0] == '1' || g[0] == '2');
-      p->gate_mode = g && g[0] == '2' ? 2 : 1;
-    }
-    const char* saved_c = getenv("VO_STREAM_CUS");
-    std::string keep_c = saved_c ? saved_c : "";
-    const char* dc = getenv("VO_DET_CUS");     // (the detection stream's own range; default: VO_SIDE_CUS)
-    if (dc || sc) setenv("VO_STREAM_CUS", dc ? dc : sc, 1);
-    else unsetenv("VO_STREAM_CUS");
-    p->det_key = side_key();
-    const std::string det_cus = getenv("VO_STREAM_CUS") ? getenv("VO_STREAM_CUS") : "";
-    if (sc) setenv("VO_STREAM_CUS", sc, 1);
-    else unsetenv("VO_STREAM_CUS");
-    p->trk_key = side_key();
-    if (!side && side_pool_evicts()) side_evict_except(ctx->device, p->det_key, p->trk_key);
-    if ((side ? vo_create(ctx->device, side, &p->trk) : side_take(ctx->device, p->trk_key, &p->trk)) != VO_OK)
-      rc = vo_set_error(ctx, VO_EHIP, "pipeline: cannot create the side streams");
-    if (!det_cus.empty()) setenv("VO_STREAM_CUS", det_cus.c_str(), 1);
-    else unsetenv("VO_STREAM_CUS");
-    if ((side ? vo_create(ctx->device, side, &p->det) : side_take(ctx->device, p->det_key, &p->det)) != VO_OK)
-      rc = vo_set_error(ctx, VO_EHIP, "pipeline: cannot create the side streams");
-    if (sp) {
-      if (saved) setenv("VO_STREAM_PRIORITY", keep.c_str(), 1);
-      else unsetenv("VO_STREAM_PRIORITY");
-    }
-    if (saved_c) setenv("VO_STREAM_CUS", keep_c.c_str(), 1);
-    else unsetenv("VO_STREAM_CUS");
+    if (!side && side_pool_evicts()) side_evict_except(ctx->device, p->side_cfg);
+    for (vo_ctx** c : {&p->trk, &p->det})
+      if ((side ? vo_create_stream(ctx->device, side, p->side_cfg, c) : side_take(ctx->device, p->side_cfg, c)) != VO_OK)
+        rc = vo_set_error(ctx, VO_EHIP, "pipeline: cannot create the side streams");
   }
   dbg_stage("create: side streams made");
   const int N = cfg->n_keypoints, Hyp = cfg->hyp;
@@ -848,7 +796,7 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
 
 // The side contexts kept from closed pipelines (side_pool above) are destroyed now.  For a process that goes on WITHOUT a
 // pipeline and wants its other queues at full speed (live CU-masked queues slow every queue of the process).
-void vo_pipeline_release_cached(void) { side_evict_except(-1, "", ""); }
+void vo_pipeline_release_cached(void) { side_evict_except(-1, {}); }
 int vo_pipeline_release_cached_at_exit(void) { return side_pool_destroy_at_exit() ? 1 : 0; }
 
 int vo_pipeline_feature_cap(vo_pipeline* p) { return p ? p->cap : 0; }
@@ -1124,14 +1072,13 @@ static vo_pose_job make_pose_job(vo_pipeline* p, const vo_feat& B, int do_replay
 
 // tracker of one step, on its own stream: it needs the previous step's regroup (the features' positions) and this
 // frame's pyramid, nothing of the previous step's pose estimation, which runs beside it on the main stream
-static int enqueue_tracker(vo_pipeline* p, const vo_pipeline::flight_t& f, bool with_pyramid, int q0, int Sn,
-                           bool gated = false) {
+static int enqueue_tracker(vo_pipeline* p, const vo_pipeline::flight_t& f, bool with_pyramid, int q0, int Sn) {
   vo_ctx* ctx = p->ctx;
   const vo_pipeline_config& c = p->cfg;
   const vo_feat A = vo_feat_seq(p->F[f.fcur], (size_t)q0);
   hipStream_t ts = p->trk->stream;
   if (with_pyramid) VO_TRY(enqueue_pyramid(p, f.next_idx, f.b));
-  if ((!gated || p->gate_resync) && f.k > 0 && hipEventQuery(p->evRegroup[(f.k - 1) & 1]) != hipSuccess)
+  if (f.k > 0 && hipEventQuery(p->evRegroup[(f.k - 1) & 1]) != hipSuccess)
     VO_HIP_TRY(ctx, hipStreamWaitEvent(ts, p->evRegroup[(f.k - 1) & 1], 0));
   if (hipEventQuery(p->evDet[f.a]) != hipSuccess) VO_HIP_TRY(ctx, hipStreamWaitEvent(ts, p->evDet[f.a], 0));
   vo_seq_ctl* ctl = p->d_ctl + q0;
@@ -1143,15 +1090,6 @@ static int enqueue_tracker(vo_pipeline* p, const vo_pipeline::flight_t& f, bool 
   src.n_det = c.n_keypoints;
   src.ts = &ctl->ts[0];
   src.det_go = p->d_det_go + (size_t)f.a * p->S + q0;
-  if (gated) {
-    src.gate_wait = &ctl->gate_regroup;
-    src.gate_want = (uint32_t)f.k;                    // published by the regroup of flight k - 1 (or a state hand-over)
-    src.gate_set = &ctl->gate_klt;
-    src.gate_cnt = &ctl->gate_klt_cnt;
-    src.gate_set_to = (uint32_t)f.k + 1u;
-    src.gate_fault = &ctl->fault;
-    src.gate_mode = p->gate_mode;
-  }
   vo_klt_batch kb;
   kb.S = Sn;
   kb.pyr = p->pyr_stride();
@@ -1161,9 +1099,8 @@ static int enqueue_tracker(vo_pipeline* p, const vo_pipeline::flight_t& f, bool 
   kb.det = p->det_stride();
   // The tracker's and the regroup's events are the kernels' own completion signals (vo_ctx::next_stop), not markers behind
   // them: a marker between the regroup and the hypothesis kernel cost the main chain 3.7 us, the tracker started 3.4 us
-  // later behind it (step 85.8 -> 84.2 us).  VO_EXT_EVENTS=0: hipEventRecord.
-  const bool ext_events = p->ext_events;
-  if (ext_events) p->trk->next_stop = p->evKlt[f.k & 1];
+  // later behind it (step 85.8 -> 84.2 us).
+  p->trk->next_stop = p->evKlt[f.k & 1];
   {
     const size_t q = (size_t)q0;
     const int rc = vo_klt_track_ndev(p->trk, p->img(q0, f.prev_idx), p->pyr(q0, f.a), p->img(q0, f.next_idx), p->pyr(q0, f.b),
@@ -1175,8 +1112,6 @@ static int enqueue_tracker(vo_pipeline* p, const vo_pipeline::flight_t& f, bool 
   if (p->trk->next_stop) {             // (the launch did not take the event)
     p->trk->next_stop = nullptr;
     VO_HIP_TRY(ctx, hipEventRecord(p->evKlt[f.k & 1], ts));
-  } else if (!ext_events) {
-    VO_HIP_TRY(ctx, hipEventRecord(p->evKlt[f.k & 1], ts));
   }
   return VO_OK;
 }
@@ -1186,17 +1121,14 @@ static int enqueue_pose_half(vo_pipeline* p, const vo_pipeline::flight_t& f, int
 // the main-stream chain of one step (the tracker's event must have been recorded);
 // first_half_only: stop behind the regroup (recover_step continues on the host)
 static int enqueue_chain(vo_pipeline* p, const vo_pipeline::flight_t& f, bool first_half_only, int debug_fault_every,
-                         int q0, int Sn, unsigned seq, bool gated = false) {
+                         int q0, int Sn, unsigned seq) {
   vo_ctx* ctx = p->ctx;
   const vo_pipeline_config& c = p->cfg;
   const size_t q = (size_t)q0;
   const vo_feat A = vo_feat_seq(p->F[f.fcur], q), B = vo_feat_seq(p->F[1 - f.fcur], q);
   vo_seq_ctl* ctl = p->d_ctl + q0;
-  if (!gated) VO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p->evKlt[f.k & 1], 0));
+  VO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, p->evKlt[f.k & 1], 0));
   vo_append ap;
-  ap.gate_klt_want = gated ? (uint32_t)f.k + 1u : 0u;
-  ap.gate_regroup_set = gated ? (uint32_t)f.k + 1u : 0u;
-  ap.gate_mode = p->gate_mode;
   ap.det_kp = p->kp(q0, f.a);
   ap.det_stride = p->det_stride();
   ap.n_det = c.n_keypoints;
@@ -1204,11 +1136,9 @@ static int enqueue_chain(vo_pipeline* p, const vo_pipeline::flight_t& f, bool fi
   ap.pose_mode = c.redetect_start_pose;
   ap.debug_fault_every = debug_fault_every > 0 ? debug_fault_every : 0;
   ap.det_go = p->d_det_go + (size_t)f.a * p->S + q0;
-  const bool ext_events = p->ext_events;
-  if (ext_events) ctx->next_stop = p->evRegroup[f.k & 1];
+  ctx->next_stop = p->evRegroup[f.k & 1];
   VO_TRY(vo_state_regroup_klt(ctx, ctl, A, B, p->d_next + q * p->cap * 2, p->d_status + q * p->cap, p->d_err + q * p->cap,
                               (float)c.klt_err_threshold, ap, p->cap, Sn));
-  if (!ext_events) VO_HIP_TRY(ctx, hipEventRecord(p->evRegroup[f.k & 1], ctx->stream));
   if (first_half_only) return VO_OK;
   return enqueue_pose_half(p, f, q0, Sn, seq);
 }
@@ -1234,42 +1164,23 @@ static int enqueue_pose_half(vo_pipeline* p, const vo_pipeline::flight_t& f, int
                                     p->ring_len - 1, c.hyp, c.p3p_thr_sq, p->d_R + q * c.hyp * 9, p->d_t + q * c.hyp * 3,
                                     p->d_valid + q * c.hyp, p->d_counts + q * c.hyp, p->d_masks + q * c.hyp * p->words,
                                     (uint32_t*)&ctl->solve_flag, (uint64_t*)&ctl->ts[2], &hb));
-  // pose, candidates, candidate triangulation, landmark update and the record in one launch (frame_pose_kernel's tail)
+  // The pose kernel stops behind the refinement (walk = 0).  The feature walk (reset_outliers, bearing-angle candidates: fp64
+  // arithmetic of every feature) was the last third of the pose kernel, on its ONE compute unit: 10 us; as a launch of its
+  // own, cap / 256 workgroups, the step period went 93.4 -> 87.8 us.  Walk and landmark stage now run in ONE launch
+  // (state_walk_landmarks_kernel), one boundary less.  (Round 2 had the pose kernel's one workgroup go on with the landmark
+  // stage -- frame_pose_kernel's tail -- which was neutral at ~450 candidates per frame on a stream that never lost a track;
+  // the forward stream triangulates ~1100 per frame, three rounds of DLTs for one workgroup: 50 us against 18 for the
+  // launch, its boundary included; step period 152 -> 121 us.)
   vo_pose_job job = make_pose_job(p, p->F[1 - f.fcur], 1, q0);
-  job.tail = 1;
+  job.walk = 0;
   job.res = p->m_res + (size_t)f.rslot * p->S + q;
   job.seq_word = p->m_seq + (size_t)f.rslot * p->S + q;
   job.seq = seq;
   job.debug_fault_every = debug_pose_fault;
-  // The landmark stage as its own launch of cap / 256 workgroups per sequence.  (Round 2 had the pose kernel's one
-  // workgroup go on with it -- VO_FUSED_TAIL=1 -- which was neutral at ~450 candidates per frame on a stream that never
-  // lost a track; the forward stream triangulates ~1100 per frame, three rounds of DLTs for one workgroup: 50 us
-  // against 18 for the launch, its boundary included; step period 152 -> 121 us.)
-  static const bool split_tail = getenv("VO_FUSED_TAIL") == nullptr;
-  if (split_tail) {
-    // The feature walk (reset_outliers, bearing-angle candidates: fp64 arithmetic of every feature) was the last third of the
-    // pose kernel, on its ONE compute unit: 10 us.  VO_SPLIT_WALK=1: a launch of its own, cap / 256 workgroups, between the pose
-    // kernel and the landmark stage (step period 93.4 -> 87.8 us); default (2): walk and landmark stage in ONE launch
-    // (state_walk_landmarks_kernel), one boundary less; 0: the walk inside the pose kernel.
-    static const int walk_mode = getenv("VO_SPLIT_WALK") ? atoi(getenv("VO_SPLIT_WALK")) : 2;
-    job.tail = 0;
-    job.walk = walk_mode ? 0 : 1;
-    VO_TRY(vo_frame_pose(ctx, job, Sn));
-    const uint64_t* bm = p->d_best_mask + (size_t)q0 * p->words;
-    const int rec_refined = c.refine_iters > 0 ? 1 : 0;
-    if (walk_mode == 2) {
-      VO_TRY(vo_state_walk_landmarks(ctx, ctl, B, bm, p->words, p->d_cams + q0, c.bearing_threshold, rec_refined, p->cap,
-                                     p->d_pend + q * p->cap, job.res, job.seq_word, seq, Sn));
-      return VO_OK;
-    }
-    if (walk_mode == 1)
-      VO_TRY(vo_state_candidates(ctx, ctl, B, bm, p->d_cams + q0, c.bearing_threshold, 1 /* ctl->refined: what the pose kernel's walk uses */,
-                                 p->cap, Sn, p->words));
-    VO_TRY(vo_state_landmarks(ctx, ctl, B, p->d_cams + q0, rec_refined, p->cap, job.res, job.seq_word, seq, Sn));
-    return VO_OK;
-  }
   VO_TRY(vo_frame_pose(ctx, job, Sn));
-  return VO_OK;
+  const uint64_t* bm = p->d_best_mask + (size_t)q0 * p->words;
+  return vo_state_walk_landmarks(ctx, ctl, B, bm, p->words, p->d_cams + q0, c.bearing_threshold, c.refine_iters > 0 ? 1 : 0,
+                                 p->cap, p->d_pend + q * p->cap, job.res, job.seq_word, seq, Sn);
 }
 
 // ---- SIFT tracker mode ----
@@ -1282,8 +1193,7 @@ extern "C" int vo_sift_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, int 
 //  its own streams and arena, so that two frames' chains are in flight side by side.  The launches are made by the worker
 //  thread; err_buf: its private error text.)
 static int enqueue_sift(vo_pipeline* p, const vo_pipeline::flight_t& f, char* err_buf = nullptr) {
-  static const bool one_ctx = getenv("VO_SIFT_ONE_CONTEXT") != nullptr;
-  vo_ctx* sc = ((f.k & 1) && !one_ctx) ? p->det : p->trk;
+  vo_ctx* sc = (f.k & 1) ? p->det : p->trk;
   const vo_pipeline_config& c = p->cfg;
   int rc = VO_OK;
   if (sc != p->trk && hipStreamWaitEvent(sc->stream, p->evImg[f.next_idx], 0) != hipSuccess) rc = VO_EHIP;   // (the upload)
@@ -1500,14 +1410,11 @@ static int upload_state(vo_pipeline* p, int seq, int n, const double* kp, const 
   const uint64_t raw_pos = raw_pos_set ? *raw_pos_set : h.raw_pos;
   const int64_t n_it = h.n_iterations;
   const double orat = h.outlier_ratio;
-  const uint32_t gate_klt = h.gate_klt;
   memset(&h, 0, sizeof(h));
   h.n = n;
   h.n2 = n;
   h.num_features = num_features;
   h.raw_pos = raw_pos;
-  h.gate_regroup = (uint32_t)p->steps_submitted;      // the features the next flight's tracker waits for are these
-  h.gate_klt = gate_klt;
   if (keep_ransac) {
     h.n_iterations = n_it;
     h.outlier_ratio = orat;
@@ -1644,7 +1551,6 @@ extern "C" int vo_pipeline_rewind(vo_pipeline* p) {
   else VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   p->slot = 0;
   p->prev_frame = p->ckpt_frame;
-  p->gate_resync = true;             // (the next tracker waits for that event, not only for its gate)
   return prime(p, false);            // pyramid + detector of that frame, queued on their streams
 }
 
@@ -1721,7 +1627,6 @@ int vo_pipeline_restart_seq(vo_pipeline* p, int seq, int idx, int n, const doubl
   VO_TRY(upload_state(p, seq, n, kp, state, landmarks, tracks, poses, T_wc, T_cw, T_wc_prev, T_cw_prev, num_features, false,
                       &p->gen_upto[seq]));
   p->seq_state[seq] = 1;
-  p->gate_resync = true;
   // a prepared pyramid may hold this lane's old frame (or be read behind a pyramid rebuilt below): it goes
   p->prepared_idx = p->prepared_slot = -1;
   if (p->primed) {                     // (else the first submit's prime() makes every sequence's)
@@ -1930,7 +1835,7 @@ int vo_pipeline_submit(vo_pipeline* p, int prev_idx, int next_idx) {
   tq = tn;
   const bool have_pyr = p->prepared_idx == next_idx && p->prepared_slot == f.b;
   p->prepared_idx = p->prepared_slot = -1;
-  VO_TRY(enqueue_tracker(p, f, !have_pyr, 0, p->S, p->gates));
+  VO_TRY(enqueue_tracker(p, f, !have_pyr, 0, p->S));
   tn = now_s();
   p->dbg_part[1] += tn - tq;
   tq = tn;
@@ -1938,8 +1843,7 @@ int vo_pipeline_submit(vo_pipeline* p, int prev_idx, int next_idx) {
   tn = now_s();
   p->dbg_part[2] += tn - tq;
   tq = tn;
-  VO_TRY(enqueue_chain(p, f, false, c.debug_fault_every, 0, p->S, f.seq, p->gates));
-  p->gate_resync = false;
+  VO_TRY(enqueue_chain(p, f, false, c.debug_fault_every, 0, p->S, f.seq));
   for (int q = 0; q < p->S; ++q) p->slot_seq[(size_t)f.rslot * p->S + q] = f.seq;
   if (p->threads_budget < 2) VO_TRY(enqueue_detection(p, f.next_idx, f.b, false));   // (needed by the NEXT step only)
   else if (!detect_early) VO_TRY(post_detection());
@@ -2244,7 +2148,6 @@ int vo_pipeline_collect_all(vo_pipeline* p, vo_step_result* outs) {
       return rc;
     }
     if (out->fault || was_open) {
-      p->gate_resync = true;             // (what is enqueued again below is ordered by events, and so is the next submit)
       rc = out->fault ? recover_step(p, f, q, out) : VO_OK;
       // steps submitted behind it saw the fault and did nothing for this sequence: their main-stream chains are
       // enqueued again for it alone (pyramids and detections are done and still in place)

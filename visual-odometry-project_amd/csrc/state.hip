@@ -229,20 +229,38 @@ __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restr
 }
 
 
-// (the body of state_regroup_klt_kernel: it returns early on several paths, the kernel's gates sit around it)
-template <bool BYP>
-__device__ __forceinline__ void regroup_klt_body(vo_seq_ctl* __restrict__ ctl, vo_feat A, vo_feat B,
-                                                 const float* __restrict__ next_xy, const uint8_t* __restrict__ status,
-                                                 const float* __restrict__ err, float err_thr, vo_append ap, int cap,
-                                                 unsigned long long (&s_red)[2][4], int (&s_wcnt)[3][4]) {
+// ---------------------------------------------------------------------------------------------
+// klt.py:191-280 behind the tracker + Matches.__init__ (matches.py:26-212) for identity matches, many workgroups,
+// none of which waits for another: every workgroup of 256 items counts the group sizes of ALL items itself (a few
+// KB of flags, coalesced, from L2) and the sizes before its own first item, so an item's place in the new frame
+//     base(group) + #(same group before the workgroup) + #(same group before it inside the workgroup)
+// needs no communication.  The re-detect branch (klt.py:207-230 -> update_features, klt.py:117-189) is not a
+// copy: when fewer than frac * _num_features features are left, items n .. n + n_det - 1 ARE the detector's
+// keypoints of the old frame (state 0, landmark NaN, track start = the keypoint, start pose np.eye(4)) -- the
+// tracker kernel read its points the same way (vo_klt_source).
+__global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat A, vo_feat B,
+                                                                const float* __restrict__ next_xy,
+                                                                const uint8_t* __restrict__ status,
+                                                                const float* __restrict__ err, float err_thr,
+                                                                vo_append ap, int cap) {
+  __shared__ unsigned long long s_red[2][4];
+  __shared__ int s_wcnt[3][4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (blockIdx.y != 0) {               // several sequences per launch: grid.y = sequence
+    const size_t q = blockIdx.y;
+    ctl += q;
+    A = vo_feat_seq(A, q);
+    B = vo_feat_seq(B, q);
+    next_xy += q * (size_t)cap * 2;
+    status += q * (size_t)cap;
+    err += q * (size_t)cap;
+    ap.det_kp += q * ap.det_stride;
+  }
+  if (blockIdx.x == 0 && tid == 0) {
+    ctl->ts[1] = wall_clock64();
+    ctl->ts[6] = ctl->ts[0];          // this step's tracker start (the next step's tracker overwrites ts[0] meanwhile)
+  }
   constexpr int RG_U = 16;
-  // gate form 2 (vo_internal.h): the tracker's outputs are read, the positions and the count the next tracker reads are written
-  // with agent-scope accesses
-  constexpr bool byp = BYP;    // (a template parameter: as a run-time flag it cost the ungated kernel 1.7 us -- its sixteen-at-a-time
-                               //  loads no longer went out together)
-  auto ld_status = [&](int j) -> int { return byp ? (int)vo_ld_agent(&status[j]) : (int)status[j]; };
-  auto ld_err = [&](int j) -> float { return byp ? vo_ld_agent(&err[j]) : err[j]; };
   const int start = blockIdx.x * 256;
   const int entry_fault = ctl->fault;
   int fault = entry_fault;
@@ -276,14 +294,14 @@ __device__ __forceinline__ void regroup_klt_body(vo_seq_ctl* __restrict__ ctl, v
 #pragma unroll
   for (int u = 0; u < RG_U; ++u) {
     const int j = u * 256 + tid;
-    r_s8[u] = ld_status(min(j, capm));
-    r_e[u] = ld_err(min(j, capm));
+    r_s8[u] = status[min(j, capm)];
+    r_e[u] = err[min(j, capm)];
     r_st[u] = A.state[min(j, pitm)];
   }
   const int jo = start + tid, jq = min(jo, pitm), jx = min(jo, capm);
   double o_land[3], o_track[2], o_kp[2], o_pose[12];
-  const float o_nx = byp ? vo_ld_agent(&next_xy[2 * jx]) : next_xy[2 * jx];
-  const float o_ny = byp ? vo_ld_agent(&next_xy[2 * jx + 1]) : next_xy[2 * jx + 1];
+  const float o_nx = next_xy[2 * jx];
+  const float o_ny = next_xy[2 * jx + 1];
 #pragma unroll
   for (int k = 0; k < 3; ++k) o_land[k] = A.land[3 * jq + k];
 #pragma unroll
@@ -297,8 +315,8 @@ __device__ __forceinline__ void regroup_klt_body(vo_seq_ctl* __restrict__ ctl, v
     // (unconditional loads at clamped indices, no short-circuit: the three requests of an item, and those of the
     //  following items, go out together instead of one dependent round trip after the other)
     const int jc = min(j, n_in - 1), js = min(j, max(n - 1, 0));
-    const int s8 = ld_status(jc);
-    const float e = ld_err(jc);
+    const int s8 = status[jc];
+    const float e = err[jc];
     const int st_raw = A.state[js];
     const int keep = (int)(j < n_in) & (int)(s8 != 0) & (int)(e < err_thr);
     const int st = j < n ? st_raw : 0;
@@ -363,13 +381,8 @@ __device__ __forceinline__ void regroup_klt_body(vo_seq_ctl* __restrict__ ctl, v
     if (j < n) {
       // (write_group, from the registers filled above)
       const double nan = dnan();
-      if (byp) {
-        vo_st_agent(&B.kp[2 * dst], (float)x);
-        vo_st_agent(&B.kp[2 * dst + 1], (float)y);
-      } else {
-        B.kp[2 * dst] = (float)x;
-        B.kp[2 * dst + 1] = (float)y;
-      }
+      B.kp[2 * dst] = (float)x;
+      B.kp[2 * dst + 1] = (float)y;
       B.kp64[2 * dst] = x;
       B.kp64[2 * dst + 1] = y;
       B.cand[dst] = 0;
@@ -391,13 +404,8 @@ __device__ __forceinline__ void regroup_klt_body(vo_seq_ctl* __restrict__ ctl, v
     } else {
       // a keypoint the detector found on the old frame, tracked: "newly matched" (matches.py:62-110)
       const int d = j - n;
-      if (byp) {
-        vo_st_agent(&B.kp[2 * dst], (float)x);
-        vo_st_agent(&B.kp[2 * dst + 1], (float)y);
-      } else {
-        B.kp[2 * dst] = (float)x;
-        B.kp[2 * dst + 1] = (float)y;
-      }
+      B.kp[2 * dst] = (float)x;
+      B.kp[2 * dst + 1] = (float)y;
       B.kp64[2 * dst] = x;
       B.kp64[2 * dst + 1] = y;
       B.cand[dst] = 0;
@@ -414,64 +422,13 @@ __device__ __forceinline__ void regroup_klt_body(vo_seq_ctl* __restrict__ ctl, v
     ctl->n_in = n_in;
     ctl->redetected = redetect ? 1 : 0;
     ctl->det_ran = ap.det_go ? ap.det_go[blockIdx.y] : 1;
-    if (byp) vo_st_agent(&ctl->n2, T0 + T1 + T2);
-    else ctl->n2 = T0 + T1 + T2;
+    ctl->n2 = T0 + T1 + T2;
     ctl->n_tri = T0;
     ctl->n_mat = T1;
     ctl->n_new = T2;
     const int few = T0 < 8 ? VO_FAULT_FEW_LANDMARKS : 0;   // (population below what the device-side sampler handles)
     ctl->n_p3p = few ? 0 : T0;
     ctl->few = few;                    // (not into ctl->fault: this launch's other workgroups read that word on entry)
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// klt.py:191-280 behind the tracker + Matches.__init__ (matches.py:26-212) for identity matches, many workgroups,
-// none of which waits for another: every workgroup of 256 items counts the group sizes of ALL items itself (a few
-// KB of flags, coalesced, from L2) and the sizes before its own first item, so an item's place in the new frame
-//     base(group) + #(same group before the workgroup) + #(same group before it inside the workgroup)
-// needs no communication.  The re-detect branch (klt.py:207-230 -> update_features, klt.py:117-189) is not a
-// copy: when fewer than frac * _num_features features are left, items n .. n + n_det - 1 ARE the detector's
-// keypoints of the old frame (state 0, landmark NaN, track start = the keypoint, start pose np.eye(4)) -- the
-// tracker kernel read its points the same way (vo_klt_source).
-template <bool BYP>
-__global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat A, vo_feat B,
-                                                                const float* __restrict__ next_xy,
-                                                                const uint8_t* __restrict__ status,
-                                                                const float* __restrict__ err, float err_thr,
-                                                                vo_append ap, int cap) {
-  __shared__ unsigned long long s_red[2][4];
-  __shared__ int s_wcnt[3][4];
-  const int tid = threadIdx.x;
-  if (blockIdx.y != 0) {               // several sequences per launch: grid.y = sequence
-    const size_t q = blockIdx.y;
-    ctl += q;
-    A = vo_feat_seq(A, q);
-    B = vo_feat_seq(B, q);
-    next_xy += q * (size_t)cap * 2;
-    status += q * (size_t)cap;
-    err += q * (size_t)cap;
-    ap.det_kp += q * ap.det_stride;
-  }
-  // device-side gate: this flight's tracker has published its end (instead of a stream event; vo_seq_ctl)
-  if (ap.gate_klt_want) {
-    if (!vo_gate_wait(&ctl->gate_klt, ap.gate_klt_want, ap.gate_mode != 2) && tid == 0) atomicOr(&ctl->fault, (int)VO_FAULT_GATE);
-    __syncthreads();
-  }
-  if (blockIdx.x == 0 && tid == 0) {
-    ctl->ts[1] = wall_clock64();
-    ctl->ts[6] = ctl->ts[0];          // this step's tracker start (the next step's tracker overwrites ts[0] meanwhile)
-  }
-  regroup_klt_body<BYP>(ctl, A, B, next_xy, status, err, err_thr, ap, cap, s_red, s_wcnt);
-  if (ap.gate_regroup_set) {          // every workgroup arrives, whatever it did: the last one opens the tracker's gate
-    if (ap.gate_mode == 2) {
-      vo_stores_done();
-      __syncthreads();
-    } else {
-      __syncthreads();
-      __threadfence();
-    }
-    if (tid == 0) vo_gate_arrive(&ctl->gate_regroup_cnt, gridDim.x, &ctl->gate_regroup, ap.gate_regroup_set, ap.gate_mode != 2);
   }
 }
 
@@ -640,7 +597,7 @@ __global__ __launch_bounds__(256) void state_walk_landmarks_kernel(vo_seq_ctl* _
                                                                    const unsigned long long* __restrict__ best_mask, int words,
                                                                    const vo_cam* __restrict__ cams, double bearing_thr, int use_refined,
                                                                    int* __restrict__ pend, vo_step_result* __restrict__ res,
-                                                                   unsigned* __restrict__ seq_word, unsigned seq, int rec_fence) {
+                                                                   unsigned* __restrict__ seq_word, unsigned seq) {
   __shared__ int s_cnt[3];             // dropped, landmarks, candidates of this workgroup
   __shared__ int s_last;
   const int tid = threadIdx.x;
@@ -821,7 +778,7 @@ __global__ __launch_bounds__(256) void state_walk_landmarks_kernel(vo_seq_ctl* _
   if (!res) return;
   __syncthreads();                     // (the record reads the committed pose)
   write_step_record(ctl, tid, use_refined, n2, n_cand, n_dropped, n_land, atomicAdd(&ctl->ts[4], 0ull), res, seq_word, seq,
-                    rec_fence != 0);
+                    false);          // (no system-scope fences: see write_step_record)
 }
 
 }  // namespace
@@ -830,12 +787,8 @@ int vo_state_regroup_klt(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, con
                          const uint8_t* d_status, const float* d_err, float err_thr, vo_append ap, int cap, int S) {
   {
     vo_prof_scope ps(ctx, VO_K_STATE_REGROUP);
-    if (ap.gate_mode == 2 && ap.gate_klt_want != 0u)
-      vo_launch_stop(ctx, state_regroup_klt_kernel<true>, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, A, B,
-                     d_next_xy, d_status, d_err, err_thr, ap, cap);
-    else
-      vo_launch_stop(ctx, state_regroup_klt_kernel<false>, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, A, B,
-                     d_next_xy, d_status, d_err, err_thr, ap, cap);
+    vo_launch_stop(ctx, state_regroup_klt_kernel, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, A, B, d_next_xy,
+                   d_status, d_err, err_thr, ap, cap);
   }
   return vo_check_launch(ctx, "state_regroup_klt_kernel");
 }
@@ -871,11 +824,9 @@ int vo_state_walk_landmarks(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat B, const uint6
   VO_REQUIRE(ctx, d_pend != nullptr && cap <= B.pitch, "state_walk_landmarks: bad arguments");
   {
     vo_prof_scope ps(ctx, VO_K_STATE_LANDMARKS);
-    // VO_RECORD_FENCE=1: system-scope fences between the record's lines and its closing words (see write_step_record)
-    static const int rec_fence = getenv("VO_RECORD_FENCE") ? atoi(getenv("VO_RECORD_FENCE")) : 0;
     hipLaunchKernelGGL(state_walk_landmarks_kernel, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, B,
                        (const unsigned long long*)d_best_mask, words, d_cams, bearing_thr, use_refined, (int*)d_pend, m_result,
-                       m_seq, seq, rec_fence);
+                       m_seq, seq);
   }
   return vo_check_launch(ctx, "state_walk_landmarks_kernel");
 }

@@ -45,11 +45,18 @@ int vo_ensure_pinned(vo_ctx* ctx, size_t bytes) {
   return VO_OK;
 }
 
-extern "C" {
+vo_stream_cfg vo_stream_cfg_parse(const char* cus, const char* priority) {
+  vo_stream_cfg c;
+  int lo = 0, hi = -1;
+  if (cus && sscanf(cus, "%d-%d", &lo, &hi) == 2 && lo >= 0 && hi >= lo && hi < 1024) {
+    c.cu_lo = lo;
+    c.cu_hi = hi;
+  }
+  if (priority && (priority[0] == 'l' || priority[0] == 'h')) c.priority = priority[0] == 'l' ? -1 : 1;
+  return c;
+}
 
-int vo_version(void) { return 100; }
-
-int vo_create(int device, void* stream, vo_ctx** out) {
+int vo_create_stream(int device, void* stream, const vo_stream_cfg& cfg, vo_ctx** out) {
   if (!out) return VO_EINVAL;
   *out = nullptr;
   int n = 0;
@@ -65,24 +72,19 @@ int vo_create(int device, void* stream, vo_ctx** out) {
     c->stream = (hipStream_t)stream;
     c->own_stream = false;
   } else {
-    // VO_STREAM_PRIORITY (read per creation; the pipeline sets it around its side streams): "low" / "high" ask the runtime
-    // for the least / greatest priority the device offers -- work of a low-priority queue is dispatched behind that of the
-    // others when both have workgroups waiting
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    const char* pr = getenv("VO_STREAM_PRIORITY");
+    // a low-priority queue's work is dispatched behind that of the others when both have workgroups waiting
     hipError_t e;
-    // VO_STREAM_CUS="lo-hi" (read per creation, as above): the stream's kernels run on compute units lo..hi only
-    const char* cus = getenv("VO_STREAM_CUS");
-    int lo = 0, hi = -1;
-    if (cus && sscanf(cus, "%d-%d", &lo, &hi) == 2 && lo >= 0 && hi >= lo && hi < 1024) {
+    if (cfg.cu_hi >= cfg.cu_lo) {
       uint32_t mask[32] = {0};
-      for (int k = lo; k <= hi; ++k) mask[k >> 5] |= 1u << (k & 31);
-      e = hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)((hi >> 5) + 1), mask);
-    } else if (pr && (pr[0] == 'l' || pr[0] == 'h'))
-      e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, pr[0] == 'l' ? least : greatest);
-    else
+      for (int k = cfg.cu_lo; k <= cfg.cu_hi; ++k) mask[k >> 5] |= 1u << (k & 31);
+      e = hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)((cfg.cu_hi >> 5) + 1), mask);
+    } else if (cfg.priority != 0) {
+      int least = 0, greatest = 0;
+      (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+      e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, cfg.priority < 0 ? least : greatest);
+    } else {
       e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    }
     if (e != hipSuccess) {
       delete c;
       return VO_EHIP;
@@ -91,6 +93,15 @@ int vo_create(int device, void* stream, vo_ctx** out) {
   }
   *out = c;
   return VO_OK;
+}
+
+extern "C" {
+
+int vo_version(void) { return 100; }
+
+// VO_STREAM_CUS="lo-hi" / VO_STREAM_PRIORITY=low|high, read per creation: the configuration of the context's own stream
+int vo_create(int device, void* stream, vo_ctx** out) {
+  return vo_create_stream(device, stream, vo_stream_cfg_parse(getenv("VO_STREAM_CUS"), getenv("VO_STREAM_PRIORITY")), out);
 }
 
 static void free_buf(vo_buf& b) {

@@ -134,56 +134,19 @@ struct vo_cam2 {      // the two intrinsic matrices of the two-view bootstrap (b
   double K1[9], K2[9];
 };
 
-// ---- device-side gates between kernels of different streams (vo_seq_ctl's gate words; pipeline.hip) ----
-constexpr int VO_FAULT_GATE_BIT = 128;      // = VO_FAULT_GATE (vo_state.h)
-// Two forms (gate_mode).  1: the data handed over are ordinary loads and stores, the waiting side makes an acquire fence at
-// agent scope when its word is there, the arriving side a release fence before it arrives -- on this part an invalidate /
-// a write-back of the XCD's L2, per workgroup (measured: the kernels running beside the tracker's ~1000 workgroups lose
-// their cached population over and over, step 103 -> 133 us).  2: no fences at all -- the handed-over arrays themselves are
-// written and read with agent-scope accesses (vo_st_agent / vo_ld_agent: sc1, coherent across the XCDs' L2s one access at
-// a time), the arriving side only waits for its own stores to be acknowledged (s_waitcnt) before it counts itself in.
-template <class T>
-__device__ __forceinline__ T vo_ld_agent(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <class T>
-__device__ __forceinline__ void vo_st_agent(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// poll `word` until it reaches `want` (agent scope; acquire: form 1); false after ~2 s of device clock
-__device__ __forceinline__ bool vo_gate_wait(const uint32_t* word, uint32_t want, bool acquire = true) {
-  const unsigned long long t0 = wall_clock64();
-  // (relaxed polls, ONE acquire when the word is there: an acquire at agent scope invalidates the L2 of this XCD)
-  while ((int32_t)(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-    __builtin_amdgcn_s_sleep(8);
-    if (wall_clock64() - t0 > 200000000ull) return false;
-  }
-  if (acquire) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     // (the compiler keeps what follows behind the poll)
-  return true;
-}
-
-// one arrival per workgroup (call from ONE work item after the workgroup's stores and a __threadfence() -- form 2: after
-// vo_stores_done() in every wave and a barrier); the last of `total` publishes `epoch` and resets the counter
-__device__ __forceinline__ void vo_gate_arrive(uint32_t* cnt, uint32_t total, uint32_t* word, uint32_t epoch, bool fenced = true) {
-  if (fenced) {
-    const uint32_t prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev + 1u == total) {
-      __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(word, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  } else {
-    const uint32_t prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev + 1u == total) {
-      __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(word, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-// form 2: this wave's stores have been acknowledged (vmcnt / lgkmcnt / expcnt all 0), nothing moves across for the compiler
-__device__ __forceinline__ void vo_stores_done() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-}
-
 // ---- internal entry points shared between translation units (not part of the C ABI) ----
+// How a context's own stream is created.  cu_lo..cu_hi: its kernels run on those compute units only (cu_hi < cu_lo: no
+// mask); priority: -1 / +1 the least / greatest the device offers, 0 the default -- a mask wins over a priority.
+struct vo_stream_cfg {
+  int cu_lo = 0, cu_hi = -1;
+  int priority = 0;
+  bool operator==(const vo_stream_cfg& o) const { return cu_lo == o.cu_lo && cu_hi == o.cu_hi && priority == o.priority; }
+};
+// cus "lo-hi" (anything else: no mask), priority "low" / "high" (anything else: the default); either may be NULL
+vo_stream_cfg vo_stream_cfg_parse(const char* cus, const char* priority);
+// vo_create with the stream's configuration given (vo_create reads it from VO_STREAM_CUS / VO_STREAM_PRIORITY); unused when
+// `stream` is the caller's
+int vo_create_stream(int device, void* stream, const vo_stream_cfg& cfg, vo_ctx** out);
 // P3P hypotheses + inlier counts of the frame loop (p3p.hip): sample indices derived on the device from raw
 // generator outputs in a ring, population size and stream position read on the device.
 struct vo_hyp_batch {     // several sequences per launch (grid.y = sequence); the output arrays are S blocks of Hyp entries
@@ -243,15 +206,6 @@ struct vo_klt_source {
   int n_det = 0;
   unsigned long long* ts = nullptr;   // (optional) receives wall_clock64() when the kernel's first work item starts
   const int* det_go = nullptr;        // (optional, one int per sequence) 0: det_kp was not produced, nothing is appended
-  // device-side gates (vo_state.h, vo_seq_ctl): wait until *gate_wait reaches gate_want before anything is read; when
-  // all workgroups are done publish *gate_set = gate_set_to (arrivals counted in *gate_cnt).  All in the control block.
-  const uint32_t* gate_wait = nullptr;
-  uint32_t gate_want = 0;
-  uint32_t* gate_set = nullptr;
-  uint32_t* gate_cnt = nullptr;
-  uint32_t gate_set_to = 0;
-  int32_t* gate_fault = nullptr;      // receives VO_FAULT_GATE when the wait times out
-  int gate_mode = 1;                  // 1 fences, 2 agent-scope accesses to the handed-over arrays (see vo_gate_wait)
 };
 // several sequences per launch (grid.y = sequence): element strides from one sequence's block to the next
 struct vo_klt_batch {
