@@ -311,6 +311,39 @@ int vo_sift_all_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride 
                           size_t desc_stride /* rows, >= rows */, int32_t* d_n /* S */,
                           int32_t* d_over /* S, nullable: 0 ok, 1 list overflow, 2 more than `rows` keypoints */);
 
+/* ---- Harris corners with sub-pixel refinement ---------------------------------------
+ * [ref: src/vo/features/klt.py:99-112]  find_corners(use_goodFeaturesToTrack=False):
+ *   cornerHarris(img, block, ksize, k) -> dilate(3x3) -> threshold(rel * max) ->
+ *   connectedComponentsWithStats (8-connected; row 0 = background) ->
+ *   cornerSubPix(img, float32(centroids), (win_w, win_h), (-1, -1), (EPS | COUNT, max_iter, eps))
+ * on every centroid row, background included (NaN when the background is empty; it stays NaN).
+ * Labels are numbered in the order of their first 2x2 block (row-major block order), as
+ * OpenCV's block-based labelling numbers them.  ksize must be 3; block 1..31; win 1..15;
+ * max_iter 1..100 (the criteria's count, clamped as OpenCV clamps it); eps >= 0 (the
+ * criteria's epsilon; steps are compared with its square).  The image must be at least
+ * (2 win_h + 5) x (2 win_w + 5).  A refused call leaves the context usable.
+ * vo_harris_subpix_capacity(H, W) = ceil(H/2) * ceil(W/2) + 1 rows bounds the result exactly. */
+int vo_harris_subpix_capacity(int H, int W);
+/* [ref: src/vo/features/klt.py:99-112]  S images of one size, enqueued on the context's stream (no
+ * synchronisation; the image is the grid's extra dimension).  Image q at d_imgs + q * img_stride bytes;
+ * its rows (x, y float32) at d_xy + q * xy_stride * 2, its row count in d_n[q].  Stage outputs, each
+ * nullable: d_response H*W float32 and d_labels H*W int32 per image (at + q * H * W), d_centroids
+ * (x, y float64) per row (at + q * xy_stride * 2).  Image q's results are those of a call on it alone. */
+int vo_harris_subpix_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride /* bytes, >= H*W */, int S, int H,
+                               int W, int block, int ksize, double k, double rel, int win_w, int win_h, int max_iter,
+                               double eps, float* d_xy, size_t xy_stride /* rows, >= capacity */, int32_t* d_n /* S */,
+                               float* d_response, int32_t* d_labels, double* d_centroids);
+/* [ref: src/vo/features/klt.py:99-112]  The same from host memory: imgs S*H*W; image q's rows at
+ * xy + q * C * 2 (C = vo_harris_subpix_capacity(H, W)), its count in n[q]; response / labels
+ * (S*H*W) and centroids (S*C*2) are nullable. */
+int vo_harris_subpix_batch(vo_ctx* ctx, const uint8_t* imgs, int S, int H, int W, int block, int ksize, double k,
+                           double rel, int win_w, int win_h, int max_iter, double eps, float* xy, int32_t* n,
+                           float* response, int32_t* labels, double* centroids);
+/* [ref: src/vo/features/klt.py:99-112]  One image: vo_harris_subpix_batch with S = 1. */
+int vo_harris_subpix_corners(vo_ctx* ctx, const uint8_t* img, int H, int W, int block, int ksize, double k, double rel,
+                             int win_w, int win_h, int max_iter, double eps, float* xy, int32_t* n, float* response,
+                             int32_t* labels, double* centroids);
+
 /* ---- RANSAC control (host-side, bit-compatible with the reference) --------------
  * [ref: src/vo/algorithms/ransac.py:52, 92-94]  the sample stream of
  *   np.random.default_rng(2023).choice(np.arange(pop), replace=False, size=s)

@@ -145,6 +145,11 @@ _SIGS = {
     "vo_sift_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
     "vo_sift_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "vo_sift_all_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "vo_harris_subpix_capacity": (_i, [_i, _i]),
+    "vo_harris_subpix_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _i, _d, _d, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp,
+                                        _vp]),
+    "vo_harris_subpix_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _d, _d, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "vo_harris_subpix_corners": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "vo_fundamental_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
     "vo_fundamental_fit": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "vo_essential_decompose": (_i, [_vp, _vp, _vp]),
@@ -445,6 +450,76 @@ class Context:
         out = np.empty((H, W), np.float32)
         self._chk(self._lib.vo_min_eigen_map(self._h, _ptr(img), H, W, int(block_size), _ptr(out)))
         return out
+
+    # ---- Harris + sub-pixel refinement (klt.py:99-112) ----
+    @staticmethod
+    def _subpix_criteria(criteria):
+        """(type, count, epsilon) -> (max_iter, eps) as cornerSubPix resolves them: without COUNT 100 iterations,
+        without EPS no epsilon; the count is clamped to 1..100."""
+        kind, count, epsilon = criteria
+        max_iter = min(max(int(count), 1), 100) if kind & 1 else 100
+        eps = max(float(epsilon), 0.0) if kind & 2 else 0.0
+        return max_iter, eps
+
+    def harris_subpix_corners(self, img, block_size=2, ksize=3, k=0.04, rel_threshold=0.01, win=(5, 5),
+                              criteria=(3, 100, 0.001), stages=False):
+        """cornerHarris -> dilate -> threshold -> connected-component centroids -> cornerSubPix on the device
+        (vo_harris_subpix_corners): (n, 2) float32 corners, row 0 the background's.  stages=True also returns a dict of
+        the stage outputs: response (H, W) float32, labels (H, W) int32, centroids (n, 2) float64."""
+        img = _c(img, np.uint8)
+        if img.ndim != 2:
+            raise ValueError("harris_subpix_corners: img must be 2-D, got shape %s" % (img.shape,))
+        H, W = img.shape
+        max_iter, eps = self._subpix_criteria(criteria)
+        cap = self._lib.vo_harris_subpix_capacity(H, W)
+        xy = np.empty((cap, 2), np.float32)
+        n = C.c_int32(0)
+        resp = np.empty((H, W), np.float32) if stages else None
+        labels = np.empty((H, W), np.int32) if stages else None
+        cen = np.empty((cap, 2), np.float64) if stages else None
+        self._chk(self._lib.vo_harris_subpix_corners(self._h, _ptr(img), H, W, int(block_size), int(ksize), float(k),
+                                                     float(rel_threshold), int(win[0]), int(win[1]), max_iter, eps,
+                                                     _ptr(xy), C.byref(n), _ptr(resp), _ptr(labels), _ptr(cen)))
+        pts = xy[: n.value].copy()
+        return (pts, dict(response=resp, labels=labels, centroids=cen[: n.value].copy())) if stages else pts
+
+    def harris_subpix_corners_batch(self, images, block_size=2, ksize=3, k=0.04, rel_threshold=0.01, win=(5, 5),
+                                    criteria=(3, 100, 0.001), stages=False):
+        """harris_subpix_corners on S images of one size in one set of launches (vo_harris_subpix_batch): `images` is an
+        (S, H, W) uint8 array or a list of equal-shape 2-D arrays.  Returns a list of S results, each what
+        harris_subpix_corners(image, ...) returns."""
+        shapes = {np.shape(a) for a in images}
+        if len(shapes) != 1 or len(next(iter(shapes))) != 2:
+            raise ValueError("harris_subpix_corners_batch: images must be 2-D and of one shape, got %s" % sorted(shapes))
+        imgs = _c(np.stack([np.asarray(a) for a in images]), np.uint8)
+        S, H, W = imgs.shape
+        max_iter, eps = self._subpix_criteria(criteria)
+        cap = self._lib.vo_harris_subpix_capacity(H, W)
+        xy = np.empty((S, cap, 2), np.float32)
+        n = np.zeros(S, np.int32)
+        resp = np.empty((S, H, W), np.float32) if stages else None
+        labels = np.empty((S, H, W), np.int32) if stages else None
+        cen = np.empty((S, cap, 2), np.float64) if stages else None
+        self._chk(self._lib.vo_harris_subpix_batch(self._h, _ptr(imgs), S, H, W, int(block_size), int(ksize), float(k),
+                                                   float(rel_threshold), int(win[0]), int(win[1]), max_iter, eps,
+                                                   _ptr(xy), _ptr(n), _ptr(resp), _ptr(labels), _ptr(cen)))
+        if not stages:
+            return [xy[q, : n[q]].copy() for q in range(S)]
+        return [(xy[q, : n[q]].copy(), dict(response=resp[q], labels=labels[q], centroids=cen[q, : n[q]].copy()))
+                for q in range(S)]
+
+    def harris_subpix_capacity(self, H, W):
+        return self._lib.vo_harris_subpix_capacity(int(H), int(W))
+
+    def harris_subpix_batch_dev(self, d_imgs, img_stride, S, H, W, d_xy, xy_stride, d_n, block_size=2, ksize=3, k=0.04,
+                                rel_threshold=0.01, win=(5, 5), criteria=(3, 100, 0.001), d_response=None, d_labels=None,
+                                d_centroids=None):
+        """vo_harris_subpix_batch_dev: enqueued on the context's stream; the stage outputs may be None."""
+        max_iter, eps = self._subpix_criteria(criteria)
+        self._chk(self._lib.vo_harris_subpix_batch_dev(
+            self._h, C.c_void_p(d_imgs), int(img_stride), int(S), int(H), int(W), int(block_size), int(ksize), float(k),
+            float(rel_threshold), int(win[0]), int(win[1]), max_iter, eps, C.c_void_p(d_xy), int(xy_stride),
+            C.c_void_p(d_n), C.c_void_p(d_response), C.c_void_p(d_labels), C.c_void_p(d_centroids)))
 
     # ---- KLT ----
     def klt_num_levels(self, H, W, win, max_level):

@@ -1,6 +1,7 @@
 """Shi-Tomasi corners + pyramidal Lucas-Kanade tracking (reference: src/vo/features/klt.py).
 Corner map / candidates and the tracker are HIP kernels (vo_good_features,
-vo_klt_track); the bookkeeping around them follows the reference."""
+vo_klt_track, and vo_harris_subpix_corners for the Harris + sub-pixel branch);
+the bookkeeping around them follows the reference."""
 import sys
 
 import numpy as np
@@ -30,6 +31,11 @@ class KLTTracker:
     # HarrisCornerDetector.extractKeypoints (harris.py:86-158) with _harris_params.
     _detector = "shi-tomasi"
     _harris_params = dict(patch_size=9, kappa=0.09, num_keypoints=2000, nonmaximum_supression_radius=5)
+    # Harris corners with sub-pixel refinement, the use_goodFeaturesToTrack=False branch: the reference's literals
+    # (klt.py:100-110): cornerHarris(img, 2, 3, 0.04), threshold 0.01 * max, cornerSubPix window (5, 5) and criteria
+    # (EPS + MAX_ITER, 100, 0.001)
+    _harris_subpix_params = dict(block_size=2, ksize=3, k=0.04, rel_threshold=0.01, win=(5, 5),
+                                 criteria=(TERM_CRITERIA_EPS | TERM_CRITERIA_COUNT, 100, 0.001))
 
     def __init__(self, frame, context=None):
         self._ctx = context
@@ -77,9 +83,10 @@ class KLTTracker:
     def find_corners(self, frame: Frame, mask=None, use_goodFeaturesToTrack=True) -> np.ndarray:
         """(n, 2, 1) float32 corners (klt.py:87-115)."""
         if not use_goodFeaturesToTrack:
-            raise NotImplementedError("the cornerHarris + cornerSubPix branch (klt.py:99-110) is not on the "
-                                      "front-end path and is not provided")
-        if self._detector == "harris":
+            # klt.py:99-112: Harris map, dilate, threshold, component centroids (background row included), cornerSubPix;
+            # the mask plays no part, as in the reference
+            pts = self._context().harris_subpix_corners(_gray(frame.image), **self._harris_subpix_params)
+        elif self._detector == "harris":
             h = self._harris_params
             pts = self._context().harris_keypoints(_gray(frame.image), h["patch_size"], h["kappa"], h["num_keypoints"],
                                                    h["nonmaximum_supression_radius"]).astype(np.float32)
