@@ -395,7 +395,8 @@ int vo_ransac_replay(vo_ransac_state* st, const uint8_t* valid, const int32_t* c
  *                 track; update_with_world_landmarks + _check_landmarks [ref: state.py:69-107]
  * No stage waits for the host: a step is a chain of launches, its result a record the last
  * kernel writes to host-visible memory.  The two-view bootstrap [ref: main.py:204-230] runs on
- * the host (vo/driver.py) and hands its Features / poses over with vo_pipeline_set_state.      */
+ * the host (vo/driver.py) and hands its Features / poses over with vo_pipeline_set_state, or inside
+ * the pipeline from two stored frames (vo_pipeline_bootstrap_seq).                              */
 typedef struct vo_pipeline vo_pipeline;
 typedef struct vo_pipeline_config {
   int32_t H, W, n_frames;        /* n_frames: frame store in HBM (vo_pipeline_set_frame slots)   */
@@ -640,6 +641,61 @@ int vo_pipeline_restart_seq(vo_pipeline* p, int seq, int idx, int n, const doubl
                             const double* landmarks, const double* tracks, const double* poses,
                             const double* T_wc, const double* T_cw, const double* T_wc_prev,
                             const double* T_cw_prev, int num_features, const vo_pcg64* rng);
+
+/* ---- two-view bootstrap inside the pipeline ------------------------------------------------------------------
+ * A sequence enters the pipeline from two frames of its frame store instead of from finished Features arrays: what
+ * vo.driver.bootstrap computes on the host [ref: src/main.py:204-230] for frames idx_a, idx_b of sequence seq, followed by
+ * the hand-over vo_pipeline_set_state_seq / vo_pipeline_restart_seq make with its result.  KLT tracker mode.
+ *   1. Shi-Tomasi corners of frame a (vo_good_features' kernels) [ref: src/vo/features/klt.py:24-26, 98];
+ *      num_features = their count [ref: klt.py:114];
+ *   2. pyramids of a and b with the bootstrap's own window / level count, LK a -> b, keep status & err <
+ *      klt_err_threshold [ref: klt.py:233-262]; the identity-pair Matches regroup of fresh Features keeps the survivors
+ *      in order, all in state 1, tracks starting at the frame-a corner with start pose identity
+ *      [ref: src/vo/primitives/matches.py:26-212];
+ *   3. 8-point RANSAC over the survivors (vo_fundamental_hypotheses' kernels: per-sample Hartley frame, squared pixel
+ *      distance to the epipolar lines in both images, a fresh generator default_rng(2023) [ref: src/vo/algorithms/
+ *      ransac.py:52], closing fit over all inliers), then vo_relative_pose's kernel
+ *      [ref: src/vo/landmarks/triangulation.py:110-163, 279-350];
+ *   4. update_with_local_pose, update_with_local_landmarks (with _check_landmarks against both cameras), reset_outliers
+ *      [ref: src/vo/primitives/state.py:24-67, 90-107, 162-172], written into the lane's current Features block and its
+ *      control block (T_cw = M, T_wc its closed-form inverse, previous pose = identity): a feature ends in state 2 with
+ *      its landmark, its track start at the frame-a corner and start pose identity, or in state 0 with track start = its
+ *      own keypoint and start pose = the current pose; none is left in state 1;
+ *   5. on a pipeline that is not running yet what vo_pipeline_set_state_seq does (idx_b under its rules for idx; the
+ *      RANSAC object fresh on the lane's first hand-over; the generator stays as seeded unless rng is given); on a
+ *      running pipeline what vo_pipeline_restart_seq does (idx_b must be the `prev` of the next submit; fresh RANSAC
+ *      object; the lane's generator from *rng, NULL: the state of the last vo_pipeline_seed; lane active; a prepared
+ *      pyramid dropped; this lane's pyramid + detection of frame b made for it alone; other lanes untouched).
+ * idx_a is any other slot.  Nothing may be in flight.  The call is synchronous.
+ * No array sized by pixels or by features crosses between host and device: what crosses is counted in bytes_h2d /
+ * bytes_d2h -- per RANSAC batch of 2048 samples 64 KiB up (the samples, drawn on the host from the reference's generator)
+ * and 8 KiB down (the inlier counts the sequential accept / adapt rule, vo_ransac_replay, walks), plus scalars.
+ * Failures are status codes: VO_ETRACKING for fewer than 8 corners or survivors or a RANSAC without a model of 8 inliers,
+ * VO_ECAPACITY for candidate lists or a corner count beyond the feature capacity.  Until step 4 only workspace is
+ * written, so A FAILED CALL LEAVES THE LANE AS IT WAS before it: Features, control block, generator, activity.
+ * (route: reserved for the reference's own RANSAC route -- population normalised once, algebraic error -- must be 0.) */
+typedef struct vo_bootstrap_params {      /* 0 in a field = the default named here */
+  int32_t max_corners;                    /* Shi-Tomasi corners on frame a; 0 = cfg.n_keypoints [ref: klt.py:24-26] */
+  double  quality, min_distance;          /* 0.01, 8                                             */
+  int32_t block;                          /* 7                                                   */
+  int32_t klt_win, klt_max_level;         /* tracker a -> b; 0 / -1 = the pipeline's own         */
+  double  threshold_px;                   /* epipolar distance, 0 = 0.25 [ref: src/main.py:185-193] */
+  double  outlier_ratio, confidence;      /* 0.9, 0.999                                          */
+  int32_t max_iterations;                 /* 0 = 2000                                            */
+  int32_t route;                          /* 0                                                   */
+} vo_bootstrap_params;
+typedef struct vo_bootstrap_result {
+  int32_t n_corners, n_tracked, n_ransac_inliers, n_landmarks, n_features;
+  int32_t reserved;
+  int64_t ransac_iterations;
+  double  M[12];                          /* camera a -> camera b, 3x4 row-major, |t| = 1        */
+  int64_t bytes_h2d, bytes_d2h;           /* what the call copied between host and device        */
+} vo_bootstrap_result;
+int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, const vo_bootstrap_params* prm /* NULL: defaults */,
+                              const vo_pcg64* rng, vo_bootstrap_result* out);
+int vo_pipeline_bootstrap(vo_pipeline* p, int idx_a, int idx_b, const vo_bootstrap_params* prm, vo_bootstrap_result* out);
+/* the generator the bootstrap's RANSAC starts from: np.random.default_rng(2023)'s PCG64 state */
+void vo_bootstrap_default_rng(vo_pcg64* rng);
 
 /* ---- shared map over RCCL ------------------------------------------------------------------
  * The reference is one process and one thread (README.md:49); frame streams shard at sequence granularity (one

@@ -1,0 +1,130 @@
+"""What a change of recording costs a lane ("restart bubble"): the two-view bootstrap of a recording's frames
+0 and 2 at the configuration frame size (1376 x 1241, 2000 corners, bench.py's bootstrap settings 21x21 / max level 3 /
+1 px) on a running one-sequence pipeline, by the two routes, alternating in one process:
+
+  host    vo.driver._device_bootstrap (the drop-in classes: one ABI call per stage, images and points uploaded and results
+          brought back around each, NumPy bookkeeping in between) + Pipeline.restart with the frame's image
+  device  lane idle, the two frames into two slots, Pipeline.bootstrap (vo_pipeline_bootstrap_seq)
+
+Both end in a synchronise (the lane's pyramid + detection are waited for); the host clock is read around them.  The frames
+are rendered before anything is timed.  --repeats calls of each route per recording, warm-up first; medians and spread.
+
+    python3 tools/dev/pipeline_bootstrap.py [--recordings 2] [--repeats 20] [--json OUT]
+    python3 tools/dev/pipeline_bootstrap.py --trace 20      # the device route only, untimed: for rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for p in (ROOT, os.path.join(ROOT, "visual-odometry-project_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+H, W, N, WIN, LEVEL, THR = 1241, 1376, 2000, 21, 3, 1.0
+
+
+class Recording:
+    """Frames 0..3 of a synthetic recording, rendered once; iterates like vo.primitives.Sequence as often as asked."""
+
+    def __init__(self, seed):
+        from vo.primitives import Sequence
+        self.seq = Sequence("synthetic", n_frames=4, height=H, width=W, seed=seed)
+        self.frames = [next(self.seq).image for _ in range(4)]
+        self.i = 0
+
+    def rewind(self):
+        self.i = 0
+        return self
+
+    def get_camera(self):
+        return self.seq.get_camera()
+
+    def __next__(self):
+        from vo.primitives import Frame
+        self.i += 1
+        return Frame(self.frames[self.i - 1].copy(), sensor=self.seq.get_camera())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--recordings", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--trace", type=int, default=0)
+    a = ap.parse_args()
+    import numpy as np
+    from vo import _native, driver
+    ctx = _native.Context(0)
+    recs = [Recording(2023 + 7 * r) for r in range(max(1, a.recordings))]
+    K = np.asarray(recs[0].get_camera().intrinsic_matrix, np.float64)
+    pipe = _native.Pipeline(ctx, H, W, 4, K, **driver._pipeline_kwargs(None, N, 17, 2, 4000, "current"))
+    boot = driver._bootstrap_kwargs(N, 17, 2, WIN, LEVEL, THR)
+    # a running pipeline: bootstrapped once and stepped once, so that every later bootstrap is a lane's change of recording
+    pipe.set_frame(1, recs[0].frames[0])
+    pipe.set_frame(0, recs[0].frames[2])
+    first = pipe.bootstrap(1, 0, **boot)
+    pipe.set_frame(1, recs[0].frames[3])
+    pipe.step(0, 1)
+    slot, other = 1, 2
+
+    def device(rec):
+        pipe.set_active(0, False)
+        pipe.set_frame(other, rec.frames[0])
+        pipe.set_frame(slot, rec.frames[2])
+        return pipe.bootstrap(other, slot, **boot)
+
+    def host(rec):
+        state, tracker = driver._device_bootstrap(rec.rewind(), N, 17, 2, WIN, LEVEL, THR)
+        f = state.curr_frame
+        pipe.restart(0, slot, f.features, state.curr_pose, state.prev_pose, num_features=tracker._tracker._num_features,
+                     image=f.image)
+        return state
+
+    if a.trace:
+        for k in range(a.trace):
+            device(recs[k % len(recs)])
+        print("bootstraps", a.trace)
+        pipe.close()
+        ctx.close()
+        return
+    for rec in recs:                      # warm-up: workspaces, code objects, the pinned staging buffers
+        for _ in range(2):
+            host(rec)
+            device(rec)
+    t = dict(host=[], device=[])
+    res = None
+    for _ in range(a.repeats):
+        for rec in recs:
+            for name, fn in (("host", host), ("device", device)):
+                ctx.sync()
+                t0 = time.perf_counter()
+                r = fn(rec)
+                t[name].append(time.perf_counter() - t0)
+                if name == "device":
+                    res = r
+    out = dict(H=H, W=W, corners=N, recordings=len(recs), repeats=a.repeats, first=dict(
+        n_corners=first.n_corners, n_tracked=first.n_tracked, n_landmarks=first.n_landmarks))
+    for name, ts in t.items():
+        ts = sorted(ts)
+        q = statistics.quantiles(ts, n=10)
+        out[name] = dict(median_ms=statistics.median(ts) * 1e3, min_ms=ts[0] * 1e3, max_ms=ts[-1] * 1e3, p10_ms=q[0] * 1e3,
+                         p90_ms=q[-1] * 1e3, calls=len(ts))
+        print("%-6s median %8.3f ms   p10 %8.3f  p90 %8.3f   min %8.3f  max %8.3f   (%d calls)" % (
+            name, out[name]["median_ms"], out[name]["p10_ms"], out[name]["p90_ms"], out[name]["min_ms"], out[name]["max_ms"],
+            len(ts)), flush=True)
+    out["bytes_h2d"], out["bytes_d2h"] = int(res.bytes_h2d), int(res.bytes_d2h)
+    print("device route: %d bytes up, %d bytes down per call; host / device = %.2f" % (
+        res.bytes_h2d, res.bytes_d2h, out["host"]["median_ms"] / out["device"]["median_ms"]))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+    pipe.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

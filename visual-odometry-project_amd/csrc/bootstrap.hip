@@ -551,6 +551,59 @@ __global__ __launch_bounds__(256) void relative_pose_kernel(const double* __rest
 
 }  // namespace
 
+// ---- device-resident forms (vo_internal.h): points, masks and results in HBM; the host-pointer entry points below upload,
+// call these and download ----
+
+int vo_fundamental_hypotheses_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const int32_t* samples, int Hyp,
+                                  int normalize_samples, int error_kind, double threshold, int32_t* d_samples, double* d_F,
+                                  int32_t* d_counts, uint64_t* d_masks, int32_t* counts) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, d_p1 && d_p2 && samples && d_samples && d_F && d_counts && counts, "fundamental_hypotheses: null pointer");
+  VO_REQUIRE(ctx, N >= 8 && Hyp >= 1 && Hyp <= (1 << 20), "fundamental_hypotheses: need N >= 8, 1 <= Hyp <= 2^20");
+  VO_REQUIRE(ctx, error_kind == 0 || error_kind == 1, "fundamental_hypotheses: error_kind must be 0 or 1");
+  for (size_t k = 0; k < (size_t)8 * Hyp; ++k)
+    VO_REQUIRE(ctx, samples[k] >= 0 && samples[k] < N, "fundamental_hypotheses: sample index %d out of range", (int)samples[k]);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int words = vo_cdiv(N, 64);
+  hipStream_t st = ctx->stream;
+  VO_HIP_TRY(ctx, hipMemcpyAsync(d_samples, samples, (size_t)Hyp * 32, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(f8_hyp_kernel, dim3(vo_cdiv(Hyp, HB)), dim3(HB), 0, st, d_p1, d_p2, N, (const int*)d_samples, Hyp,
+                     normalize_samples, d_F);
+  VO_TRY(vo_check_launch(ctx, "f8_hyp_kernel"));
+  hipLaunchKernelGGL(f_score_kernel, dim3(Hyp), dim3(256), 0, st, d_p1, d_p2, N, (const double*)d_F, error_kind, threshold,
+                     (int*)d_counts, (unsigned long long*)d_masks, words);
+  VO_TRY(vo_check_launch(ctx, "f_score_kernel"));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, (size_t)Hyp * 4, hipMemcpyDeviceToHost, st));
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  ctx->bytes_h2d += (int64_t)Hyp * 32;
+  ctx->bytes_d2h += (int64_t)Hyp * 4;
+  return VO_OK;
+}
+
+int vo_fundamental_fit_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const uint8_t* d_mask, int normalize,
+                           double* d_F, int32_t* d_n_used) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, d_p1 && d_p2 && d_F, "fundamental_fit: null pointer");
+  VO_REQUIRE(ctx, N >= 8, "fundamental_fit: the 8-point algorithm needs 8 correspondences");
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(f8_fit_kernel, dim3(1), dim3(256), 0, ctx->stream, d_p1, d_p2, N, d_mask, normalize, d_F, (int*)d_n_used);
+  return vo_check_launch(ctx, "f8_fit_kernel");
+}
+
+int vo_relative_pose_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, int N, const uint8_t* d_inliers, const double* K1,
+                         const double* K2, const double* d_F, double* d_M, double* d_X, uint8_t* d_mask_out, double* d_M4) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, d_x1 && d_x2 && K1 && K2 && d_F && d_M && d_X, "relative_pose: null pointer");
+  VO_REQUIRE(ctx, N >= 1, "relative_pose: no correspondences");
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  vo_cam2 cams;
+  memcpy(cams.K1, K1, 72);
+  memcpy(cams.K2, K2, 72);
+  hipLaunchKernelGGL(relative_pose_kernel, dim3(1), dim3(256), 0, ctx->stream, d_x1, d_x2, N, d_inliers, d_F, cams, d_M, d_X,
+                     d_mask_out, d_M4);
+  return vo_check_launch(ctx, "relative_pose_kernel");
+}
+
 extern "C" {
 
 int vo_fundamental_hypotheses(vo_ctx* ctx, const double* p1, const double* p2, int N, const int32_t* samples, int Hyp,
@@ -559,9 +612,6 @@ int vo_fundamental_hypotheses(vo_ctx* ctx, const double* p1, const double* p2, i
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, p1 && p2 && samples && F && counts, "fundamental_hypotheses: null pointer");
   VO_REQUIRE(ctx, N >= 8 && Hyp >= 1 && Hyp <= (1 << 20), "fundamental_hypotheses: need N >= 8, 1 <= Hyp <= 2^20");
-  VO_REQUIRE(ctx, error_kind == 0 || error_kind == 1, "fundamental_hypotheses: error_kind must be 0 or 1");
-  for (size_t k = 0; k < (size_t)8 * Hyp; ++k)
-    VO_REQUIRE(ctx, samples[k] >= 0 && samples[k] < N, "fundamental_hypotheses: sample index %d out of range", (int)samples[k]);
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int words = vo_cdiv(N, 64);
   vo_buf* s = ctx->scratch;
@@ -574,16 +624,10 @@ int vo_fundamental_hypotheses(vo_ctx* ctx, const double* p1, const double* p2, i
   hipStream_t st = ctx->stream;
   VO_HIP_TRY(ctx, hipMemcpyAsync(s[0].p, p1, (size_t)N * 16, hipMemcpyHostToDevice, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(s[1].p, p2, (size_t)N * 16, hipMemcpyHostToDevice, st));
-  VO_HIP_TRY(ctx, hipMemcpyAsync(s[2].p, samples, (size_t)Hyp * 32, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(f8_hyp_kernel, dim3(vo_cdiv(Hyp, HB)), dim3(HB), 0, st, (const double*)s[0].p, (const double*)s[1].p, N,
-                     (const int*)s[2].p, Hyp, normalize_samples, (double*)s[3].p);
-  VO_TRY(vo_check_launch(ctx, "f8_hyp_kernel"));
-  hipLaunchKernelGGL(f_score_kernel, dim3(Hyp), dim3(256), 0, st, (const double*)s[0].p, (const double*)s[1].p, N,
-                     (const double*)s[3].p, error_kind, threshold, (int*)s[4].p,
-                     masks ? (unsigned long long*)s[5].p : nullptr, words);
-  VO_TRY(vo_check_launch(ctx, "f_score_kernel"));
+  VO_TRY(vo_fundamental_hypotheses_dev(ctx, (const double*)s[0].p, (const double*)s[1].p, N, samples, Hyp, normalize_samples,
+                                       error_kind, threshold, (int32_t*)s[2].p, (double*)s[3].p, (int32_t*)s[4].p,
+                                       masks ? (uint64_t*)s[5].p : nullptr, counts));
   VO_HIP_TRY(ctx, hipMemcpyAsync(F, s[3].p, (size_t)Hyp * 72, hipMemcpyDeviceToHost, st));
-  VO_HIP_TRY(ctx, hipMemcpyAsync(counts, s[4].p, (size_t)Hyp * 4, hipMemcpyDeviceToHost, st));
   if (masks) VO_HIP_TRY(ctx, hipMemcpyAsync(masks, s[5].p, (size_t)Hyp * words * 8, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   return VO_OK;
@@ -609,9 +653,8 @@ int vo_fundamental_fit(vo_ctx* ctx, const double* p1, const double* p2, int N, c
   VO_HIP_TRY(ctx, hipMemcpyAsync(s[0].p, p1, (size_t)N * 16, hipMemcpyHostToDevice, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(s[1].p, p2, (size_t)N * 16, hipMemcpyHostToDevice, st));
   if (mask) VO_HIP_TRY(ctx, hipMemcpyAsync(s[2].p, mask, (size_t)N, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(f8_fit_kernel, dim3(1), dim3(256), 0, st, (const double*)s[0].p, (const double*)s[1].p, N,
-                     mask ? (const uint8_t*)s[2].p : nullptr, normalize, (double*)s[3].p, (int*)nullptr);
-  VO_TRY(vo_check_launch(ctx, "f8_fit_kernel"));
+  VO_TRY(vo_fundamental_fit_dev(ctx, (const double*)s[0].p, (const double*)s[1].p, N, mask ? (const uint8_t*)s[2].p : nullptr,
+                                normalize, (double*)s[3].p, nullptr));
   VO_HIP_TRY(ctx, hipMemcpyAsync(F, s[3].p, 72, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   return VO_OK;
@@ -651,13 +694,8 @@ int vo_relative_pose(vo_ctx* ctx, const double* x1, const double* x2, int N, con
   if (inliers) VO_HIP_TRY(ctx, hipMemcpyAsync(s[2].p, inliers, (size_t)N, hipMemcpyHostToDevice, st));
   double* dF = (double*)s[3].p;
   VO_HIP_TRY(ctx, hipMemcpyAsync(dF, F, 72, hipMemcpyHostToDevice, st));
-  vo_cam2 cams;
-  memcpy(cams.K1, K1, 72);
-  memcpy(cams.K2, K2, 72);
-  hipLaunchKernelGGL(relative_pose_kernel, dim3(1), dim3(256), 0, st, (const double*)s[0].p, (const double*)s[1].p, N,
-                     inliers ? (const uint8_t*)s[2].p : nullptr, (const double*)dF, cams, dF + 16, (double*)s[4].p,
-                     (uint8_t*)s[5].p, dF + 32);
-  VO_TRY(vo_check_launch(ctx, "relative_pose_kernel"));
+  VO_TRY(vo_relative_pose_dev(ctx, (const double*)s[0].p, (const double*)s[1].p, N, inliers ? (const uint8_t*)s[2].p : nullptr,
+                              K1, K2, dF, dF + 16, (double*)s[4].p, (uint8_t*)s[5].p, dF + 32));
   VO_HIP_TRY(ctx, hipMemcpyAsync(M, dF + 16, 96, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(X, s[4].p, (size_t)N * 24, hipMemcpyDeviceToHost, st));
   if (mask_out) VO_HIP_TRY(ctx, hipMemcpyAsync(mask_out, s[5].p, (size_t)N, hipMemcpyDeviceToHost, st));

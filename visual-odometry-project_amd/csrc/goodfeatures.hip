@@ -489,13 +489,19 @@ int vo_min_eigen_map(vo_ctx* ctx, const uint8_t* img, int H, int W, int block, f
   return VO_OK;
 }
 
-int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_t* mask, int max_corners,
-                     double quality, double min_dist, int block, float* xy, int32_t* n_out) {
+}  // extern "C"
+
+// The device-resident form (vo_internal.h): image and mask are in HBM already, the corners stay there (*d_xy_out points
+// into the context's workspace and holds until the context's next call).  Only the counts the launches are sized by come
+// back to the host (vo_ctx::bytes_d2h).
+int vo_good_features_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const uint8_t* d_mask, int max_corners,
+                         double quality, double min_dist, int block, const float** d_xy_out, int32_t* n_out) {
   if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, img && xy && n_out && H > 0 && W > 0, "good_features: bad arguments");
+  VO_REQUIRE(ctx, d_img && d_xy_out && n_out && H > 0 && W > 0, "good_features: bad arguments");
   VO_REQUIRE(ctx, block >= 1 && block <= 31, "good_features: blockSize must be in 1..31");
   VO_REQUIRE(ctx, quality > 0 && min_dist >= 0, "good_features: bad quality / minDistance");
   *n_out = 0;
+  *d_xy_out = nullptr;
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t px = (size_t)H * W;
   hipStream_t st = ctx->stream;
@@ -509,7 +515,6 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
   size_t sort_tmp = 0;
   VO_HIP_TRY(ctx, rocprim::radix_sort_keys_desc(nullptr, sort_tmp, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                                 (size_t)cap, 0, 64, st));
-  VO_TRY(vo_ensure(ctx, ctx->img, px));
   VO_TRY(vo_ensure(ctx, s[0], px * 4));
   VO_TRY(vo_ensure(ctx, s[1], (size_t)GC_WORDS * 4));
   VO_TRY(vo_ensure(ctx, s[2], (size_t)cap * 8));
@@ -518,17 +523,13 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
   VO_TRY(vo_ensure(ctx, s[5], cells * 4));
   VO_TRY(vo_ensure(ctx, s[6], cells * GRID_SLOTS * 4));
   VO_TRY(vo_ensure(ctx, s[7], out_cap * 8));
-  if (mask) VO_TRY(vo_ensure(ctx, ctx->img2, px));
-  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, img, px, hipMemcpyHostToDevice, st));
-  if (mask) VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img2.p, mask, px, hipMemcpyHostToDevice, st));
   VO_HIP_TRY(ctx, hipMemsetAsync(s[1].p, 0, (size_t)GC_WORDS * 4, st));
   VO_HIP_TRY(ctx, hipMemsetAsync(s[5].p, 0, cells * 4, st));
-  const uint8_t* d_mask = mask ? (const uint8_t*)ctx->img2.p : nullptr;
   unsigned* d_ctl = (unsigned*)s[1].p;                            // [0] max key, [1] candidate count, [2] corners, [3] fault
   const double scale = 1.0 / (4.0 * block * 255.0);
   const int RW = GX + block - 1, RH = GY + block - 1;
   const size_t lds = ((size_t)RW * RH + (size_t)3 * RH * GX) * 4;
-  hipLaunchKernelGGL(min_eig_kernel, dim3(vo_cdiv(W, GX), vo_cdiv(H, GY)), dim3(GT), lds, st, (const uint8_t*)ctx->img.p,
+  hipLaunchKernelGGL(min_eig_kernel, dim3(vo_cdiv(W, GX), vo_cdiv(H, GY)), dim3(GT), lds, st, d_img,
                      H, W, block, (float)(scale * scale), d_mask, (float*)s[0].p, d_ctl);
   VO_TRY(vo_check_launch(ctx, "min_eig_kernel"));
   hipLaunchKernelGGL(corner_candidates_kernel, dim3(vo_cdiv(W, GX), vo_cdiv(H, GY)), dim3(GT), 0, st,
@@ -537,6 +538,7 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
   unsigned ctl[4] = {0, 0, 0, 0};
   VO_HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 8, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));                      // (the sort is sized by the candidate count)
+  ctx->bytes_d2h += 8;
   if (ctl[1] > cap)      // (ties count as maxima: plateaus can exceed one maximum per 2x2 block)
     return vo_set_error(ctx, VO_ECAPACITY, "good_features: %u local maxima exceed the candidate capacity %u", ctl[1], cap);
   const unsigned nc = ctl[1];
@@ -558,6 +560,7 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
       VO_TRY(vo_check_launch(ctx, "greedy_distance_rounds_kernel"));
       VO_HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, st));
       VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+      ctx->bytes_d2h += 16;
       done = ctl[3] == 0;
       if (!done) {                     // a crowded cell: the walk decides (its grid holds accepted corners only)
         VO_HIP_TRY(ctx, hipMemsetAsync(s[5].p, 0, cells * 4, st));
@@ -570,6 +573,7 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
       VO_TRY(vo_check_launch(ctx, "greedy_distance_kernel"));
       VO_HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, st));
       VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+      ctx->bytes_d2h += 16;
       if (ctl[3]) return vo_set_error(ctx, VO_ECAPACITY, "good_features: more than %d corners in one grid cell", GRID_SLOTS);
     }
     n = (int)ctl[2];
@@ -578,6 +582,29 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
     hipLaunchKernelGGL(take_sorted_kernel, dim3(vo_cdiv(n, 256)), dim3(256), 0, st, d_sorted, (unsigned)n, W, d_xy);
     VO_TRY(vo_check_launch(ctx, "take_sorted_kernel"));
   }
+  *d_xy_out = d_xy;
+  *n_out = n;
+  return VO_OK;
+}
+
+extern "C" {
+
+int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_t* mask, int max_corners,
+                     double quality, double min_dist, int block, float* xy, int32_t* n_out) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, img && xy && n_out && H > 0 && W > 0, "good_features: bad arguments");
+  *n_out = 0;
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t px = (size_t)H * W;
+  hipStream_t st = ctx->stream;
+  VO_TRY(vo_ensure(ctx, ctx->img, px));
+  if (mask) VO_TRY(vo_ensure(ctx, ctx->img2, px));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, img, px, hipMemcpyHostToDevice, st));
+  if (mask) VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img2.p, mask, px, hipMemcpyHostToDevice, st));
+  const float* d_xy = nullptr;
+  int32_t n = 0;
+  VO_TRY(vo_good_features_dev(ctx, (const uint8_t*)ctx->img.p, H, W, mask ? (const uint8_t*)ctx->img2.p : nullptr, max_corners,
+                              quality, min_dist, block, &d_xy, &n));
   if (n > 0) {
     VO_HIP_TRY(ctx, hipMemcpyAsync(xy, d_xy, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     VO_HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -20,6 +20,8 @@
 #include "vo_state.h"
 #include "state_device.h"
 
+struct vo_pipeline_boot;    // pipeline_bootstrap.hip: the two-view bootstrap's workspace
+
 struct vo_pipeline {
   vo_ctx* ctx = nullptr;
   vo_ctx* det = nullptr;             // detection stream (+ the NMS workspace of all sequences)
@@ -102,6 +104,7 @@ struct vo_pipeline {
   int last_fbuf = 0;
   hipEvent_t evA = nullptr, evB = nullptr;
   double* d_newkp = nullptr;         // scratch of the bookkeeping entry point
+  vo_pipeline_boot* boot = nullptr;  // vo_pipeline_bootstrap_seq's workspace (device memory in dev_mem; made at its first call)
   // SIFT tracker mode (vo_pipeline_config.tracker_mode = 1; src/vo/features/tracker.py:60-61, sift.py:23-56): the frame's
   // keypoints and descriptors are made by the SIFT kernels on the tracker's stream, matched against the descriptors the
   // current Features carry (bytes, regrouped with them: matches.py:51-58, 134-141) on the matrix cores, and regrouped
@@ -266,4 +269,6 @@ VO_PIPE_INTERNAL void worker_main(vo_pipeline* p);
 VO_PIPE_INTERNAL int worker_idle(vo_pipeline* p);
 // pyramid and detection of the frame the handed-over states belong to, sequences q0 .. q0 + Sn - 1 (Sn = 0: all of them)
 VO_PIPE_INTERNAL int prime(vo_pipeline* p, bool wait = true, int q0 = 0, int Sn = 0);
+// releases p->boot (its device memory is in dev_mem)
+VO_PIPE_INTERNAL void vo_pipeline_boot_free(vo_pipeline* p);
 VO_PIPE_INTERNAL int enqueue_detection(vo_pipeline* p, int frame, int s, bool force, char* err_buf = nullptr, int q0 = 0, int Sn = 0);

@@ -166,6 +166,7 @@ void vo_pipeline_destroy(vo_pipeline* p) {
   for (vo_ctx* q : {p->det, p->trk})
     if (q) (void)hipStreamSynchronize(q->stream);
   dbg_stage("destroy: streams idle");
+  vo_pipeline_boot_free(p);
   for (void* q : p->dev_mem) (void)hipFree(q);
   for (void* q : p->host_mem) (void)hipHostFree(q);
   dbg_stage("destroy: memory freed");

@@ -67,6 +67,9 @@ struct vo_ctx {
   // pinned host staging
   void* h_pin = nullptr;
   size_t h_pin_cap = 0;
+  // bytes the device-resident forms of the bootstrap stages (vo_good_features_dev, vo_fundamental_*_dev) copied between
+  // host and device: scalars and the RANSAC batch's samples / counts; vo_pipeline_bootstrap_seq reports the difference
+  int64_t bytes_h2d = 0, bytes_d2h = 0;
 };
 
 // a launch that takes vo_ctx::next_stop as its stop event when one is set (and clears it)
@@ -186,6 +189,23 @@ extern "C" int vo_patch_descriptors_u8_dev(vo_ctx* ctx, const uint8_t* d_img, in
 extern "C" int vo_patch_descriptors_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_img, size_t img_stride, int S, int H, int W,
                                                  const double* d_kp_xy, size_t kp_stride, int N, int r, uint8_t* d_desc,
                                                  size_t desc_stride, int row_bytes);
+// Device-resident forms of the two-view bootstrap's stages (goodfeatures.hip, bootstrap.hip): inputs in HBM, results left
+// there.  vo_good_features / vo_fundamental_hypotheses / vo_fundamental_fit / vo_relative_pose upload, call these and
+// download.  All work on ctx->stream; the hypothesis form synchronises (the counts come back), the others do not.
+//   good_features: *d_xy_out (n float pairs) points into the context's workspace (scratch[7]) until its next call
+int vo_good_features_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const uint8_t* d_mask, int max_corners,
+                         double quality, double min_dist, int block, const float** d_xy_out, int32_t* n_out);
+//   hypotheses: samples (host, Hyp x 8, checked against N) are the only array uploaded; counts (host, Hyp) the only one
+//   downloaded; d_F Hyp x 9, d_counts Hyp, d_masks Hyp x cdiv(N, 64) words (nullable) are the caller's device buffers
+int vo_fundamental_hypotheses_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const int32_t* samples, int Hyp,
+                                  int normalize_samples, int error_kind, double threshold, int32_t* d_samples, double* d_F,
+                                  int32_t* d_counts, uint64_t* d_masks, int32_t* counts);
+//   fit: over the correspondences d_mask selects (nullable: all); d_F 9 doubles; d_n_used (nullable) their count
+int vo_fundamental_fit_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const uint8_t* d_mask, int normalize,
+                           double* d_F, int32_t* d_n_used);
+//   relative pose: d_M 12, d_X N x 3, d_mask_out N (nullable), d_M4 48 (nullable)
+int vo_relative_pose_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, int N, const uint8_t* d_inliers, const double* K1,
+                         const double* K2, const double* d_F, double* d_M, double* d_X, uint8_t* d_mask_out, double* d_M4);
 // the next `count` 32-bit outputs of NumPy's PCG64 Generator (ransac_host.hip); advances *rng
 void vo_rng_raw32(vo_pcg64* rng, int count, uint32_t* out);
 // DLT with a device-resident point count (dlt.hip)

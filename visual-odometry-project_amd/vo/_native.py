@@ -13,8 +13,9 @@ import numpy as np
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libvo_hip.so")
 
-VO_OK, VO_EINVAL, VO_ENOMEM, VO_EHIP, VO_ECAPACITY = 0, -1, -2, -3, -4
-_CODES = {VO_EINVAL: "VO_EINVAL", VO_ENOMEM: "VO_ENOMEM", VO_EHIP: "VO_EHIP", VO_ECAPACITY: "VO_ECAPACITY"}
+VO_OK, VO_EINVAL, VO_ENOMEM, VO_EHIP, VO_ECAPACITY, VO_ETRACKING = 0, -1, -2, -3, -4, -5
+_CODES = {VO_EINVAL: "VO_EINVAL", VO_ENOMEM: "VO_ENOMEM", VO_EHIP: "VO_EHIP", VO_ECAPACITY: "VO_ECAPACITY",
+          VO_ETRACKING: "VO_ETRACKING"}
 
 # kernel ids (vo_hip.h)
 K_HARRIS_RESPONSE, K_NMS_CANDIDATES, K_NMS_THRESHOLD, K_NMS_COMPACT, K_NMS_SELECT = 0, 1, 2, 3, 4
@@ -93,6 +94,26 @@ class StepResult(C.Structure):
     def idle(self):
         """The record of an idle lane (vo_pipeline_set_active_seq): nothing was computed for it."""
         return self.n_features_in == -1
+
+
+class BootstrapParams(C.Structure):
+    """vo_bootstrap_params: 0 in a field = its default (klt_max_level: -1)."""
+    _fields_ = [("max_corners", C.c_int32), ("quality", C.c_double), ("min_distance", C.c_double), ("block", C.c_int32),
+                ("klt_win", C.c_int32), ("klt_max_level", C.c_int32), ("threshold_px", C.c_double),
+                ("outlier_ratio", C.c_double), ("confidence", C.c_double), ("max_iterations", C.c_int32),
+                ("route", C.c_int32)]
+
+
+class BootstrapResult(C.Structure):
+    """vo_bootstrap_result."""
+    _fields_ = [("n_corners", C.c_int32), ("n_tracked", C.c_int32), ("n_ransac_inliers", C.c_int32),
+                ("n_landmarks", C.c_int32), ("n_features", C.c_int32), ("reserved", C.c_int32),
+                ("ransac_iterations", C.c_int64), ("M", C.c_double * 12), ("bytes_h2d", C.c_int64),
+                ("bytes_d2h", C.c_int64)]
+
+    def relative_pose(self):
+        """M: camera a -> camera b, (3, 4), |t| = 1."""
+        return np.array(self.M).reshape(3, 4)
 
 
 _vp, _i, _d, _sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
@@ -205,6 +226,9 @@ _SIGS = {
     "vo_pipeline_set_camera_seq": (_i, [_vp, _i, _vp, _vp]),
     "vo_pipeline_set_active_seq": (_i, [_vp, _i, _i]),
     "vo_pipeline_restart_seq": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "vo_pipeline_bootstrap_seq": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "vo_pipeline_bootstrap": (_i, [_vp, _i, _i, _vp, _vp]),
+    "vo_bootstrap_default_rng": (None, [_vp]),
 }
 
 

@@ -175,6 +175,23 @@ class Pipeline:
         self.ctx._chk(self.ctx._lib.vo_pipeline_restart_seq(self._h, int(seq), int(idx), *args,
                                                             C.byref(pcg) if pcg is not None else None))
 
+    def bootstrap(self, idx_a, idx_b, seq=0, generator=None, max_corners=0, quality=0.0, min_distance=0.0, block=0,
+                  klt_win=0, klt_max_level=None, threshold_px=0.0, outlier_ratio=0.0, confidence=0.0, max_iterations=0):
+        """The two-view bootstrap of lane `seq` from frame slots idx_a, idx_b of its frame store, inside the pipeline
+        (vo_pipeline_bootstrap_seq; nothing in flight): what vo.driver.bootstrap + set_state (a pipeline that is not running
+        yet) or restart (a running one; generator: the lane's P3P generator, None = the state the pipeline was seeded
+        with) do, without an array leaving HBM.  Parameters left at 0 / None take vo_bootstrap_params' defaults.  Returns a
+        BootstrapResult; a failure (too few corners / survivors, no model) raises VoError and leaves the lane as it was."""
+        from vo import _native
+        prm = _native.BootstrapParams(int(max_corners), float(quality), float(min_distance), int(block), int(klt_win),
+                                      -1 if klt_max_level is None else int(klt_max_level), float(threshold_px),
+                                      float(outlier_ratio), float(confidence), int(max_iterations), 0)
+        pcg = None if generator is None else _native.Pcg64.from_generator(generator)
+        res = _native.BootstrapResult()
+        self.ctx._chk(self.ctx._lib.vo_pipeline_bootstrap_seq(self._h, int(seq), int(idx_a), int(idx_b), C.byref(prm),
+                                                              C.byref(pcg) if pcg is not None else None, C.byref(res)))
+        return res
+
     def checkpoint(self):
         """Keeps a copy of every sequence's Features / State as they are now (nothing in flight) in HBM."""
         self.ctx._chk(self.ctx._lib.vo_pipeline_checkpoint(self._h))

@@ -108,7 +108,7 @@ def _gray(image):
 def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
                   klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                   redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
-                  bootstrap_threshold: float = 0.25):
+                  bootstrap_threshold: float = 0.25, bootstrap: str = "host"):
     """Same loop, same bootstrap, but the steady state runs as the device-resident pipeline (vo_pipeline_*):
     after the host bootstrap the Features / State arrays are handed to the GPU once, every later frame costs one
     image upload and one call, and nothing but the pose record comes back.  KLT tracker mode with the Harris
@@ -118,22 +118,38 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     device).  redetect_start_pose: "identity" is the reference's
     update_features (klt.py:148-153: re-detected keypoints start their track at np.eye(4), so away from the origin
     they triangulate against a wrong baseline and can take the estimate with them); "current" starts them at the
-    pose of the frame they were found on."""
+    pose of the frame they were found on.
+    bootstrap: "host" -- the bootstrap through the drop-in classes, handed over with set_state; "device" -- frames 0 and 2
+    go into two slots of the frame store and the pipeline bootstraps itself from them (Pipeline.bootstrap,
+    vo_pipeline_bootstrap_seq): same kernels, same result, no array brought back in between."""
     from vo import _native
+    _check_bootstrap_route(bootstrap)
     ctx = context or _native.default_context()
-    state, tracker = _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level,
-                                       bootstrap_threshold)
-    frame = state.curr_frame
-    img = _gray(frame.image)
-    H, W = img.shape
     K = np.asarray(sequence.get_camera().intrinsic_matrix, np.float64)
     SLOTS = 4
-    pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp,
-                                                                     redetect_start_pose))
-    pipe.set_frame(0, img)
-    pipe.set_state(0, frame.features, state.curr_pose, state.prev_pose, num_features=tracker._tracker._num_features)
-    trajectory = [np.eye(4), state.get_pose()]
-    n_landmarks = [len(frame.features.triangulated_inliers_landmarks)]
+    if bootstrap == "device":
+        img0, img = _bootstrap_frames(sequence)
+        H, W = img.shape
+        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(None, n_keypoints, klt_win, klt_max_level, hyp,
+                                                                         redetect_start_pose))
+        pipe.set_frame(1, img0)                          # (slot 1 takes frame 3 next: the bootstrap is done with it by then)
+        pipe.set_frame(0, img)
+        boot = pipe.bootstrap(1, 0, **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
+                                                        bootstrap_max_level, bootstrap_threshold))
+        trajectory = [np.eye(4), pipe.get_state()["curr_pose"]]
+        n_landmarks = [boot.n_landmarks]
+    else:
+        state, tracker = _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level,
+                                           bootstrap_threshold)
+        frame = state.curr_frame
+        img = _gray(frame.image)
+        H, W = img.shape
+        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp,
+                                                                         redetect_start_pose))
+        pipe.set_frame(0, img)
+        pipe.set_state(0, frame.features, state.curr_pose, state.prev_pose, num_features=tracker._tracker._num_features)
+        trajectory = [np.eye(4), state.get_pose()]
+        n_landmarks = [len(frame.features.triangulated_inliers_landmarks)]
     seconds, results = [], []
     # Frames go through a ring of pinned buffers (the grey conversion writes into them) and are uploaded on the
     # pipeline's upload stream ONE STEP AHEAD of their use (vo_pipeline_set_frame_pinned): while step k -> k+1 runs,
@@ -215,8 +231,30 @@ def _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_w
     return state, tracker
 
 
+def _check_bootstrap_route(bootstrap):
+    if bootstrap not in ("host", "device"):
+        raise ValueError("bootstrap must be 'host' or 'device', not %r" % (bootstrap,))
+
+
+def _bootstrap_frames(sequence):
+    """Frames 0 and 2 of a recording as grey images (main.py:204-212: frame 1 is skipped)."""
+    first = next(sequence)
+    next(sequence)
+    return _gray(first.image), _gray(next(sequence).image)
+
+
+def _bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold):
+    """Pipeline.bootstrap's parameters for what _device_bootstrap sets up on the host route."""
+    return dict(max_corners=n_keypoints, klt_win=bootstrap_win or klt_win,
+                klt_max_level=klt_max_level if bootstrap_max_level is None else bootstrap_max_level,
+                threshold_px=bootstrap_threshold)
+
+
 def _pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose):
-    """The pipeline's configuration for the steady state of main.py:194-201 (what run_on_device documents)."""
+    """The pipeline's configuration for the steady state of main.py:194-201 (what run_on_device documents).  state: the
+    bootstrap's State (its bearing threshold), None: State's default."""
+    if state is None:
+        state = State(None)
     return dict(n_keypoints=n_keypoints, klt_win=klt_win, klt_max_level=klt_max_level, hyp=hyp, p3p_threshold=1.25 ** 2,
                 outlier_ratio=0.9, confidence=0.9999, max_iterations=10000, refine_iters=20,
                 bearing_threshold=state._bearing_threshold, redetect_start_pose=redetect_start_pose)
@@ -288,17 +326,22 @@ def _frame_shape(sequence):
 def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
                         klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
-                        bootstrap_threshold: float = 0.25):
+                        bootstrap_threshold: float = 0.25, bootstrap: str = "host"):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
     as run_on_device does it; when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
     goes idle (vo_pipeline_set_active_seq) -- lane_schedule says when.  Frames go through one pinned ring per lane,
     uploaded a step ahead.  The steps in flight are drained before a lane changes recording (nothing may be in flight for
     the three calls), so each such step loses the look-ahead once.  All recordings must have the same frame size.
+    bootstrap="device": a lane's recording starts from its frames 0 and 2 inside the pipeline instead (Pipeline.bootstrap):
+    for a change of recording the lane goes idle, frame 0 goes into the slot after the current one and frame 2 into the
+    current one, then one call.  (A recording without a steady-state step never holds a lane: host route.)
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
     each step the recording took part in).  Each lane computes what run_on_device computes for its recording alone."""
     from vo import _native
+    _check_bootstrap_route(bootstrap)
+    on_device = bootstrap == "device"
     sequences = list(sequences)
     if not sequences:
         return []
@@ -335,7 +378,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
             open_result(r)
     if steps:
         first = next(r for (_, _, r) in plan["starts"])
-        state0, _ = boot_of(first)
+        state0 = None if on_device else boot_of(first)[0]
         K0 = np.asarray(sequences[first].get_camera().intrinsic_matrix, np.float64)
         SLOTS = 4
         pipe = _native.Pipeline(ctx, H, W, SLOTS, K0, sequences=lanes,
@@ -351,7 +394,22 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
             ring[lane][s][...] = _gray(next_frame(r).image)
             pipe.set_frame(s, ring[lane][s], seq=lane, pinned=True)
 
+        def start_on_device(lane, r, t, slot):
+            img0, img2 = _bootstrap_frames(sequences[r])
+            pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
+            if t > 0:
+                pipe.set_active(lane, False)             # (the lane's frame in the current slot can only be replaced while idle)
+            a = (slot + 1) % SLOTS                       # (the slot the recording's next frame takes afterwards)
+            pipe.set_frame(a, img0, seq=lane, pinned=False)
+            pipe.set_frame(slot, img2, seq=lane, pinned=False)
+            res = pipe.bootstrap(a, slot, seq=lane, **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
+                                                                        bootstrap_max_level, bootstrap_threshold))
+            out[r] = dict(trajectory=[np.eye(4), pipe.get_state(lane)["curr_pose"]], n_landmarks=[res.n_landmarks],
+                          frame_seconds=[], results=[], features=None)
+
         def start(lane, r, t, slot):
+            if on_device:
+                return start_on_device(lane, r, t, slot)
             state, tracker = boot_of(r)
             open_result(r)
             frame = state.curr_frame
