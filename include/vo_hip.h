@@ -364,6 +364,29 @@ typedef struct vo_ransac_state {
   int32_t s, adaptive;
 } vo_ransac_state;
 int vo_rng_choice(vo_pcg64* rng, int pop, int s, int count, int32_t* out);
+/* One Generator.choice(pop, 8, replace=False) from the 15 outputs raw[0..14] it consumes when no draw is rejected (eight
+ * Floyd draws, seven for the shuffle): host arithmetic, the function the device sampler runs.  *possibly_rejected = 1
+ * when one of the draws could have been rejected (the generator may then stand elsewhere).  pop >= 9 (VO_EINVAL below:
+ * at pop = 8 the first draw consumes no output). */
+int vo_rng_choice8_from_raw(const uint32_t* raw, int pop, int32_t* out, int* possibly_rejected);
+/* ---- the two-view bootstrap's RANSAC loop on the device (bootstrap.hip) ----
+ * vo_fundamental_ransac: the whole loop of _find_fundamental_matrix_ransac (:110-163; src/vo/algorithms/ransac.py:69-129,
+ *   s = 8) in one call, with nothing of it on the host: the generator's outputs are made on the device from *rng, every
+ *   sample is derived from them in the hypothesis kernel, one wavefront replays the accept / adapt rule (strict `>`,
+ *   outlier ratio clipped to [0.01, 0.99], the bound through a table made with the host's libm) over batches of 2048
+ *   samples, and the closing fit runs over the accepted model's inliers.  F 9, inlier_mask N bytes; iterations,
+ *   best_count, finished_by_host nullable.  *rng: where the loop starts; advanced by what it consumed.  The results equal
+ *   vo_rng_choice + vo_fundamental_hypotheses + vo_ransac_replay + vo_fundamental_fit composed on the host.  That
+ *   composition is also the fall-back, reported as *finished_by_host = 1: a loop whose consumed samples hold a draw NumPy
+ *   might have rejected, N = 8 (the first Floyd draw consumes no output), max_iterations < 0 (unbounded) or > 65536.
+ *   VO_ETRACKING: no model with 8 inliers.
+ * vo_rng_raw32_device: the next `count` 32-bit outputs of *rng (a buffered half first, then each 64-bit output low half,
+ *   high half) made by the kernel that feeds the loop above, brought to the host; *rng advanced as NumPy's would be. */
+int vo_fundamental_ransac(vo_ctx* ctx, const double* p1, const double* p2, int N, int normalize_samples, int error_kind,
+                          double threshold, double outlier_ratio, double confidence, int64_t max_iterations,
+                          vo_pcg64* rng, double* F, uint8_t* inlier_mask, int64_t* iterations, int32_t* best_count,
+                          int32_t* finished_by_host);
+int vo_rng_raw32_device(vo_ctx* ctx, vo_pcg64* rng, int count, uint32_t* out);
 int64_t vo_ransac_num_iterations(double confidence, double outlier_ratio, int s);
 int vo_ransac_replay(vo_ransac_state* st, const uint8_t* valid, const int32_t* counts, int B,
                      int N, int64_t* n_done, int32_t* best_count, int32_t* best_idx,
@@ -668,8 +691,9 @@ int vo_pipeline_restart_seq(vo_pipeline* p, int seq, int idx, int n, const doubl
  *      pyramid dropped; this lane's pyramid + detection of frame b made for it alone; other lanes untouched).
  * idx_a is any other slot.  Nothing may be in flight.  The call is synchronous.
  * No array sized by pixels or by features crosses between host and device: what crosses is counted in bytes_h2d /
- * bytes_d2h -- per RANSAC batch of 2048 samples 64 KiB up (the samples, drawn on the host from the reference's generator)
- * and 8 KiB down (the inlier counts the sequential accept / adapt rule, vo_ransac_replay, walks), plus scalars.
+ * bytes_d2h -- scalars: parameters and the RANSAC loop's control block up; counts, status words, F, M and the landmark
+ * count down (the loop's sampler and accept / adapt rule run on the device, see vo_fundamental_ransac; the first call with
+ * given confidence / budget also uploads the bound's threshold table, 8 bytes per iteration of the budget).
  * Failures are status codes: VO_ETRACKING for fewer than 8 corners or survivors or a RANSAC without a model of 8 inliers,
  * VO_ECAPACITY for candidate lists or a corner count beyond the feature capacity.  Until step 4 only workspace is
  * written, so A FAILED CALL LEAVES THE LANE AS IT WAS before it: Features, control block, generator, activity.
@@ -686,7 +710,7 @@ typedef struct vo_bootstrap_params {      /* 0 in a field = the default named he
 } vo_bootstrap_params;
 typedef struct vo_bootstrap_result {
   int32_t n_corners, n_tracked, n_ransac_inliers, n_landmarks, n_features;
-  int32_t reserved;
+  int32_t reserved;                       /* 1: the RANSAC loop was finished by the host sampler  */
   int64_t ransac_iterations;
   double  M[12];                          /* camera a -> camera b, 3x4 row-major, |t| = 1        */
   int64_t bytes_h2d, bytes_d2h;           /* what the call copied between host and device        */
@@ -694,6 +718,16 @@ typedef struct vo_bootstrap_result {
 int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, const vo_bootstrap_params* prm /* NULL: defaults */,
                               const vo_pcg64* rng, vo_bootstrap_result* out);
 int vo_pipeline_bootstrap(vo_pipeline* p, int idx_a, int idx_b, const vo_bootstrap_params* prm, vo_bootstrap_result* out);
+/* Several lanes in one call: lanes seqs[0 .. n_lanes-1] (in range, distinct) go through ONE set of launches -- the lane is a
+ * grid dimension of every stage but Shi-Tomasi -- and each ends exactly as if vo_pipeline_bootstrap_seq(p, seqs[i], idx_a,
+ * idx_b, prm, rngs ? &rngs[i] : NULL, &outs[i]) had been called for it alone, in the order given.  The call-level rules are
+ * the one-lane call's; a refused call (VO_EINVAL) changes nothing.  A lane that FAILS (VO_ETRACKING: fewer than 8 corners or
+ * survivors, no model with 8 inliers; VO_ECAPACITY) gets its code in status[i] (nullable) and stays as it was, the other
+ * lanes go through; the call returns VO_OK when every lane did, otherwise the first failing lane's code, the lane named in
+ * the error text.  outs[i].bytes_h2d / bytes_d2h: the CALL's traffic divided by n_lanes (rounded up).  outs[i].reserved:
+ * 1 = the lane's RANSAC loop was finished by the host sampler (see vo_fundamental_ransac), 0 = on the device. */
+int vo_pipeline_bootstrap_lanes(vo_pipeline* p, int n_lanes, const int32_t* seqs, int idx_a, int idx_b,
+                                const vo_bootstrap_params* prm, const vo_pcg64* rngs, vo_bootstrap_result* outs, int32_t* status);
 /* the generator the bootstrap's RANSAC starts from: np.random.default_rng(2023)'s PCG64 state */
 void vo_bootstrap_default_rng(vo_pcg64* rng);
 

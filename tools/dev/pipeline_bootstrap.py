@@ -11,6 +11,13 @@ are rendered before anything is timed.  --repeats calls of each route per record
 
     python3 tools/dev/pipeline_bootstrap.py [--recordings 2] [--repeats 20] [--json OUT]
     python3 tools/dev/pipeline_bootstrap.py --trace 20      # the device route only, untimed: for rocprofv3 --kernel-trace --stats
+
+Lanes mode: a running pipeline of --sequences lanes, every lane its own recording; the first --lanes L of them change
+recording (idle, two frames each, bootstrap) either in ONE Pipeline.bootstrap_lanes call or in L Pipeline.bootstrap calls,
+alternating in one process; the clock runs from the first frame upload to the end of the last call.
+
+    python3 tools/dev/pipeline_bootstrap.py --lanes 4 [--sequences 16] [--repeats 40] [--json OUT]
+    python3 tools/dev/pipeline_bootstrap.py --lanes 16 --trace 10     # the one-call route only, untimed
 """
 import argparse
 import json
@@ -49,13 +56,90 @@ class Recording:
         return Frame(self.frames[self.i - 1].copy(), sensor=self.seq.get_camera())
 
 
+def summary(name, ts):
+    ts = sorted(ts)
+    q = statistics.quantiles(ts, n=10)
+    d = dict(median_ms=statistics.median(ts) * 1e3, min_ms=ts[0] * 1e3, max_ms=ts[-1] * 1e3, p10_ms=q[0] * 1e3,
+             p90_ms=q[-1] * 1e3, calls=len(ts))
+    print("%-8s median %8.3f ms   p10 %8.3f  p90 %8.3f   min %8.3f  max %8.3f   (%d calls)" % (
+        name, d["median_ms"], d["p10_ms"], d["p90_ms"], d["min_ms"], d["max_ms"], len(ts)), flush=True)
+    return d
+
+
+def lanes_mode(a):
+    import numpy as np
+    from vo import _native, driver
+    S, L = max(a.sequences, a.lanes), a.lanes
+    ctx = _native.Context(0)
+    recs = [Recording(2023 + 7 * r) for r in range(S)]
+    K = np.asarray(recs[0].get_camera().intrinsic_matrix, np.float64)
+    pipe = _native.Pipeline(ctx, H, W, 4, K, sequences=S, **driver._pipeline_kwargs(None, N, 17, 2, 4000, "current"))
+    boot = driver._bootstrap_kwargs(N, 17, 2, WIN, LEVEL, THR)
+    for q, rec in enumerate(recs):
+        pipe.set_frame(1, rec.frames[0], seq=q)
+        pipe.set_frame(0, rec.frames[2], seq=q)
+    first = pipe.bootstrap_lanes(1, 0, list(range(S)), **boot)
+    assert all(r.status == 0 for r in first), [r.status for r in first]
+    for q, rec in enumerate(recs):
+        pipe.set_frame(1, rec.frames[3], seq=q)
+    pipe.submit(0, 1)
+    pipe.collect_all()
+    slot, other, lanes = 1, 2, list(range(L))
+
+    def frames_in():
+        for q in lanes:
+            pipe.set_active(q, False)
+            pipe.set_frame(other, recs[q].frames[0], seq=q)
+            pipe.set_frame(slot, recs[q].frames[2], seq=q)
+
+    def one_call():
+        frames_in()
+        return pipe.bootstrap_lanes(other, slot, lanes, **boot)
+
+    def one_each():
+        frames_in()
+        return [pipe.bootstrap(other, slot, seq=q, **boot) for q in lanes]
+
+    if a.trace:
+        for _ in range(a.trace):
+            one_call()
+        print("bootstrap_lanes calls", a.trace, "lanes", L)
+    else:
+        for _ in range(3):
+            one_each()
+            one_call()
+        t = dict(one_each=[], one_call=[])
+        for _ in range(a.repeats):
+            for name, fn in (("one_each", one_each), ("one_call", one_call)):
+                ctx.sync()
+                t0 = time.perf_counter()
+                res = fn()
+                t[name].append(time.perf_counter() - t0)
+        out = dict(H=H, W=W, corners=N, sequences=S, lanes=L, repeats=a.repeats)
+        for name, ts in t.items():
+            out[name] = summary(name, ts)
+        out["bytes_h2d"], out["bytes_d2h"] = int(res[0].bytes_h2d), int(res[0].bytes_d2h)
+        print("%d lanes: one call / one each = %.3f; per lane %.3f ms in one call; %d bytes up, %d down per lane" % (
+            L, out["one_call"]["median_ms"] / out["one_each"]["median_ms"], out["one_call"]["median_ms"] / L,
+            res[0].bytes_h2d, res[0].bytes_d2h))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+    pipe.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lanes", type=int, default=0)
+    ap.add_argument("--sequences", type=int, default=16)
     ap.add_argument("--recordings", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--json", default=None)
     ap.add_argument("--trace", type=int, default=0)
     a = ap.parse_args()
+    if a.lanes:
+        return lanes_mode(a)
     import numpy as np
     from vo import _native, driver
     ctx = _native.Context(0)
@@ -109,13 +193,7 @@ def main():
     out = dict(H=H, W=W, corners=N, recordings=len(recs), repeats=a.repeats, first=dict(
         n_corners=first.n_corners, n_tracked=first.n_tracked, n_landmarks=first.n_landmarks))
     for name, ts in t.items():
-        ts = sorted(ts)
-        q = statistics.quantiles(ts, n=10)
-        out[name] = dict(median_ms=statistics.median(ts) * 1e3, min_ms=ts[0] * 1e3, max_ms=ts[-1] * 1e3, p10_ms=q[0] * 1e3,
-                         p90_ms=q[-1] * 1e3, calls=len(ts))
-        print("%-6s median %8.3f ms   p10 %8.3f  p90 %8.3f   min %8.3f  max %8.3f   (%d calls)" % (
-            name, out[name]["median_ms"], out[name]["p10_ms"], out[name]["p90_ms"], out[name]["min_ms"], out[name]["max_ms"],
-            len(ts)), flush=True)
+        out[name] = summary(name, ts)
     out["bytes_h2d"], out["bytes_d2h"] = int(res.bytes_h2d), int(res.bytes_d2h)
     print("device route: %d bytes up, %d bytes down per call; host / device = %.2f" % (
         res.bytes_h2d, res.bytes_d2h, out["host"]["median_ms"] / out["device"]["median_ms"]))

@@ -1,31 +1,61 @@
-// Frame pipeline: the two-view bootstrap from two frames of the frame store (vo_hip.h, vo_pipeline_bootstrap_seq).
+// Frame pipeline: the two-view bootstrap from two frames of the frame store, for any subset of the lanes through one set
+// of launches (vo_hip.h, vo_pipeline_bootstrap_lanes; vo_pipeline_bootstrap_seq is its one-lane call).
 //
 // The stages are the kernels the host route (vo/driver.py: bootstrap) calls one ABI call at a time -- Shi-Tomasi corners,
-// pyramids + LK, 8-point hypotheses / scores / closing fit, relative pose -- in their device-resident forms; the
-// bookkeeping between them, NumPy on the host route, is three small kernels here:
+// pyramids + LK, the 8-point RANSAC loop with its closing fit, relative pose -- in their device-resident forms, with the
+// lane as a grid dimension everywhere but in Shi-Tomasi; the bookkeeping between them, NumPy on the host route, is three
+// small kernels here:
+//   boot_corners_kernel     a lane's corners from the context's workspace into the lane's block, with their count
 //   boot_gather_kernel      klt.py:244-262 + matches.py:26-212 for fresh Features and identity pairs: the survivors of
 //                           status & err < thr, in order, as the float64 (n, 2) pairs the bootstrap kernels read.  The
 //                           fresh frame-a Features block is never materialised: all its fields are constants (state 0,
 //                           track = keypoint, pose = identity, landmark NaN) that the apply kernel writes where they survive.
-//   boot_unpack_mask_kernel the accepted hypothesis' packed inlier row -> one byte per correspondence
 //   bootstrap_apply_kernel  driver.py: bootstrap after triangulate_matches (update_with_local_pose,
 //                           update_with_local_landmarks incl. _check_landmarks, reset_outliers) into the lane's current
 //                           Features block and control block
-// Everything before the apply kernel writes workspace only, so a failed call leaves the lane as it was.
+// Everything before the apply kernel writes workspace only, and the apply kernel skips a lane whose RANSAC did not end
+// with a model, so a lane that fails is left as it was while the others go through.
 #include "pipeline.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int BOOT_BATCH = 2048;     // RANSAC samples per launch (what crosses PCIe per batch: 64 KiB up, 8 KiB down)
+// Lane k of a call (its position in the call, not its number) owns block k of every workspace array.
+struct boot_lanes {
+  size_t xy;        // floats between the lanes' corner / tracker-output arrays
+  size_t out;       // elements between their status / err arrays
+  size_t pts;       // doubles between their p1 / p2 arrays
+};
 
-// One workgroup walks the n0 tracked corners in order, 256 at a time (ballot + prefix: the survivors keep their order).
+// the corners Shi-Tomasi left in the context's workspace -> the lane's block, with their count (0: the lane sits out)
+__global__ __launch_bounds__(256) void boot_corners_kernel(const float* __restrict__ src, int n0, int n_live,
+                                                           float* __restrict__ dst, int32_t* __restrict__ cnt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 2 * n0) dst[i] = src[i];
+  if (i == 0) {
+    cnt[0] = n_live;
+    cnt[1] = 0;
+    cnt[2] = 0;
+  }
+}
+
+// One workgroup per lane walks its n0 tracked corners in order, 256 at a time (ballot + prefix: the survivors keep their
+// order).  cnt: four ints per lane -- [0] corners (in), [1] survivors (out).
 __global__ __launch_bounds__(256) void boot_gather_kernel(const float* __restrict__ xy_a, const float* __restrict__ xy_b,
                                                           const uint8_t* __restrict__ status, const float* __restrict__ err,
-                                                          float err_thr, int n0, double* __restrict__ p1,
-                                                          double* __restrict__ p2, int32_t* __restrict__ n_out) {
+                                                          float err_thr, boot_lanes ln, double* __restrict__ p1,
+                                                          double* __restrict__ p2, int32_t* __restrict__ cnt) {
   __shared__ int s_cnt[4];
+  const size_t q = blockIdx.x;
+  xy_a += q * ln.xy;
+  xy_b += q * ln.xy;
+  status += q * ln.out;
+  err += q * ln.out;
+  p1 += q * ln.pts;
+  p2 += q * ln.pts;
+  cnt += q * 4;
+  const int n0 = cnt[0];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   int base = 0;
   for (int i0 = 0; i0 < n0; i0 += 256) {
@@ -50,33 +80,45 @@ __global__ __launch_bounds__(256) void boot_gather_kernel(const float* __restric
     base += total;
     __syncthreads();
   }
-  if (t == 0) *n_out = base;
+  if (t == 0) cnt[1] = base;
 }
 
-__global__ __launch_bounds__(256) void boot_unpack_mask_kernel(const unsigned long long* __restrict__ row, int n,
-                                                               uint8_t* __restrict__ mask) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) mask[i] = (uint8_t)((row[i >> 6] >> (i & 63)) & 1ull);
-}
-
-struct boot_apply_args {
-  int n, num_features;
-  int keep_ransac, keep_raw_pos;       // 1: the control block's RANSAC fields / generator position stay
-  int64_t n_iterations;
-  double outlier_ratio;
+struct boot_apply_lane {      // what the host knows of a lane (uploaded: 24 bytes per lane)
+  int32_t seq;                // the lane's number
+  int32_t keep_ransac, keep_raw_pos;       // 1: the control block's RANSAC fields / generator position stay
+  int32_t pad;
   uint64_t raw_pos;
 };
+struct boot_apply_args {
+  int64_t n_iterations;
+  double outlier_ratio;
+  size_t pts, X, F, mask;     // strides of the workspace blocks (doubles, doubles, doubles, bytes)
+};
 
-// One workgroup (n <= feature capacity).  mask = RANSAC inlier AND in front of both cameras (relative_pose_kernel's), X the
-// winner's triangulation of every correspondence, M camera a -> camera b.  With prev_pose = identity:
+// One workgroup per lane (n <= feature capacity); lanes whose RANSAC did not end with a model are left as they were.
+// mask = RANSAC inlier AND in front of both cameras (relative_pose_kernel's), X the winner's triangulation of every
+// correspondence, M camera a -> camera b.  With prev_pose = identity:
 //   curr_pose = inv(M4) (closed form: [R^T | -R^T t]), world landmarks = X;
 //   update_with_local_landmarks: masked features -> state 2 with X, then _check_landmarks drops those behind either camera;
 //   reset_outliers(behind), reset_outliers(~mask): state 0, track = own keypoint, start pose = curr_pose.
-__global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args a, const double* __restrict__ p1,
+__global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args g, const boot_apply_lane* __restrict__ lanes,
+                                                              const vo_f8_ctl* __restrict__ f8, const double* __restrict__ p1,
                                                               const double* __restrict__ p2, const uint8_t* __restrict__ mask,
                                                               const double* __restrict__ X, const double* __restrict__ Min,
-                                                              vo_feat F, vo_seq_ctl* __restrict__ ctl,
-                                                              int32_t* __restrict__ n_land_out) {
+                                                              vo_feat Fall, vo_seq_ctl* __restrict__ ctls,
+                                                              int32_t* __restrict__ cnt) {
+  const size_t q = blockIdx.x;
+  if (f8[q].status != VO_F8_DONE) return;
+  const boot_apply_lane a = lanes[q];
+  const int a_n = f8[q].n, a_num_features = cnt[4 * q];
+  p1 += q * g.pts;
+  p2 += q * g.pts;
+  mask += q * g.mask;
+  X += q * g.X;
+  Min += q * g.F;
+  const vo_feat F = vo_feat_seq(Fall, (size_t)a.seq);
+  vo_seq_ctl* ctl = ctls + a.seq;
+  int32_t* n_land_out = cnt + 4 * q + 2;
   __shared__ double s_M[12], s_T[12];
   __shared__ int s_land;
   const int t = threadIdx.x;
@@ -89,7 +131,7 @@ __global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args a,
   }
   __syncthreads();
   int mine = 0;
-  for (int i = t; i < a.n; i += 256) {
+  for (int i = t; i < a_n; i += 256) {
     const double kx = p2[2 * i], ky = p2[2 * i + 1];
     F.kp[2 * i] = (float)kx;             // (LK's float32 output widened by the gather: exact both ways)
     F.kp[2 * i + 1] = (float)ky;
@@ -127,13 +169,13 @@ __global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args a,
   if (t == 0) {
     // the control block starts over as in a hand-over (pipeline_state.hip: upload_state)
     const uint64_t raw_pos = a.keep_raw_pos ? ctl->raw_pos : a.raw_pos;
-    const int64_t n_it = a.keep_ransac ? ctl->n_iterations : a.n_iterations;
-    const double orat = a.keep_ransac ? ctl->outlier_ratio : a.outlier_ratio;
+    const int64_t n_it = a.keep_ransac ? ctl->n_iterations : g.n_iterations;
+    const double orat = a.keep_ransac ? ctl->outlier_ratio : g.outlier_ratio;
     vo_seq_ctl h;
     memset(&h, 0, sizeof(h));
-    h.n = a.n;
-    h.n2 = a.n;
-    h.num_features = a.num_features;
+    h.n = a_n;
+    h.n2 = a_n;
+    h.num_features = a_num_features;
     h.raw_pos = raw_pos;
     h.n_iterations = n_it;
     h.outlier_ratio = orat;
@@ -151,39 +193,48 @@ __global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args a,
 
 }  // namespace
 
-// the bootstrap's workspace, made at the first call and kept (the pyramids grow when a call asks for more levels)
+// The bootstrap's workspace: one block per lane of a call (by its position in the call), grown to the largest lane count
+// seen and kept (the pyramids also grow when a call asks for more levels).  Superseded blocks stay the pipeline's until it
+// is destroyed.
 struct vo_pipeline_boot {
-  uint8_t* pyr[2] = {nullptr, nullptr};
+  int lanes = 0;
   size_t pyr_bytes = 0;
-  double *p1 = nullptr, *p2 = nullptr, *X = nullptr, *F = nullptr, *Fhyp = nullptr;   // F: [0..8] F, [16..27] M
+  uint8_t* pyr[2] = {nullptr, nullptr};          // [lanes][pyr_bytes]
+  float *xy = nullptr, *next = nullptr, *err = nullptr;     // corners of frame a, LK's outputs: [lanes][cap * 2], [lanes][cap]
+  uint8_t* status = nullptr;
+  double *p1 = nullptr, *p2 = nullptr, *X = nullptr, *F = nullptr;   // F: 32 doubles per lane, [0..8] F, [16..27] M
   uint8_t *inl = nullptr, *mask = nullptr;
-  int32_t *cnt = nullptr, *samples = nullptr, *counts = nullptr;
-  uint64_t* masks = nullptr;
+  int32_t *cnt = nullptr, *seq = nullptr;        // cnt: four ints per lane (corners, survivors, landmarks, spare)
+  boot_apply_lane* apply = nullptr;
 };
 typedef vo_pipeline_boot boot_ws;
 
-static int boot_workspace(vo_pipeline* p, size_t pyr_bytes) {
-  if (!p->boot) {
-    p->boot = new vo_pipeline_boot();
-    boot_ws& w = *p->boot;
-    const size_t cap = (size_t)p->cap, words = (cap + 63) / 64;
-    VO_TRY(dev_alloc(p, &w.p1, cap * 2));
-    VO_TRY(dev_alloc(p, &w.p2, cap * 2));
-    VO_TRY(dev_alloc(p, &w.X, cap * 3));
-    VO_TRY(dev_alloc(p, &w.F, (size_t)32));
-    VO_TRY(dev_alloc(p, &w.Fhyp, (size_t)BOOT_BATCH * 9));
-    VO_TRY(dev_alloc(p, &w.inl, cap));
-    VO_TRY(dev_alloc(p, &w.mask, cap));
-    VO_TRY(dev_alloc(p, &w.cnt, (size_t)4));
-    VO_TRY(dev_alloc(p, &w.samples, (size_t)BOOT_BATCH * 8));
-    VO_TRY(dev_alloc(p, &w.counts, (size_t)BOOT_BATCH));
-    VO_TRY(dev_alloc(p, &w.masks, (size_t)BOOT_BATCH * words));
-  }
+static int boot_workspace(vo_pipeline* p, int L, size_t pyr_bytes) {
+  if (!p->boot) p->boot = new vo_pipeline_boot();
   boot_ws& w = *p->boot;
-  if (w.pyr_bytes < pyr_bytes) {         // (a smaller one stays the pipeline's until it is destroyed)
+  const size_t cap = (size_t)p->cap;
+  if (w.lanes < L) {
+    w.lanes = 0;
     w.pyr_bytes = 0;
-    VO_TRY(dev_alloc(p, &w.pyr[0], pyr_bytes));
-    VO_TRY(dev_alloc(p, &w.pyr[1], pyr_bytes));
+    VO_TRY(dev_alloc(p, &w.xy, L * cap * 2));
+    VO_TRY(dev_alloc(p, &w.next, L * cap * 2));
+    VO_TRY(dev_alloc(p, &w.err, L * cap));
+    VO_TRY(dev_alloc(p, &w.status, L * cap));
+    VO_TRY(dev_alloc(p, &w.p1, L * cap * 2));
+    VO_TRY(dev_alloc(p, &w.p2, L * cap * 2));
+    VO_TRY(dev_alloc(p, &w.X, L * cap * 3));
+    VO_TRY(dev_alloc(p, &w.F, (size_t)L * 32));
+    VO_TRY(dev_alloc(p, &w.inl, L * cap));
+    VO_TRY(dev_alloc(p, &w.mask, L * cap));
+    VO_TRY(dev_alloc(p, &w.cnt, (size_t)L * 4));
+    VO_TRY(dev_alloc(p, &w.seq, (size_t)L));
+    VO_TRY(dev_alloc(p, &w.apply, (size_t)L));
+    w.lanes = L;
+  }
+  if (w.pyr_bytes < pyr_bytes) {
+    w.pyr_bytes = 0;
+    VO_TRY(dev_alloc(p, &w.pyr[0], (size_t)w.lanes * pyr_bytes));
+    VO_TRY(dev_alloc(p, &w.pyr[1], (size_t)w.lanes * pyr_bytes));
     w.pyr_bytes = pyr_bytes;
   }
   return VO_OK;
@@ -207,19 +258,23 @@ void vo_bootstrap_default_rng(vo_pcg64* rng) {
   rng->uinteger = 0;
 }
 
-int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, const vo_bootstrap_params* prm,
-                              const vo_pcg64* rng, vo_bootstrap_result* out) {
+int vo_pipeline_bootstrap_lanes(vo_pipeline* p, int n_lanes, const int32_t* seqs, int idx_a, int idx_b,
+                                const vo_bootstrap_params* prm, const vo_pcg64* rngs, vo_bootstrap_result* outs, int32_t* status) {
   if (!p) return VO_EINVAL;
   vo_ctx* ctx = p->ctx;
   const vo_pipeline_config& c = p->cfg;
-  VO_REQUIRE(ctx, out, "pipeline_bootstrap: null result");
-  memset(out, 0, sizeof(*out));
+  const int L = n_lanes;
+  VO_REQUIRE(ctx, outs && seqs && L >= 1, "pipeline_bootstrap: null result or no lane");
   VO_REQUIRE(ctx, c.tracker_mode == 0, "pipeline_bootstrap: KLT tracker mode only (the descriptor modes match descriptors)");
-  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_bootstrap: bad sequence index");
+  VO_REQUIRE(ctx, L <= p->S, "pipeline_bootstrap: %d lanes named, the pipeline has %d", L, p->S);
+  for (int k = 0; k < L; ++k) {
+    VO_REQUIRE(ctx, seqs[k] >= 0 && seqs[k] < p->S, "pipeline_bootstrap: bad sequence index %d", (int)seqs[k]);
+    for (int j = 0; j < k; ++j) VO_REQUIRE(ctx, seqs[j] != seqs[k], "pipeline_bootstrap: sequence %d is named twice", (int)seqs[k]);
+  }
   VO_REQUIRE(ctx, idx_a >= 0 && idx_a < c.n_frames && idx_b >= 0 && idx_b < c.n_frames, "pipeline_bootstrap: bad frame index");
   VO_REQUIRE(ctx, idx_a != idx_b, "pipeline_bootstrap: the two frames are the same slot %d", idx_a);
   VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_bootstrap: %d submitted step(s) not collected", p->n_flight);
-  // a running pipeline: the lane is restarted (vo_pipeline_restart_seq's rules); else this is a hand-over (_set_state_seq's)
+  // a running pipeline: the lanes are restarted (vo_pipeline_restart_seq's rules); else this is a hand-over (_set_state_seq's)
   const bool restart = p->have_state && p->primed;
   if (restart) {
     VO_REQUIRE(ctx, p->seeded, "pipeline_bootstrap: seed the pipeline first");
@@ -227,8 +282,8 @@ int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, con
                idx_b, p->prev_frame);
   } else {
     VO_REQUIRE(ctx, !(p->S > 1 && p->have_state && idx_b != p->prev_frame),
-               "pipeline_bootstrap: sequence %d is handed over for frame %d, the others of this hand-over for frame %d", seq,
-               idx_b, p->prev_frame);
+               "pipeline_bootstrap: sequence %d is handed over for frame %d, the others of this hand-over for frame %d",
+               (int)seqs[0], idx_b, p->prev_frame);
   }
   vo_bootstrap_params q;
   memset(&q, 0, sizeof(q));
@@ -244,6 +299,8 @@ int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, con
   const int64_t max_it = q.max_iterations > 0 ? q.max_iterations : 2000;
   VO_REQUIRE(ctx, max_corners <= p->cap, "pipeline_bootstrap: %d corners exceed the feature capacity %d", max_corners, p->cap);
   VO_REQUIRE(ctx, orat0 < 1.0 && conf < 1.0, "pipeline_bootstrap: outlier ratio and confidence must be below 1");
+  memset(outs, 0, sizeof(*outs) * (size_t)L);
+  std::vector<int32_t> code((size_t)L, VO_OK);
   VO_TRY(worker_idle(p));
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -254,133 +311,212 @@ int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, con
   }
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   const int64_t h2d0 = ctx->bytes_h2d, d2h0 = ctx->bytes_d2h;
-  int64_t d2h = 0;                       // this file's own copies (scalars; it uploads nothing itself)
+  int64_t h2d = 0, d2h = 0;              // this file's own copies (scalars)
   const int nl = vo_klt_num_levels(c.H, c.W, win, max_level);
-  VO_TRY(boot_workspace(p, vo_pyramid_bytes(c.H, c.W, nl)));
+  const size_t pyr_bytes = vo_pyramid_bytes(c.H, c.W, nl);
+  VO_TRY(boot_workspace(p, L, pyr_bytes));
   boot_ws& w = *p->boot;
-  const uint8_t *img_a = p->img(seq, idx_a), *img_b = p->img(seq, idx_b);
-
-  // 1. Shi-Tomasi corners of frame a
-  const float* d_xy = nullptr;
-  int32_t n0 = 0;
-  VO_TRY(vo_good_features_dev(ctx, img_a, c.H, c.W, nullptr, max_corners, quality, min_dist, block, &d_xy, &n0));
-  out->n_corners = n0;
-  out->bytes_d2h = ctx->bytes_d2h - d2h0;
-  if (n0 < 8) return vo_set_error(ctx, VO_ETRACKING, "pipeline_bootstrap: %d corners on frame %d, the 8-point algorithm needs 8", n0, idx_a);
-  if (n0 > p->cap) return vo_set_error(ctx, VO_ECAPACITY, "pipeline_bootstrap: %d corners exceed the feature capacity %d", n0, p->cap);
-
-  // 2. pyramids with the bootstrap's level count, LK a -> b, the survivors as float64 pairs
-  VO_TRY(vo_pyramid_build_batch_dev(ctx, img_a, 0, 1, c.H, c.W, nl, w.pyr[0], 0));
-  VO_TRY(vo_pyramid_build_batch_dev(ctx, img_b, 0, 1, c.H, c.W, nl, w.pyr[1], 0));
-  float* d_next = p->d_next + (size_t)seq * p->cap * 2;      // (the lane's tracker outputs: a step rewrites them)
-  uint8_t* d_status = p->d_status + (size_t)seq * p->cap;
-  float* d_err = p->d_err + (size_t)seq * p->cap;
-  VO_TRY(vo_klt_track_ndev(ctx, img_a, w.pyr[0], img_b, w.pyr[1], c.H, c.W, nl, d_xy, n0, nullptr, win, c.klt_max_iter, c.klt_eps,
-                           c.klt_min_eig, d_next, d_status, d_err));
-  hipLaunchKernelGGL(boot_gather_kernel, dim3(1), dim3(256), 0, st, d_xy, (const float*)d_next, (const uint8_t*)d_status,
-                     (const float*)d_err, (float)c.klt_err_threshold, (int)n0, w.p1, w.p2, w.cnt);
-  VO_TRY(vo_check_launch(ctx, "boot_gather_kernel"));
-  int32_t n = 0;
-  VO_HIP_TRY(ctx, mcpy(st, &n, w.cnt, 4, hipMemcpyDeviceToHost));
-  d2h += 4;
-  out->n_tracked = n;
-  out->bytes_d2h = ctx->bytes_d2h - d2h0 + d2h;
-  if (n < 8) return vo_set_error(ctx, VO_ETRACKING, "pipeline_bootstrap: %d of %d corners tracked, the 8-point algorithm needs 8", n, n0);
-
-  // 3. 8-point RANSAC: samples from the reference's generator on the host, hypotheses + counts on the device, the
-  //    sequential accept / adapt rule over the counts on the host (vo_ransac_replay), the accepted row unpacked on the device
-  const int words = vo_cdiv(n, 64);
-  vo_ransac_state rs;
-  rs.outlier_ratio = orat0;
-  rs.confidence = conf;
-  rs.max_iterations = max_it;
-  rs.s = 8;
-  rs.adaptive = 1;
-  {
-    const int64_t k0 = vo_ransac_num_iterations(conf, orat0, 8);
-    rs.n_iterations = k0 < max_it ? k0 : max_it;
-  }
-  vo_pcg64 gen;
-  vo_bootstrap_default_rng(&gen);
-  std::vector<int32_t> samples((size_t)BOOT_BATCH * 8), counts((size_t)BOOT_BATCH);
-  const std::vector<uint8_t> valid((size_t)BOOT_BATCH, 1);
-  int64_t n_done = 0;
-  int32_t best_count = -1, best_idx = -1;
-  int finished = 0;
-  for (int batch = 0; !finished; ++batch) {
-    vo_pcg64 spec = gen;                 // speculative copy: the generator moves by what the rule consumed
-    if (vo_rng_choice(&spec, n, 8, BOOT_BATCH, samples.data()) != VO_OK)
-      return vo_set_error(ctx, VO_EINVAL, "pipeline_bootstrap: cannot draw 8 of %d", n);
-    VO_TRY(vo_fundamental_hypotheses_dev(ctx, w.p1, w.p2, n, samples.data(), BOOT_BATCH, 1, 1, thr_px * thr_px, w.samples, w.Fhyp,
-                                         w.counts, w.masks, counts.data()));
-    const int32_t before = best_idx;
-    int consumed = 0;
-    if (vo_ransac_replay(&rs, valid.data(), counts.data(), BOOT_BATCH, n, &n_done, &best_count, &best_idx, batch * BOOT_BATCH,
-                         &consumed, &finished) != VO_OK)
-      return vo_set_error(ctx, VO_EINVAL, "pipeline_bootstrap: vo_ransac_replay failed");
-    if (best_idx != before) {
-      const int row = best_idx - batch * BOOT_BATCH;       // 0 .. BOOT_BATCH - 1: an index of this batch
-      hipLaunchKernelGGL(boot_unpack_mask_kernel, dim3(vo_cdiv(n, 256)), dim3(256), 0, st,
-                         (const unsigned long long*)w.masks + (size_t)row * words, (int)n, w.inl);
-      VO_TRY(vo_check_launch(ctx, "boot_unpack_mask_kernel"));
+  const size_t cap = (size_t)p->cap;
+  // the first failure's text is the call's (the lane named in it); every lane's code goes to status[]
+  int first_fail = -1;
+  char first_msg[sizeof(ctx->err)] = {0};
+  auto fail = [&](int k, int rc) {
+    code[(size_t)k] = rc;
+    if (first_fail < 0) {
+      first_fail = k;
+      snprintf(first_msg, sizeof(first_msg), "%s", ctx->err);
     }
-    vo_rng_choice(&gen, n, 8, consumed, samples.data());
-  }
-  out->ransac_iterations = n_done;
-  out->n_ransac_inliers = best_count < 0 ? 0 : best_count;
-  out->bytes_h2d = ctx->bytes_h2d - h2d0;
-  out->bytes_d2h = ctx->bytes_d2h - d2h0 + d2h;
-  if (best_idx < 0 || best_count < 8)
-    return vo_set_error(ctx, VO_ETRACKING, "pipeline_bootstrap: RANSAC found no model with 8 inliers among %d correspondences (best: %d)",
-                        n, (int)best_count);
-  VO_TRY(vo_fundamental_fit_dev(ctx, w.p1, w.p2, n, w.inl, 1, w.F, nullptr));
-  const double* K = p->cams[(size_t)seq].K;
-  VO_TRY(vo_relative_pose_dev(ctx, w.p1, w.p2, n, w.inl, K, K, w.F, w.F + 16, w.X, w.mask, nullptr));
+  };
 
-  // 4. + 5. the lane's Features block and control block
-  boot_apply_args a;
-  a.n = n;
-  a.num_features = n0;
-  a.keep_ransac = (!restart && p->seq_state[seq] != 0) ? 1 : 0;
-  a.keep_raw_pos = (restart || rng) ? 0 : 1;
-  a.raw_pos = p->gen_upto[seq];
-  a.outlier_ratio = c.ransac_outlier_ratio;        // RANSAC.__init__ (ransac.py:47-56), as upload_state writes it
+  // 1. Shi-Tomasi corners of frame a, lane by lane (its rounds are separated by a launch-wide barrier that needs all its
+  //    workgroups resident: no lane dimension); the result moves from the context's workspace to the lane's block
+  int n0_max = 0;
+  for (int k = 0; k < L; ++k) {
+    const float* d_xy = nullptr;
+    int32_t n0 = 0;
+    VO_TRY(vo_good_features_dev(ctx, p->img(seqs[k], idx_a), c.H, c.W, nullptr, max_corners, quality, min_dist, block, &d_xy, &n0));
+    outs[k].n_corners = n0;
+    if (n0 < 8)
+      fail(k, vo_set_error(ctx, VO_ETRACKING, "pipeline_bootstrap: %d corners on frame %d of sequence %d, the 8-point algorithm needs 8",
+                           n0, idx_a, (int)seqs[k]));
+    else if (n0 > p->cap)
+      fail(k, vo_set_error(ctx, VO_ECAPACITY, "pipeline_bootstrap: %d corners of sequence %d exceed the feature capacity %d", n0,
+                           (int)seqs[k], p->cap));
+    const int live = code[(size_t)k] == VO_OK ? n0 : 0;
+    hipLaunchKernelGGL(boot_corners_kernel, dim3(std::max(1, vo_cdiv(2 * live, 256))), dim3(256), 0, st, d_xy, live, live,
+                       w.xy + (size_t)k * cap * 2, w.cnt + 4 * k);
+    VO_TRY(vo_check_launch(ctx, "boot_corners_kernel"));
+    n0_max = std::max(n0_max, live);
+  }
+
+  vo_f8_lanes ln;
+  ln.L = L;
+  ln.pts = cap * 2;
+  ln.inl = cap;
+  ln.F = 32;
+  ln.n = 4;
+  std::vector<vo_f8_result> rs((size_t)L);
+  std::vector<vo_pcg64> gens((size_t)L);
+  if (n0_max > 0) {
+    // 2. pyramids with the bootstrap's level count (one launch per run of consecutive lanes), LK a -> b for all lanes, the
+    //    survivors as float64 pairs
+    for (int k = 0; k < L;) {
+      int run = 1;
+      while (k + run < L && seqs[k + run] == seqs[k] + run) ++run;
+      VO_TRY(vo_pyramid_build_batch_dev(ctx, p->img(seqs[k], idx_a), p->img_stride(), run, c.H, c.W, nl, w.pyr[0] + (size_t)k * pyr_bytes, pyr_bytes));
+      VO_TRY(vo_pyramid_build_batch_dev(ctx, p->img(seqs[k], idx_b), p->img_stride(), run, c.H, c.W, nl, w.pyr[1] + (size_t)k * pyr_bytes, pyr_bytes));
+      k += run;
+    }
+    vo_klt_source src;                   // the lanes' corner counts are read on the device (no detector keypoints: frac = 0)
+    src.n = w.cnt;
+    src.num_features = w.cnt;
+    vo_klt_batch kb;
+    kb.S = L;
+    kb.pyr = pyr_bytes;
+    kb.xy = cap * 2;
+    kb.out = cap;
+    kb.ctl = 16;
+    VO_TRY(vo_klt_track_ndev(ctx, p->img(seqs[0], idx_a), w.pyr[0], p->img(seqs[0], idx_b), w.pyr[1], c.H, c.W, nl, w.xy, n0_max, nullptr,
+                             win, c.klt_max_iter, c.klt_eps, c.klt_min_eig, w.next, w.status, w.err, &src, &kb));
+    boot_lanes bl;
+    bl.xy = cap * 2;
+    bl.out = cap;
+    bl.pts = cap * 2;
+    hipLaunchKernelGGL(boot_gather_kernel, dim3(L), dim3(256), 0, st, (const float*)w.xy, (const float*)w.next,
+                       (const uint8_t*)w.status, (const float*)w.err, (float)c.klt_err_threshold, bl, w.p1, w.p2, w.cnt);
+    VO_TRY(vo_check_launch(ctx, "boot_gather_kernel"));
+
+    // 3. 8-point RANSAC on the device (sampler, hypotheses, scores, the accept / adapt rule), its closing fit, the relative
+    //    pose: grid x lanes.  The survivor counts never come to the host on their own: they arrive with the loops' control
+    //    blocks (one download for all lanes); a lane with fewer than 8 survivors leaves every kernel at once.
+    vo_f8_params fp;
+    fp.normalize_samples = 1;
+    fp.error_kind = 1;
+    fp.threshold = thr_px * thr_px;
+    fp.outlier_ratio = orat0;
+    fp.confidence = conf;
+    fp.max_iterations = max_it;
+    for (int k = 0; k < L; ++k) vo_bootstrap_default_rng(&gens[(size_t)k]);
+    VO_TRY(vo_fundamental_ransac_dev(ctx, w.p1, w.p2, p->cap, w.cnt + 1, nullptr, fp, gens.data(), w.inl, w.F, &ln, rs.data()));
+    std::vector<boot_apply_lane> al((size_t)L);
+    for (int k = 0; k < L; ++k) {
+      const int seq = seqs[k];
+      boot_apply_lane& a = al[(size_t)k];
+      memset(&a, 0, sizeof(a));
+      a.seq = seq;
+      a.keep_ransac = (!restart && p->seq_state[seq] != 0) ? 1 : 0;
+      a.keep_raw_pos = (restart || rngs) ? 0 : 1;
+      a.raw_pos = p->gen_upto[seq];
+    }
+    VO_HIP_TRY(ctx, hipMemcpyAsync(w.seq, seqs, (size_t)L * 4, hipMemcpyHostToDevice, st));
+    VO_HIP_TRY(ctx, hipMemcpyAsync(w.apply, al.data(), (size_t)L * sizeof(boot_apply_lane), hipMemcpyHostToDevice, st));
+    h2d += (int64_t)L * (4 + (int64_t)sizeof(boot_apply_lane));
+    VO_TRY(vo_relative_pose_lanes_dev(ctx, w.p1, w.p2, ln, w.inl, w.F, (const double*)p->d_cams, sizeof(vo_cam) / 8, w.seq, w.F + 16,
+                                      w.X, cap * 3, w.mask));
+
+    // 4. + 5. the lanes' Features blocks and control blocks (a lane without a model is left as it was)
+    boot_apply_args g;
+    g.outlier_ratio = c.ransac_outlier_ratio;        // RANSAC.__init__ (ransac.py:47-56), as upload_state writes it
+    {
+      const int64_t k0 = vo_ransac_num_iterations(c.ransac_confidence, c.ransac_outlier_ratio, 4);
+      g.n_iterations = (c.ransac_max_iterations >= 0 && c.ransac_max_iterations < k0) ? c.ransac_max_iterations : k0;
+    }
+    g.pts = cap * 2;
+    g.X = cap * 3;
+    g.F = 32;
+    g.mask = cap;
+    hipLaunchKernelGGL(bootstrap_apply_kernel, dim3(L), dim3(256), 0, st, g, (const boot_apply_lane*)w.apply,
+                       (const vo_f8_ctl*)ctx->f8_ctl.p, (const double*)w.p1, (const double*)w.p2, (const uint8_t*)w.mask,
+                       (const double*)w.X, (const double*)(w.F + 16), p->F[p->cur], p->d_ctl, w.cnt);
+    VO_TRY(vo_check_launch(ctx, "bootstrap_apply_kernel"));
+    std::vector<double> hF((size_t)L * 32);
+    std::vector<int32_t> hcnt((size_t)L * 4);
+    VO_HIP_TRY(ctx, hipMemcpyAsync(hF.data(), w.F, (size_t)L * 256, hipMemcpyDeviceToHost, st));
+    VO_HIP_TRY(ctx, mcpy(st, hcnt.data(), w.cnt, (size_t)L * 16, hipMemcpyDeviceToHost));
+    d2h += (int64_t)L * (256 + 16);
+    for (int k = 0; k < L; ++k) {
+      if (code[(size_t)k] != VO_OK) continue;
+      const vo_f8_result& r = rs[(size_t)k];
+      vo_bootstrap_result& o = outs[k];
+      o.n_tracked = r.n;
+      if (r.n < 8) {
+        fail(k, vo_set_error(ctx, VO_ETRACKING, "pipeline_bootstrap: %d of %d corners of sequence %d tracked, the 8-point algorithm needs 8",
+                             (int)r.n, (int)o.n_corners, (int)seqs[k]));
+        continue;
+      }
+      o.ransac_iterations = r.iterations;
+      o.n_ransac_inliers = r.best_count < 0 ? 0 : r.best_count;
+      o.reserved = r.finished_by_host;
+      if (r.status != VO_F8_DONE) {
+        fail(k, vo_set_error(ctx, VO_ETRACKING,
+                             "pipeline_bootstrap: RANSAC found no model with 8 inliers among %d correspondences of sequence %d (best: %d)",
+                             (int)r.n, (int)seqs[k], (int)r.best_count));
+        continue;
+      }
+      memcpy(o.M, hF.data() + (size_t)k * 32 + 16, 96);
+      o.n_landmarks = hcnt[(size_t)k * 4 + 2];
+      o.n_features = r.n;
+    }
+  }
+  // what crossed PCIe, divided among the call's lanes
   {
-    const int64_t k0 = vo_ransac_num_iterations(c.ransac_confidence, c.ransac_outlier_ratio, 4);
-    a.n_iterations = (c.ransac_max_iterations >= 0 && c.ransac_max_iterations < k0) ? c.ransac_max_iterations : k0;
+    const int64_t up = ctx->bytes_h2d - h2d0 + h2d, down = ctx->bytes_d2h - d2h0 + d2h;
+    for (int k = 0; k < L; ++k) {
+      outs[k].bytes_h2d = (up + L - 1) / L;
+      outs[k].bytes_d2h = (down + L - 1) / L;
+    }
   }
-  hipLaunchKernelGGL(bootstrap_apply_kernel, dim3(1), dim3(256), 0, st, a, (const double*)w.p1, (const double*)w.p2,
-                     (const uint8_t*)w.mask, (const double*)w.X, (const double*)(w.F + 16), vo_feat_seq(p->F[p->cur], (size_t)seq),
-                     p->d_ctl + seq, w.cnt + 1);
-  VO_TRY(vo_check_launch(ctx, "bootstrap_apply_kernel"));
-  int32_t n_land = 0;
-  VO_HIP_TRY(ctx, hipMemcpyAsync(out->M, w.F + 16, 96, hipMemcpyDeviceToHost, st));
-  VO_HIP_TRY(ctx, mcpy(st, &n_land, w.cnt + 1, 4, hipMemcpyDeviceToHost));
-  d2h += 100;
-  out->n_landmarks = n_land;
-  out->n_features = n;
-  out->bytes_h2d = ctx->bytes_h2d - h2d0;
-  out->bytes_d2h = ctx->bytes_d2h - d2h0 + d2h;
-  // host side of the hand-over (pipeline_state.hip: vo_pipeline_set_state_seq / vo_pipeline_restart_seq)
-  if (restart || rng) {
-    const vo_pcg64 g = rng ? *rng : p->seed_rng;
-    p->rng[seq] = g;
-    p->raw_gen[seq] = g;
-    p->pos_known[seq] = p->gen_upto[seq];
-    p->pos_dev[seq] = p->gen_upto[seq];
+  // host side of the hand-over (pipeline_state.hip: vo_pipeline_set_state_seq / vo_pipeline_restart_seq), lane by lane
+  bool any_ok = false;
+  for (int k = 0; k < L; ++k) {
+    if (status) status[k] = code[(size_t)k];
+    if (code[(size_t)k] != VO_OK) continue;
+    any_ok = true;
+    const int seq = seqs[k];
+    if (restart || rngs) {
+      const vo_pcg64 g = rngs ? rngs[k] : p->seed_rng;
+      p->rng[seq] = g;
+      p->raw_gen[seq] = g;
+      p->pos_known[seq] = p->gen_upto[seq];
+      p->pos_dev[seq] = p->gen_upto[seq];
+    }
+    p->idle[seq] = 0;
+    p->seq_state[seq] = 1;
   }
-  p->idle[seq] = 0;
-  p->seq_state[seq] = 1;
-  if (restart) {
-    p->prepared_idx = p->prepared_slot = -1;
-    VO_TRY(prime(p, true, seq, 1));
-  } else {
-    p->slot = 0;
-    p->prev_frame = idx_b;
-    p->have_state = true;
-    p->primed = false;
+  if (any_ok) {
+    if (restart) {
+      p->prepared_idx = p->prepared_slot = -1;
+      for (int k = 0; k < L;) {          // frame b's pyramid + detection, one call per run of consecutive restarted lanes
+        if (code[(size_t)k] != VO_OK) {
+          ++k;
+          continue;
+        }
+        int run = 1;
+        while (k + run < L && code[(size_t)(k + run)] == VO_OK && seqs[k + run] == seqs[k] + run) ++run;
+        VO_TRY(prime(p, true, seqs[k], run));
+        k += run;
+      }
+    } else {
+      p->slot = 0;
+      p->prev_frame = idx_b;
+      p->have_state = true;
+      p->primed = false;
+    }
+  }
+  if (first_fail >= 0) {
+    snprintf(ctx->err, sizeof(ctx->err), "%s", first_msg);
+    return code[(size_t)first_fail];
   }
   return VO_OK;
+}
+
+int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, const vo_bootstrap_params* prm,
+                              const vo_pcg64* rng, vo_bootstrap_result* out) {
+  if (!p) return VO_EINVAL;
+  VO_REQUIRE(p->ctx, out, "pipeline_bootstrap: null result");
+  memset(out, 0, sizeof(*out));
+  const int32_t s = seq;
+  return vo_pipeline_bootstrap_lanes(p, 1, &s, idx_a, idx_b, prm, rng, out, nullptr);
 }
 
 int vo_pipeline_bootstrap(vo_pipeline* p, int idx_a, int idx_b, const vo_bootstrap_params* prm, vo_bootstrap_result* out) {

@@ -9,6 +9,7 @@
 // Pure host code (no device work); compiled into libvo_hip.so.
 #include <cmath>
 
+#include "rng_device.h"
 #include "vo_internal.h"
 
 namespace {
@@ -179,6 +180,19 @@ int vo_rng_choice(vo_pcg64* rng, int pop, int s, int count, int32_t* out) {
     for (int k = 0; k < s; ++k) out[(size_t)c * s + k] = (int32_t)idx[k];
   }
   store(g, rng);
+  return VO_OK;
+}
+
+// One Generator.choice(pop, 8, replace=False) from the 15 generator outputs it consumes when no draw is rejected: the
+// function the raw-reading hypothesis kernel runs (rng_device.h), here so that a CPU test can hold it to NumPy.
+int vo_rng_choice8_from_raw(const uint32_t* raw, int pop, int32_t* out, int* possibly_rejected) {
+  if (!raw || !out || !possibly_rejected) return VO_EINVAL;
+  if (pop < 9) return VO_EINVAL;         // not covered: at pop = 8 the first Floyd draw consumes no output (14 per sample)
+  uint32_t r[vo_rng::CHOICE8_RAWS];
+  for (int k = 0; k < vo_rng::CHOICE8_RAWS; ++k) r[k] = raw[k];
+  int32_t v[8];
+  *possibly_rejected = vo_rng::choice8_from_raw(r, (uint32_t)pop, v) ? 1 : 0;
+  for (int k = 0; k < 8; ++k) out[k] = v[k];
   return VO_OK;
 }
 

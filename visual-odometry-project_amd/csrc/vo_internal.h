@@ -70,6 +70,11 @@ struct vo_ctx {
   // bytes the device-resident forms of the bootstrap stages (vo_good_features_dev, vo_fundamental_*_dev) copied between
   // host and device: scalars and the RANSAC batch's samples / counts; vo_pipeline_bootstrap_seq reports the difference
   int64_t bytes_h2d = 0, bytes_d2h = 0;
+  // the device 8-point RANSAC's workspace (bootstrap.hip: vo_fundamental_ransac_dev), grown to the largest lane count and
+  // population seen; the threshold table goes up when the confidence or the budget change, not per call
+  vo_buf f8_ctl, f8_raws, f8_F, f8_counts, f8_risky, f8_masks, f8_table, f8_samples;
+  std::vector<double> f8_table_host;
+  double f8_table_conf = 0.0;
 };
 
 // a launch that takes vo_ctx::next_stop as its stop event when one is set (and clears it)
@@ -208,6 +213,48 @@ int vo_relative_pose_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, in
                          const double* K2, const double* d_F, double* d_M, double* d_X, uint8_t* d_mask_out, double* d_M4);
 // the next `count` 32-bit outputs of NumPy's PCG64 Generator (ransac_host.hip); advances *rng
 void vo_rng_raw32(vo_pcg64* rng, int count, uint32_t* out);
+// The 8-point RANSAC loop of the two-view bootstrap on the device (bootstrap.hip): sampler, hypotheses, scores and the
+// sequential accept / adapt rule, for L lanes through one set of launches.
+enum { VO_F8_RUN = 0,       // the loop wants a (another) batch of samples
+       VO_F8_DONE = 1,      // the loop has ended with a model of >= 8 inliers; its mask is unpacked
+       VO_F8_HOST = 2,      // the device cannot finish it: a draw NumPy might have rejected inside the consumed prefix, a
+                            // population of 8, a budget the threshold table does not hold -- the host sampler redoes it
+       VO_F8_FAILED = 3 };  // fewer than 8 correspondences, or no model with 8 inliers
+struct vo_f8_ctl {          // one lane's loop state in device memory
+  vo_pcg64 rng;             // where the loop starts
+  int32_t n;                // population; -1 on upload: read from the device count
+  int32_t status;
+  int32_t best_count, best_idx, consumed, batch;
+  int64_t n_done, n_it;
+  double orat;
+};
+struct vo_f8_lanes {        // lane q's blocks: p1 / p2 + q * pts, inliers + q * inl, F + q * F, its count at d_n[q * n]
+  int L = 1;
+  size_t pts = 0, inl = 0, F = 0;
+  int n = 0;
+};
+struct vo_f8_params {
+  int normalize_samples, error_kind;
+  double threshold, outlier_ratio, confidence;
+  int64_t max_iterations;   // < 0: unbounded
+};
+struct vo_f8_result {
+  int32_t status;           // VO_F8_DONE or VO_F8_FAILED
+  int32_t n, best_count, consumed, finished_by_host;
+  int64_t iterations;
+};
+// d_p1 / d_p2: n_cap pairs per lane; the populations from d_n (device) or n_host (d_n == NULL).  rngs[q]: where lane q's
+// loop starts, advanced by what it consumed.  d_inl: n_cap bytes per lane (the accepted model's inliers); d_F: the closing
+// fit over them (9 doubles per lane).  Synchronises: res[q] is complete when it returns.
+int vo_fundamental_ransac_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int n_cap, const int32_t* d_n,
+                              const int32_t* n_host, const vo_f8_params& prm, vo_pcg64* rngs, uint8_t* d_inl, double* d_F,
+                              const vo_f8_lanes* lanes, vo_f8_result* res);
+// The relative pose of every lane vo_fundamental_ransac_dev just finished (status VO_F8_DONE in the context's control blocks;
+// the others are skipped): lane q's points, inliers and F as above, its camera K at d_cam + d_seq[q] * cam_stride (doubles)
+// for both views; M (12 doubles) at d_M + q * lanes.F, X (n x 3) at d_X + q * X_stride, mask at d_mask_out + q * lanes.inl.
+int vo_relative_pose_lanes_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, const vo_f8_lanes& lanes, const uint8_t* d_inl,
+                               const double* d_F, const double* d_cam, size_t cam_stride, const int32_t* d_seq, double* d_M,
+                               double* d_X, size_t X_stride, uint8_t* d_mask_out);
 // DLT with a device-resident point count (dlt.hip)
 int vo_triangulate_dlt_ndev(vo_ctx* ctx, const double* d_x1, const double* d_x2, const int32_t* d_n, int n_cap,
                             const double* d_C1, const double* d_C2, double* d_X);

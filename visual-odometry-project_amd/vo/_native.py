@@ -111,6 +111,8 @@ class BootstrapResult(C.Structure):
                 ("ransac_iterations", C.c_int64), ("M", C.c_double * 12), ("bytes_h2d", C.c_int64),
                 ("bytes_d2h", C.c_int64)]
 
+    seq, status = 0, 0          # Pipeline.bootstrap_lanes: the lane and its VO_E* code (0 = bootstrapped)
+
     def relative_pose(self):
         """M: camera a -> camera b, (3, 4), |t| = 1."""
         return np.array(self.M).reshape(3, 4)
@@ -173,6 +175,9 @@ _SIGS = {
     "vo_harris_subpix_corners": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "vo_fundamental_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
     "vo_fundamental_fit": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "vo_fundamental_ransac": (_i, [_vp, _vp, _vp, _i, _i, _i, _d, _d, _d, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_rng_raw32_device": (_i, [_vp, _vp, _i, _vp]),
+    "vo_rng_choice8_from_raw": (_i, [_vp, _i, _vp, _vp]),
     "vo_essential_decompose": (_i, [_vp, _vp, _vp]),
     "vo_relative_pose": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_comm_unique_id": (_i, [_vp, _vp]),
@@ -228,6 +233,7 @@ _SIGS = {
     "vo_pipeline_restart_seq": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "vo_pipeline_bootstrap_seq": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "vo_pipeline_bootstrap": (_i, [_vp, _i, _i, _vp, _vp]),
+    "vo_pipeline_bootstrap_lanes": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "vo_bootstrap_default_rng": (None, [_vp]),
 }
 
@@ -621,6 +627,34 @@ class Context:
         self._chk(self._lib.vo_fundamental_fit(self._h, _ptr(p1), _ptr(p2), p1.shape[0], _ptr(m), int(bool(normalize)), _ptr(F)))
         return F
 
+    def fundamental_ransac(self, p1, p2, threshold, rng, normalize_samples=False, error_kind=0, outlier_ratio=0.9,
+                           confidence=0.999, max_iterations=2000):
+        """The 8-point RANSAC loop and its closing fit in one call, sampler and accept / adapt rule on the device
+        (vo_fundamental_ransac): (F (3, 3), inlier mask (N,) bool, info) with info = {"iterations", "best_count",
+        "finished_by_host"}.  rng: a Pcg64 (advanced in place by what the loop consumed) or a NumPy Generator (likewise).
+        max_iterations: None / np.inf = unbounded (the host sampler's loop)."""
+        p1 = _c(np.asarray(p1).reshape(-1, 2), np.float64)
+        p2 = _c(np.asarray(p2).reshape(-1, 2), np.float64)
+        n = p1.shape[0]
+        pcg = rng if isinstance(rng, Pcg64) else Pcg64.from_generator(rng)
+        budget = -1 if max_iterations is None or max_iterations == np.inf else int(max_iterations)
+        F = np.empty((3, 3), np.float64)
+        mask = np.zeros(n, np.uint8)
+        it, best, host = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.vo_fundamental_ransac(self._h, _ptr(p1), _ptr(p2), n, int(bool(normalize_samples)), int(error_kind),
+                                                  float(threshold), float(outlier_ratio), float(confidence), budget,
+                                                  C.byref(pcg), _ptr(F), _ptr(mask), C.byref(it), C.byref(best), C.byref(host)))
+        if not isinstance(rng, Pcg64):
+            pcg.to_generator(rng)
+        return F, mask.astype(bool), {"iterations": int(it.value), "best_count": int(best.value),
+                                      "finished_by_host": int(host.value)}
+
+    def rng_raw32_device(self, pcg, count):
+        """The next `count` 32-bit outputs of `pcg` (a Pcg64, advanced in place) made by the device's fill kernel."""
+        out = np.empty(int(count), np.uint32)
+        self._chk(self._lib.vo_rng_raw32_device(self._h, C.byref(pcg), int(count), _ptr(out)))
+        return out
+
     def essential_decompose(self, E):
         E = _c(np.asarray(E).reshape(3, 3), np.float64)
         M4 = np.empty((4, 3, 4), np.float64)
@@ -788,6 +822,18 @@ def rng_choice(pcg, pop, s, count):
     if rc != VO_OK:
         raise VoError(rc, "vo_rng_choice(pop=%d, s=%d)" % (pop, s))
     return out
+
+
+def rng_choice8_from_raw(raw, pop):
+    """One Generator.choice(pop, 8, replace=False) from the 15 generator outputs it consumes when no draw is rejected:
+    (sample (8,) int32, possibly_rejected).  pop >= 9 (host only)."""
+    raw = _c(np.asarray(raw).reshape(15), np.uint32)
+    out = np.empty(8, np.int32)
+    flag = C.c_int(0)
+    rc = load().vo_rng_choice8_from_raw(_ptr(raw), int(pop), _ptr(out), C.byref(flag))
+    if rc != VO_OK:
+        raise VoError(rc, "vo_rng_choice8_from_raw(pop=%d)" % pop)
+    return out, int(flag.value)
 
 
 def ransac_num_iterations(confidence, outlier_ratio, s):

@@ -192,6 +192,34 @@ class Pipeline:
                                                               C.byref(pcg) if pcg is not None else None, C.byref(res)))
         return res
 
+    def bootstrap_lanes(self, idx_a, idx_b, seqs, generators=None, max_corners=0, quality=0.0, min_distance=0.0, block=0,
+                        klt_win=0, klt_max_level=None, threshold_px=0.0, outlier_ratio=0.0, confidence=0.0, max_iterations=0):
+        """The two-view bootstrap of the lanes `seqs` (distinct) through one set of launches (vo_pipeline_bootstrap_lanes):
+        every lane ends as bootstrap(idx_a, idx_b, seq=q, generator=generators[i], ...) would leave it.  generators: None or
+        one NumPy Generator per lane.  Returns a list of BootstrapResult, one per lane, each with `.seq` and `.status` (0, or
+        the VO_E* code of a lane that failed and was left as it was); raises VoError only for a refused call."""
+        from vo import _native
+        seqs = [int(q) for q in seqs]
+        n = len(seqs)
+        prm = _native.BootstrapParams(int(max_corners), float(quality), float(min_distance), int(block), int(klt_win),
+                                      -1 if klt_max_level is None else int(klt_max_level), float(threshold_px),
+                                      float(outlier_ratio), float(confidence), int(max_iterations), 0)
+        if generators is not None and len(generators) != n:
+            raise ValueError("bootstrap_lanes: %d generators for %d lanes" % (len(generators), n))
+        pcgs = None if generators is None else (_native.Pcg64 * n)(*[_native.Pcg64.from_generator(g) for g in generators])
+        res = (_native.BootstrapResult * max(n, 1))()
+        status = (C.c_int32 * max(n, 1))()
+        rc = self.ctx._lib.vo_pipeline_bootstrap_lanes(self._h, n, (C.c_int32 * max(n, 1))(*seqs), int(idx_a), int(idx_b),
+                                                       C.byref(prm), pcgs, res, status)
+        if rc != 0 and all(status[k] == 0 for k in range(n)):       # refused: no lane was touched
+            self.ctx._chk(rc)
+        out = []
+        for k in range(n):
+            r = _native.BootstrapResult.from_buffer_copy(res[k])
+            r.seq, r.status = seqs[k], int(status[k])
+            out.append(r)
+        return out
+
     def checkpoint(self):
         """Keeps a copy of every sequence's Features / State as they are now (nothing in flight) in HBM."""
         self.ctx._chk(self.ctx._lib.vo_pipeline_checkpoint(self._h))

@@ -333,9 +333,10 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     goes idle (vo_pipeline_set_active_seq) -- lane_schedule says when.  Frames go through one pinned ring per lane,
     uploaded a step ahead.  The steps in flight are drained before a lane changes recording (nothing may be in flight for
     the three calls), so each such step loses the look-ahead once.  All recordings must have the same frame size.
-    bootstrap="device": a lane's recording starts from its frames 0 and 2 inside the pipeline instead (Pipeline.bootstrap):
-    for a change of recording the lane goes idle, frame 0 goes into the slot after the current one and frame 2 into the
-    current one, then one call.  (A recording without a steady-state step never holds a lane: host route.)
+    bootstrap="device": a lane's recording starts from its frames 0 and 2 inside the pipeline instead: for a change of
+    recording the lane goes idle, frame 0 goes into the slot after the current one and frame 2 into the current one; the
+    lanes that start at the same step (all of them at step 0) then go through ONE call (Pipeline.bootstrap_lanes).  (A
+    recording without a steady-state step never holds a lane: host route.)
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
     each step the recording took part in).  Each lane computes what run_on_device computes for its recording alone."""
@@ -394,22 +395,26 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
             ring[lane][s][...] = _gray(next_frame(r).image)
             pipe.set_frame(s, ring[lane][s], seq=lane, pinned=True)
 
-        def start_on_device(lane, r, t, slot):
-            img0, img2 = _bootstrap_frames(sequences[r])
-            pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
-            if t > 0:
-                pipe.set_active(lane, False)             # (the lane's frame in the current slot can only be replaced while idle)
-            a = (slot + 1) % SLOTS                       # (the slot the recording's next frame takes afterwards)
-            pipe.set_frame(a, img0, seq=lane, pinned=False)
-            pipe.set_frame(slot, img2, seq=lane, pinned=False)
-            res = pipe.bootstrap(a, slot, seq=lane, **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
-                                                                        bootstrap_max_level, bootstrap_threshold))
-            out[r] = dict(trajectory=[np.eye(4), pipe.get_state(lane)["curr_pose"]], n_landmarks=[res.n_landmarks],
-                          frame_seconds=[], results=[], features=None)
+        def start_on_device(starts, t, slot):
+            """The lanes that start a recording at this step -- starts: (lane, recording) -- through ONE bootstrap call."""
+            a = (slot + 1) % SLOTS                       # (the slot the recordings' next frames take afterwards)
+            for lane, r in starts:
+                img0, img2 = _bootstrap_frames(sequences[r])
+                pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
+                if t > 0:
+                    pipe.set_active(lane, False)         # (the lane's frame in the current slot can only be replaced while idle)
+                pipe.set_frame(a, img0, seq=lane, pinned=False)
+                pipe.set_frame(slot, img2, seq=lane, pinned=False)
+            results = pipe.bootstrap_lanes(a, slot, [lane for lane, _ in starts],
+                                           **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
+                                                               bootstrap_max_level, bootstrap_threshold))
+            for (lane, r), res in zip(starts, results):
+                if res.status != 0:
+                    raise _native.VoError(res.status, "the bootstrap of recording %d (lane %d) failed" % (r, lane))
+                out[r] = dict(trajectory=[np.eye(4), pipe.get_state(lane)["curr_pose"]], n_landmarks=[res.n_landmarks],
+                              frame_seconds=[], results=[], features=None)
 
         def start(lane, r, t, slot):
-            if on_device:
-                return start_on_device(lane, r, t, slot)
             state, tracker = boot_of(r)
             open_result(r)
             frame = state.curr_frame
@@ -443,11 +448,23 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
         for t, lane in plan["idles"]:
             events.setdefault(t, []).append((lane, None))
         slot = 0
-        for lane, r in sorted(events.pop(0, [])):
-            if r is None:
-                pipe.set_active(lane, False)
-            else:
-                start(lane, r, 0, slot)
+
+        def change(t, slot):
+            """Step t's events: lanes going idle, lanes starting a recording (the host route one by one, the device route
+            all of them in one call)."""
+            starts = [(lane, r) for lane, r in sorted(events[t]) if r is not None]
+            for lane, r in sorted(events[t]):
+                if r is None:
+                    pipe.set_active(lane, False)
+                elif not on_device:
+                    start(lane, r, t, slot)
+            if on_device and starts:
+                start_on_device(starts, t, slot)
+            return starts
+
+        if 0 in events:
+            change(0, slot)
+            del events[0]
         for lane, e in enumerate(steps[0]):
             if e is not None:
                 put(lane, 1, e[0])
@@ -461,11 +478,8 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                     prev = steps[t - 1][lane]
                     if prev is not None:
                         finish(lane, prev[0])
-                    if r is None:
-                        pipe.set_active(lane, False)
-                    else:
-                        start(lane, r, t, slot)
-                        put(lane, (slot + 1) % SLOTS, r)
+                for lane, r in change(t, slot):
+                    put(lane, (slot + 1) % SLOTS, r)
             t0 = time.perf_counter()
             nxt = (slot + 1) % SLOTS
             if len(pending) == 2:
