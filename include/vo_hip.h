@@ -265,6 +265,27 @@ int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_
                      int max_corners, double quality, double min_dist, int block, float* xy,
                      int32_t* n);
 int vo_min_eigen_map(vo_ctx* ctx, const uint8_t* img, int H, int W, int block, float* eig);
+/* S images of one size per set of launches [ref: src/vo/features/klt.py:98, one call per
+ * image there].  Image q's corners are those of vo_good_features on image q alone, bit for
+ * bit and in order.  The _dev form enqueues a fixed launch sequence on the context's stream
+ * and neither synchronises nor reads anything back: image q at d_imgs + q * img_stride, its
+ * mask at d_masks + q * mask_stride (d_masks NULL: none), its corners at d_xy + q *
+ * xy_stride * 2 (xy_stride rows, at least vo_good_features_capacity(H, W, max_corners)),
+ * their number in d_n[q].  d_over[q] (nullable): 0 ok, 1 the local maxima exceed the
+ * candidate capacity (H*W/4 + 64), 2 the minimum-distance walk's cell slots overflowed; when
+ * it is non-zero d_n[q] = 0 and nothing of image q is written, the other images are as
+ * without it.  d_info (nullable) receives four words per image: candidates, path (0 the
+ * parallel rounds, 1 the one-workgroup walk, 2 min_dist < 1: the sorted list's head), round
+ * launches used, reserved.  vo_good_features_batch uploads, calls the _dev form and
+ * downloads (xy: S blocks of capacity rows); a non-zero d_over[q] is VO_ECAPACITY naming q.
+ * Argument rules as for vo_good_features; a refused call leaves the context usable.        */
+int vo_good_features_capacity(int H, int W, int max_corners);
+int vo_good_features_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                               const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
+                               double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n,
+                               int32_t* d_over, int32_t* d_info);
+int vo_good_features_batch(vo_ctx* ctx, const uint8_t* imgs, const uint8_t* masks, int S, int H, int W,
+                           int max_corners, double quality, double min_dist, int block, float* xy, int32_t* n);
 
 /* ---- SIFT ---------------------------------------------------------------------------
  * [ref: src/vo/features/sift.py:10,17]  cv2.SIFT_create().detectAndCompute(image, None)
@@ -669,7 +690,7 @@ int vo_pipeline_restart_seq(vo_pipeline* p, int seq, int idx, int n, const doubl
  * A sequence enters the pipeline from two frames of its frame store instead of from finished Features arrays: what
  * vo.driver.bootstrap computes on the host [ref: src/main.py:204-230] for frames idx_a, idx_b of sequence seq, followed by
  * the hand-over vo_pipeline_set_state_seq / vo_pipeline_restart_seq make with its result.  KLT tracker mode.
- *   1. Shi-Tomasi corners of frame a (vo_good_features' kernels) [ref: src/vo/features/klt.py:24-26, 98];
+ *   1. Shi-Tomasi corners of frame a (vo_good_features_batch_dev) [ref: src/vo/features/klt.py:24-26, 98];
  *      num_features = their count [ref: klt.py:114];
  *   2. pyramids of a and b with the bootstrap's own window / level count, LK a -> b, keep status & err <
  *      klt_err_threshold [ref: klt.py:233-262]; the identity-pair Matches regroup of fresh Features keeps the survivors
@@ -719,7 +740,7 @@ int vo_pipeline_bootstrap_seq(vo_pipeline* p, int seq, int idx_a, int idx_b, con
                               const vo_pcg64* rng, vo_bootstrap_result* out);
 int vo_pipeline_bootstrap(vo_pipeline* p, int idx_a, int idx_b, const vo_bootstrap_params* prm, vo_bootstrap_result* out);
 /* Several lanes in one call: lanes seqs[0 .. n_lanes-1] (in range, distinct) go through ONE set of launches -- the lane is a
- * grid dimension of every stage but Shi-Tomasi -- and each ends exactly as if vo_pipeline_bootstrap_seq(p, seqs[i], idx_a,
+ * grid dimension of every stage, Shi-Tomasi included -- and each ends exactly as if vo_pipeline_bootstrap_seq(p, seqs[i], idx_a,
  * idx_b, prm, rngs ? &rngs[i] : NULL, &outs[i]) had been called for it alone, in the order given.  The call-level rules are
  * the one-lane call's; a refused call (VO_EINVAL) changes nothing.  A lane that FAILS (VO_ETRACKING: fewer than 8 corners or
  * survivors, no model with 8 inliers; VO_ECAPACITY) gets its code in status[i] (nullable) and stays as it was, the other

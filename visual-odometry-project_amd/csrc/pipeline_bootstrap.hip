@@ -3,9 +3,10 @@
 //
 // The stages are the kernels the host route (vo/driver.py: bootstrap) calls one ABI call at a time -- Shi-Tomasi corners,
 // pyramids + LK, the 8-point RANSAC loop with its closing fit, relative pose -- in their device-resident forms, with the
-// lane as a grid dimension everywhere but in Shi-Tomasi; the bookkeeping between them, NumPy on the host route, is three
-// small kernels here:
-//   boot_corners_kernel     a lane's corners from the context's workspace into the lane's block, with their count
+// lane as a grid dimension of every stage (Shi-Tomasi: vo_good_features_batch_dev, straight into the lanes' blocks); the
+// bookkeeping between them, NumPy on the host route, is three small kernels here:
+//   boot_corners_kernel     the lanes' corner counts as the following stages read them (a lane with fewer than 8
+//                           corners, or whose detection failed, sits out)
 //   boot_gather_kernel      klt.py:244-262 + matches.py:26-212 for fresh Features and identity pairs: the survivors of
 //                           status & err < thr, in order, as the float64 (n, 2) pairs the bootstrap kernels read.  The
 //                           fresh frame-a Features block is never materialised: all its fields are constants (state 0,
@@ -28,16 +29,17 @@ struct boot_lanes {
   size_t pts;       // doubles between their p1 / p2 arrays
 };
 
-// the corners Shi-Tomasi left in the context's workspace -> the lane's block, with their count (0: the lane sits out)
-__global__ __launch_bounds__(256) void boot_corners_kernel(const float* __restrict__ src, int n0, int n_live,
-                                                           float* __restrict__ dst, int32_t* __restrict__ cnt) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < 2 * n0) dst[i] = src[i];
-  if (i == 0) {
-    cnt[0] = n_live;
-    cnt[1] = 0;
-    cnt[2] = 0;
-  }
+// Shi-Tomasi's counts -> the lanes' count blocks.  cnt: four ints per lane -- [0] corners the following stages work on (0:
+// the lane sits out), [3] what the host is told with the result: the corners found, or -d_over when the detection failed
+__global__ __launch_bounds__(64) void boot_corners_kernel(int L, int cap, const int32_t* __restrict__ n, const int32_t* __restrict__ over,
+                                                          int32_t* __restrict__ cnt) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= L) return;
+  const int n0 = n[k], ov = over[k];
+  cnt[4 * k] = (ov == 0 && n0 >= 8 && n0 <= cap) ? n0 : 0;
+  cnt[4 * k + 1] = 0;
+  cnt[4 * k + 2] = 0;
+  cnt[4 * k + 3] = ov ? -ov : n0;
 }
 
 // One workgroup per lane walks its n0 tracked corners in order, 256 at a time (ballot + prefix: the survivors keep their
@@ -204,7 +206,8 @@ struct vo_pipeline_boot {
   uint8_t* status = nullptr;
   double *p1 = nullptr, *p2 = nullptr, *X = nullptr, *F = nullptr;   // F: 32 doubles per lane, [0..8] F, [16..27] M
   uint8_t *inl = nullptr, *mask = nullptr;
-  int32_t *cnt = nullptr, *seq = nullptr;        // cnt: four ints per lane (corners, survivors, landmarks, spare)
+  int32_t *cnt = nullptr, *seq = nullptr;        // cnt: four ints per lane (corners, survivors, landmarks, corners found)
+  int32_t* gf = nullptr;                         // Shi-Tomasi's d_n [lanes], d_over [lanes]
   boot_apply_lane* apply = nullptr;
 };
 typedef vo_pipeline_boot boot_ws;
@@ -228,6 +231,7 @@ static int boot_workspace(vo_pipeline* p, int L, size_t pyr_bytes) {
     VO_TRY(dev_alloc(p, &w.mask, L * cap));
     VO_TRY(dev_alloc(p, &w.cnt, (size_t)L * 4));
     VO_TRY(dev_alloc(p, &w.seq, (size_t)L));
+    VO_TRY(dev_alloc(p, &w.gf, (size_t)L * 2));
     VO_TRY(dev_alloc(p, &w.apply, (size_t)L));
     w.lanes = L;
   }
@@ -328,26 +332,19 @@ int vo_pipeline_bootstrap_lanes(vo_pipeline* p, int n_lanes, const int32_t* seqs
     }
   };
 
-  // 1. Shi-Tomasi corners of frame a, lane by lane (its rounds are separated by a launch-wide barrier that needs all its
-  //    workgroups resident: no lane dimension); the result moves from the context's workspace to the lane's block
-  int n0_max = 0;
-  for (int k = 0; k < L; ++k) {
-    const float* d_xy = nullptr;
-    int32_t n0 = 0;
-    VO_TRY(vo_good_features_dev(ctx, p->img(seqs[k], idx_a), c.H, c.W, nullptr, max_corners, quality, min_dist, block, &d_xy, &n0));
-    outs[k].n_corners = n0;
-    if (n0 < 8)
-      fail(k, vo_set_error(ctx, VO_ETRACKING, "pipeline_bootstrap: %d corners on frame %d of sequence %d, the 8-point algorithm needs 8",
-                           n0, idx_a, (int)seqs[k]));
-    else if (n0 > p->cap)
-      fail(k, vo_set_error(ctx, VO_ECAPACITY, "pipeline_bootstrap: %d corners of sequence %d exceed the feature capacity %d", n0,
-                           (int)seqs[k], p->cap));
-    const int live = code[(size_t)k] == VO_OK ? n0 : 0;
-    hipLaunchKernelGGL(boot_corners_kernel, dim3(std::max(1, vo_cdiv(2 * live, 256))), dim3(256), 0, st, d_xy, live, live,
-                       w.xy + (size_t)k * cap * 2, w.cnt + 4 * k);
-    VO_TRY(vo_check_launch(ctx, "boot_corners_kernel"));
-    n0_max = std::max(n0_max, live);
+  // 1. Shi-Tomasi corners of frame a, straight into the lanes' blocks (one call per run of consecutive lanes); their counts
+  //    stay on the device and reach the host with the result's download
+  for (int k = 0; k < L;) {
+    int run = 1;
+    while (k + run < L && seqs[k + run] == seqs[k] + run) ++run;
+    VO_TRY(vo_good_features_batch_dev(ctx, p->img(seqs[k], idx_a), p->img_stride(), run, c.H, c.W, nullptr, 0, max_corners, quality,
+                                      min_dist, block, w.xy + (size_t)k * cap * 2, cap, w.gf + k, w.gf + L + k, nullptr));
+    k += run;
   }
+  hipLaunchKernelGGL(boot_corners_kernel, dim3(vo_cdiv(L, 64)), dim3(64), 0, st, L, p->cap, (const int32_t*)w.gf,
+                     (const int32_t*)(w.gf + L), w.cnt);
+  VO_TRY(vo_check_launch(ctx, "boot_corners_kernel"));
+  const int n0_max = max_corners;
 
   vo_f8_lanes ln;
   ln.L = L;
@@ -357,7 +354,7 @@ int vo_pipeline_bootstrap_lanes(vo_pipeline* p, int n_lanes, const int32_t* seqs
   ln.n = 4;
   std::vector<vo_f8_result> rs((size_t)L);
   std::vector<vo_pcg64> gens((size_t)L);
-  if (n0_max > 0) {
+  {
     // 2. pyramids with the bootstrap's level count (one launch per run of consecutive lanes), LK a -> b for all lanes, the
     //    survivors as float64 pairs
     for (int k = 0; k < L;) {
@@ -434,6 +431,23 @@ int vo_pipeline_bootstrap_lanes(vo_pipeline* p, int n_lanes, const int32_t* seqs
     VO_HIP_TRY(ctx, hipMemcpyAsync(hF.data(), w.F, (size_t)L * 256, hipMemcpyDeviceToHost, st));
     VO_HIP_TRY(ctx, mcpy(st, hcnt.data(), w.cnt, (size_t)L * 16, hipMemcpyDeviceToHost));
     d2h += (int64_t)L * (256 + 16);
+    for (int k = 0; k < L; ++k) {        // the corner stage's failures first: they are the earliest of the call
+      const int32_t found = hcnt[(size_t)k * 4 + 3];
+      const int n0 = found < 0 ? 0 : found;
+      outs[k].n_corners = n0;
+      if (found == -1)
+        fail(k, vo_set_error(ctx, VO_ECAPACITY, "pipeline_bootstrap: the local maxima on frame %d of sequence %d exceed Shi-Tomasi's candidate capacity",
+                             idx_a, (int)seqs[k]));
+      else if (found < 0)
+        fail(k, vo_set_error(ctx, VO_ECAPACITY, "pipeline_bootstrap: Shi-Tomasi's minimum-distance walk overflowed a grid cell on frame %d of sequence %d",
+                             idx_a, (int)seqs[k]));
+      else if (n0 < 8)
+        fail(k, vo_set_error(ctx, VO_ETRACKING, "pipeline_bootstrap: %d corners on frame %d of sequence %d, the 8-point algorithm needs 8",
+                             n0, idx_a, (int)seqs[k]));
+      else if (n0 > p->cap)
+        fail(k, vo_set_error(ctx, VO_ECAPACITY, "pipeline_bootstrap: %d corners of sequence %d exceed the feature capacity %d", n0,
+                             (int)seqs[k], p->cap));
+    }
     for (int k = 0; k < L; ++k) {
       if (code[(size_t)k] != VO_OK) continue;
       const vo_f8_result& r = rs[(size_t)k];

@@ -200,6 +200,15 @@ extern "C" int vo_patch_descriptors_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_i
 //   good_features: *d_xy_out (n float pairs) points into the context's workspace (scratch[7]) until its next call
 int vo_good_features_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const uint8_t* d_mask, int max_corners,
                          double quality, double min_dist, int block, const float** d_xy_out, int32_t* n_out);
+// vo_good_features_batch_dev (vo_hip.h) with the number of round launches (0 .. 24; the ABI call: 24) and the rounds path's
+// candidate limit (1 .. 131 072; the ABI call: 131 072) given.  Results never depend on either: an image the rounds do not
+// finish, or whose candidates exceed the limit, is finished by the one-workgroup walk.  Like the other extern "C" entry
+// points of this file it is exported by libvo_hip.so without being part of the C ABI of vo_hip.h (no stability promise):
+// tests/test_gpu_good_features_batch.py binds it by hand to reach both hand-overs to the walk.
+extern "C" int vo_good_features_batch_rounds_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                                                 const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
+                                                 double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n,
+                                                 int32_t* d_over, int32_t* d_info, int n_rounds, int cand_limit);
 //   hypotheses: samples (host, Hyp x 8, checked against N) are the only array uploaded; counts (host, Hyp) the only one
 //   downloaded; d_F Hyp x 9, d_counts Hyp, d_masks Hyp x cdiv(N, 64) words (nullable) are the caller's device buffers
 int vo_fundamental_hypotheses_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const int32_t* samples, int Hyp,

@@ -162,6 +162,9 @@ _SIGS = {
     "vo_knn2_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "vo_good_features": (_i, [_vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _vp, _vp]),
     "vo_min_eigen_map": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "vo_good_features_capacity": (_i, [_i, _i, _i]),
+    "vo_good_features_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _sz, _i, _d, _d, _i, _vp, _sz, _vp, _vp, _vp]),
+    "vo_good_features_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _i, _vp, _vp]),
     "vo_sift": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "vo_sift_capacity": (_i, [_i, _i]),
     "vo_sift_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -445,6 +448,51 @@ class Context:
         self._chk(self._lib.vo_good_features(self._h, _ptr(img), H, W, _ptr(m), int(max_corners), float(quality),
                                              float(min_distance), int(block_size), _ptr(xy), C.byref(n)))
         return xy[: n.value].copy()
+
+    def good_features_capacity(self, H, W, max_corners):
+        """Rows per image the outputs of the batched forms must hold (vo_good_features_capacity)."""
+        return int(self._lib.vo_good_features_capacity(int(H), int(W), int(max_corners)))
+
+    @staticmethod
+    def _image_stack(what, images, masks=None):
+        shapes = {np.shape(a) for a in images}
+        if len(shapes) != 1 or len(next(iter(shapes))) != 2:
+            raise ValueError("%s: images must be 2-D and of one shape, got %s" % (what, sorted(shapes)))
+        imgs = _c(np.stack([np.asarray(a) for a in images]), np.uint8)
+        if masks is None:
+            return imgs, None
+        if len(masks) != len(imgs):
+            raise ValueError("%s: %d masks for %d images" % (what, len(masks), len(imgs)))
+        if all(m is None for m in masks):
+            return imgs, None
+        full = np.full(imgs.shape[1:], 255, np.uint8)                # (no mask = every pixel allowed)
+        ms = [full if m is None else np.asarray(m) for m in masks]
+        if any(m.shape != imgs.shape[1:] for m in ms):
+            raise ValueError("%s: a mask's shape differs from the images' %s" % (what, imgs.shape[1:]))
+        return imgs, _c(np.stack(ms), np.uint8)
+
+    def good_features_batch(self, imgs, masks=None, max_corners=500, quality=0.01, min_distance=8, block_size=7):
+        """Shi-Tomasi corners of S images of one size in one set of launches (vo_good_features_batch): `imgs` is an
+        (S, H, W) uint8 array or a list of equal-shape 2-D arrays, `masks` None or one mask (or None) per image.  Returns a
+        list of S (n_q, 2) float32 arrays, each what good_features(image, mask, ...) returns."""
+        imgs, m = self._image_stack("good_features_batch", imgs, masks)
+        S, H, W = imgs.shape
+        rows = self.good_features_capacity(H, W, max_corners)
+        xy = np.empty((S, rows, 2), np.float32)
+        n = np.zeros(S, np.int32)
+        self._chk(self._lib.vo_good_features_batch(self._h, _ptr(imgs), _ptr(m), S, H, W, int(max_corners), float(quality),
+                                                   float(min_distance), int(block_size), _ptr(xy), _ptr(n)))
+        return [xy[q, : n[q]].copy() for q in range(S)]
+
+    def good_features_batch_dev(self, d_imgs, img_stride, S, H, W, d_xy, xy_stride, d_n, d_masks=None, mask_stride=0,
+                                max_corners=500, quality=0.01, min_distance=8, block_size=7, d_over=None, d_info=None):
+        """vo_good_features_batch_dev on device pointers (dev_alloc): enqueued on the context's stream, nothing read back."""
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        self._chk(self._lib.vo_good_features_batch_dev(self._h, vp(d_imgs), int(img_stride), int(S), int(H), int(W),
+                                                       vp(d_masks), int(mask_stride), int(max_corners), float(quality),
+                                                       float(min_distance), int(block_size), vp(d_xy), int(xy_stride),
+                                                       vp(d_n), vp(d_over), vp(d_info)))
 
     def sift(self, img, cap=None):
         """(kp (n, 6) float32: x, y, size, angle, response, octave; desc (n, 128) float32).
