@@ -92,6 +92,7 @@ enum {
   VO_K_RANSAC_REPLAY = 24,
   VO_K_STATE_LANDMARKS = 25,
   VO_K_EXPORT = 26,
+  VO_K_SHI_TOMASI_CHAIN = 27,   /* the frame loop's Shi-Tomasi re-detect, all of its launches (vo_pipeline_config.detector = 1) */
   VO_K_COUNT = 32
 };
 int vo_prof_enable(vo_ctx* ctx, int kernel_id);
@@ -501,6 +502,18 @@ typedef struct vo_pipeline_config {
                                     up to feature_cap -- a frame with more, or whose SIFT lists overflow, fails its step
                                     with VO_ECAPACITY (never a truncated list).  Below -1: refused.                   */
   double match_ratio;            /* 0 = the reference's: 0.8 in SIFT mode (sift.py:49), 0.85 in Harris mode (harris.py:255) */
+  int32_t detector;              /* tracker_mode 0: what refills the feature set when fewer than redetect_fraction of the
+                                    tracks are left.  0: Harris response + greedy NMS, exactly n_keypoints keypoints
+                                    (harris_patch, harris_kappa, nms_radius above).  1: Shi-Tomasi corners, the reference's
+                                    cv2.goodFeaturesToTrack [ref: src/vo/features/klt.py:24-26, 87-98, 207-230] with
+                                    maxCorners = n_keypoints, no mask (klt.py:216-222 leaves it all-255 whenever features
+                                    exist): the step appends however many corners the frame has (none included), and
+                                    KLTTracker._num_features becomes that count (klt.py:114), so the re-detect limit
+                                    moves with every refill.  A frame whose candidate lists overflow fails its step with
+                                    VO_ECAPACITY naming the frame.  Refused with tracker_mode != 0.                   */
+  int32_t st_block;              /* Shi-Tomasi blockSize, 1..31; 0 = 7                                              */
+  double st_quality;             /* qualityLevel; 0 = 0.01                                                          */
+  double st_min_distance;        /* minDistance; 0 = 8                                                              */
 } vo_pipeline_config;
 typedef struct vo_step_result {
   double R[9], t[3];            /* world -> camera pose of `next` (best hypothesis)   */
@@ -592,6 +605,10 @@ int vo_pipeline_get_state(vo_pipeline* p, int32_t* n_out, double* kp, uint8_t* s
                           vo_ransac_state* rs, int32_t* num_features);
 /* keypoints the detector found on the frame submitted last (n_keypoints*2 float64)              */
 int vo_pipeline_get_detection(vo_pipeline* p, double* kp_xy);
+/* The same for sequence seq with the count: kp_xy holds n_keypoints*2 float64, *n_out = how many of them the detector
+ * found (detector 0: always n_keypoints; detector 1: the frame's Shi-Tomasi corners, 0..n_keypoints).  A frame the
+ * detector sat out is detected now, for that sequence alone.  Nothing may be in flight.                          */
+int vo_pipeline_get_detection_seq(vo_pipeline* p, int seq, double* kp_xy, int32_t* n_out);
 /* One frame.  submit enqueues all GPU work of the step prev_idx -> next_idx and returns; collect
  * waits for the oldest submitted step's record.  At most two steps may be in flight (the frame
  * store and the per-frame buffers rotate over three slots); with submit(k+1) before collect(k)

@@ -500,6 +500,7 @@ constexpr int GB_CTL = 64, GB_R = 24;
 enum { GB_MAX = 0, GB_NC = 1, GB_N = 2, GB_FAULT = 3, GB_PATH = 4, GB_ROUNDS = 5, GB_WALK = 6, GB_OPEN = 8 /* .. 8 + GB_R */,
        GB_COUNT = 40 };
 static_assert(GB_OPEN + GB_R < GB_COUNT && GB_COUNT < GB_CTL, "control block layout");
+static_assert(GB_R == VO_GFB_ROUNDS && GC_WG * GC_T == VO_GFB_CANDIDATES, "vo_internal.h names the ABI call's values");
 
 struct gfb_dims {
   int H, W, cell, gw, gh, ccap;     // ccap: candidates a cell holds on the rounds path, min(GC_CCAP, cell * cell)
@@ -511,8 +512,9 @@ struct gfb_dims {
 __global__ __launch_bounds__(GT) void min_eig_batch_kernel(const uint8_t* __restrict__ imgs, size_t img_stride, gfb_dims g,
                                                            int block, float s2, const uint8_t* __restrict__ masks,
                                                            size_t mask_stride, float* __restrict__ eig,
-                                                           unsigned* __restrict__ ctl) {
+                                                           unsigned* __restrict__ ctl, const int* __restrict__ go) {
   const size_t q = blockIdx.z;
+  if (go && !go[q]) return;          // (gated out: no map, no maximum -- and no candidates below)
   min_eig_tile(imgs + q * img_stride, g.H, g.W, block, s2, masks ? masks + q * mask_stride : nullptr, eig + q * g.px,
                ctl + q * GB_CTL + GB_MAX);
 }
@@ -520,8 +522,9 @@ __global__ __launch_bounds__(GT) void min_eig_batch_kernel(const uint8_t* __rest
 __global__ __launch_bounds__(GT) void corner_candidates_batch_kernel(const float* __restrict__ eig, gfb_dims g,
                                                                      const uint8_t* __restrict__ masks, size_t mask_stride,
                                                                      double quality, unsigned long long* __restrict__ keys,
-                                                                     unsigned* __restrict__ ctl) {
+                                                                     unsigned* __restrict__ ctl, const int* __restrict__ go) {
   const size_t q = blockIdx.z;
+  if (go && !go[q]) return;          // (its count of local maxima stays 0: every later stage falls through)
   corner_candidates_tile(eig + q * g.px, g.H, g.W, masks ? masks + q * mask_stride : nullptr, ctl + q * GB_CTL + GB_MAX,
                          quality, keys + q * g.cap, ctl + q * GB_CTL + GB_COUNT, g.cap);
 }
@@ -947,18 +950,38 @@ int vo_good_features_batch_rounds_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t
                                       const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
                                       double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over,
                                       int32_t* d_info, int n_rounds, int cand_limit) {
+  return vo_good_features_batch_gated_dev(ctx, d_imgs, img_stride, S, H, W, d_masks, mask_stride, max_corners, quality, min_dist,
+                                          block, d_xy, xy_stride, d_n, d_over, d_info, n_rounds, cand_limit, nullptr);
+}
+
+}  // extern "C"
+
+// (vo_internal.h) the argument checks of the batched forms alone
+int vo_good_features_batch_check(vo_ctx* ctx, int S, int H, int W, double quality, double min_dist, int block) {
   if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, n_rounds >= 0 && n_rounds <= GB_R && cand_limit >= 1 && cand_limit <= GC_WG * GC_T,
-             "good_features_batch: rounds must be in 0..%d, the candidate limit in 1..%d", GB_R, GC_WG * GC_T);
-  VO_REQUIRE(ctx, d_imgs && d_xy && d_n && H > 0 && W > 0, "good_features_batch: bad arguments");
+  VO_REQUIRE(ctx, H > 0 && W > 0, "good_features_batch: bad arguments");
   VO_REQUIRE(ctx, S >= 1 && S <= 65535, "good_features_batch: S must be in 1..65535");
   VO_REQUIRE(ctx, block >= 1 && block <= 31, "good_features_batch: blockSize must be in 1..31");
   VO_REQUIRE(ctx, quality > 0 && min_dist >= 0, "good_features_batch: bad quality / minDistance");
   VO_REQUIRE(ctx, W < 65536 && H < 65536, "good_features_batch: image side must be below 65536");
+  const size_t cap = ((size_t)H * W + 3) / 4 + 64;                // 3x3 maxima: at most one per 2x2 block
+  VO_REQUIRE(ctx, (size_t)S * cap < 0xffffffffull, "good_features_batch: %d images of %d x %d exceed the sort's 32-bit offsets", S, H, W);
+  return VO_OK;
+}
+
+// (vo_internal.h) ... and with a gate per image
+int vo_good_features_batch_gated_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                                     const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
+                                     double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over,
+                                     int32_t* d_info, int n_rounds, int cand_limit, const int* d_go) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, n_rounds >= 0 && n_rounds <= GB_R && cand_limit >= 1 && cand_limit <= GC_WG * GC_T,
+             "good_features_batch: rounds must be in 0..%d, the candidate limit in 1..%d", GB_R, GC_WG * GC_T);
+  VO_REQUIRE(ctx, d_imgs && d_xy && d_n && H > 0 && W > 0, "good_features_batch: bad arguments");
+  VO_TRY(vo_good_features_batch_check(ctx, S, H, W, quality, min_dist, block));
   const size_t px = (size_t)H * W, Sz = (size_t)S;
   VO_REQUIRE(ctx, img_stride >= px && (!d_masks || mask_stride >= px), "good_features_batch: image / mask stride below H*W");
   const size_t cap = (px + 3) / 4 + 64;                          // 3x3 maxima: at most one per 2x2 block
-  VO_REQUIRE(ctx, Sz * cap < 0xffffffffull, "good_features_batch: %d images of %d x %d exceed the sort's 32-bit offsets", S, H, W);
   const size_t out_cap = max_corners > 0 ? (size_t)max_corners : cap;
   VO_REQUIRE(ctx, xy_stride >= out_cap, "good_features_batch: xy_stride %zu is below the capacity %zu", xy_stride, out_cap);
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1006,10 +1029,10 @@ int vo_good_features_batch_rounds_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t
   const size_t lds = ((size_t)RW * RH + (size_t)3 * RH * GX) * 4;
   const dim3 tiles(vo_cdiv(W, GX), vo_cdiv(H, GY), S);
   hipLaunchKernelGGL(min_eig_batch_kernel, tiles, dim3(GT), lds, st, d_imgs, img_stride, g, block, (float)(scale * scale),
-                     d_masks, mask_stride, (float*)s[0].p, d_ctl);
+                     d_masks, mask_stride, (float*)s[0].p, d_ctl, d_go);
   VO_TRY(vo_check_launch(ctx, "min_eig_batch_kernel"));
   hipLaunchKernelGGL(corner_candidates_batch_kernel, tiles, dim3(GT), 0, st, (const float*)s[0].p, g, d_masks, mask_stride,
-                     quality, d_keys, d_ctl);
+                     quality, d_keys, d_ctl, d_go);
   VO_TRY(vo_check_launch(ctx, "corner_candidates_batch_kernel"));
   hipLaunchKernelGGL(gfb_segments_kernel, dim3(1), dim3(256), 0, st, S, g, rounds ? 0 : 1, d_ctl, d_seg);
   VO_TRY(vo_check_launch(ctx, "gfb_segments_kernel"));
@@ -1043,6 +1066,8 @@ int vo_good_features_batch_rounds_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t
   VO_TRY(vo_check_launch(ctx, "gfb_emit_kernel"));
   return VO_OK;
 }
+
+extern "C" {
 
 int vo_good_features_batch(vo_ctx* ctx, const uint8_t* imgs, const uint8_t* masks, int S, int H, int W, int max_corners,
                            double quality, double min_dist, int block, float* xy, int32_t* n_out) {

@@ -516,6 +516,7 @@ __global__ __launch_bounds__(64 * KLT_WAVES) void klt_track_kernel(pyr_t P, cons
       src.det_kp += q * B.det;
       if (src.ts) src.ts = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(src.ts) + q * B.ctl);
       if (src.det_go) src.det_go += q;
+      if (src.n_det_dev) src.n_det_dev += q;
     }
   }
   if (d_n) N = min(N, *d_n);                           // keypoint count read on the device (frame pipeline)
@@ -524,7 +525,7 @@ __global__ __launch_bounds__(64 * KLT_WAVES) void klt_track_kernel(pyr_t P, cons
   if (src.n) {
     n_own = *src.n;
     const bool redetect = (double)n_own < (double)*src.num_features * src.frac && (!src.det_go || *src.det_go != 0);
-    N = min(N, n_own + (redetect ? src.n_det : 0));
+    N = min(N, n_own + (redetect ? (src.n_det_dev ? max(*src.n_det_dev, 0) : src.n_det) : 0));
   }
   if (i >= N) return;                                  // whole wave leaves together
   unsigned char* smem = smem_all + (size_t)(threadIdx.x >> 6) * lds_per_wave;
@@ -862,6 +863,7 @@ __global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* _
       src.det_kp += q * B.det;
       if (src.ts) src.ts = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(src.ts) + q * B.ctl);
       if (src.det_go) src.det_go += q;
+      if (src.n_det_dev) src.n_det_dev += q;
     }
   }
   if (d_n) N = min(N, *d_n);                           // keypoint count read on the device (frame pipeline)
@@ -870,7 +872,7 @@ __global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* _
   if (src.n) {
     n_own = *src.n;
     const bool redetect = (double)n_own < (double)*src.num_features * src.frac && (!src.det_go || *src.det_go != 0);
-    N = min(N, n_own + (redetect ? src.n_det : 0));
+    N = min(N, n_own + (redetect ? (src.n_det_dev ? max(*src.n_det_dev, 0) : src.n_det) : 0));
   }
   if (i >= N) return;                                  // all lanes of a keypoint leave together
   const int r = lane & (LPK - 1);                      // window row of this lane (row WIN only feeds row WIN-1's derivatives)

@@ -44,6 +44,13 @@ struct vo_pipeline {
   double* d_kp = nullptr;            // [S][3][N * 2]          detector output per frame slot
   double* d_scores[2] = {nullptr, nullptr};   // [S][px] each, alternating between consecutive detections
   int* d_det_go = nullptr;           // [3][S]: 1 = the detector ran for that sequence on the frame in keypoint slot s
+  // vo_pipeline_config.detector = 1 (Shi-Tomasi re-detect; all null otherwise): the batched detector's float corners and
+  // verdicts of the detection being made (the detection stream runs one at a time), and what the closing kernel leaves
+  // per keypoint slot: the corner count of every sequence (-1: its candidate lists overflowed)
+  float* d_st_xy = nullptr;          // [S][N * 2]
+  int32_t* d_st_n = nullptr;         // [2][S]: counts, verdicts
+  int32_t* d_det_cnt = nullptr;      // [3][S]
+  int st_rounds = 0;                 // round launches of the minimum-distance rule per detection (VO_ST_ROUNDS)
   double detect_limit = 0.0;         // detect when n < detect_limit * num_features (< 0: always)
   double detect_losses = 2.5;        // ... with n extrapolated by this many times the last step's loss
   hipEvent_t evPyr[3] = {nullptr, nullptr, nullptr}, evDet[3] = {nullptr, nullptr, nullptr};

@@ -199,6 +199,17 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   VO_REQUIRE(ctx, cfg->tracker_mode != 1 || cfg->sequences <= 1, "pipeline: the SIFT tracker mode runs one sequence per pipeline");
   VO_REQUIRE(ctx, cfg->tracker_mode != 1 || cfg->sift_cap >= -1,
              "pipeline: sift_cap must be -1 (every keypoint), 0 (n_keypoints) or 1..4000, got %d", cfg->sift_cap);
+  VO_REQUIRE(ctx, cfg->detector >= 0 && cfg->detector <= 1, "pipeline: detector must be 0 (harris) or 1 (shi-tomasi), got %d",
+             cfg->detector);
+  VO_REQUIRE(ctx, cfg->detector == 0 || cfg->tracker_mode == 0,
+             "pipeline: the Shi-Tomasi detector (detector = 1) belongs to the KLT tracker mode (tracker_mode = 0)");
+  if (cfg->detector == 1) {            // klt.py:24-26 where a field is 0; the rest is what the batched detector takes
+    const int rc = vo_good_features_batch_check(ctx, cfg->sequences > 0 ? cfg->sequences : 1, cfg->H, cfg->W,
+                                                cfg->st_quality == 0.0 ? 0.01 : cfg->st_quality,
+                                                cfg->st_min_distance == 0.0 ? 8.0 : cfg->st_min_distance,
+                                                cfg->st_block == 0 ? 7 : cfg->st_block);
+    if (rc != VO_OK) return rc;
+  }
   const int cap = cfg->feature_cap > 0 ? cfg->feature_cap : 2 * cfg->n_keypoints;
   VO_REQUIRE(ctx, cap >= cfg->n_keypoints && cap <= 32768, "pipeline: feature_cap must be in n_keypoints..32768");
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -215,6 +226,9 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   if (p->cfg.redetect_fraction == 0.0) p->cfg.redetect_fraction = 0.8;       // klt.py:212
   if (p->cfg.detect_margin == 0.0) p->cfg.detect_margin = 0.01;
   if (p->cfg.detect_losses <= 0.0) p->cfg.detect_losses = 2.5;
+  if (p->cfg.st_block == 0) p->cfg.st_block = 7;                             // klt.py:24-26
+  if (p->cfg.st_quality == 0.0) p->cfg.st_quality = 0.01;
+  if (p->cfg.st_min_distance == 0.0) p->cfg.st_min_distance = 8.0;
   p->detect_losses = p->cfg.detect_losses;
   p->detect_limit = p->cfg.detect_margin < 0.0 ? -1.0 : p->cfg.redetect_fraction + p->cfg.detect_margin;
   if (p->cfg.debug_never_detect) p->detect_limit = 0.0;     // test hook: only forced detections (state hand-over, host path)
@@ -269,6 +283,11 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   PA(dev_alloc(p, &p->d_scores[0], Sz * px));
   PA(dev_alloc(p, &p->d_scores[1], Sz * px));
   PA(dev_alloc(p, &p->d_det_go, 3 * Sz));
+  if (cfg->detector == 1) {
+    PA(dev_alloc(p, &p->d_st_xy, Sz * N * 2));
+    PA(dev_alloc(p, &p->d_st_n, 2 * Sz));
+    PA(dev_alloc(p, &p->d_det_cnt, 3 * Sz));
+  }
   {
     const size_t fb = feat_bytes(cap, S);
     char* mem = nullptr;
@@ -393,6 +412,27 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
       (void)hipMemsetAsync(p->d_status, 0, 4, q);
       (void)hipStreamSynchronize(q);
       dbg_stage("create: a stream ran");
+    }
+  }
+  if (cfg->detector == 1) {
+    // The Shi-Tomasi chain's workspace on the detection context, sized for all S images, before the first step: one pass of
+    // the chain itself with every image gated out (no step allocates).  VO_ST_ROUNDS: round launches of the minimum-distance
+    // rule per detection (measurements; results do not depend on it, an unfinished image goes to the walk).
+    p->st_rounds = VO_GFB_ROUNDS;
+    if (const char* e = getenv("VO_ST_ROUNDS")) p->st_rounds = std::min(VO_GFB_ROUNDS, std::max(0, atoi(e)));
+    if (mset(p->det->stream, p->d_det_go, 0, 3 * Sz * sizeof(int)) != hipSuccess ||
+        mset(p->det->stream, p->d_det_cnt, 0, 3 * Sz * sizeof(int32_t)) != hipSuccess)
+      rc = vo_set_error(ctx, VO_EHIP, "pipeline: hipMemset failed");
+    if (rc == VO_OK) {
+      rc = vo_good_features_batch_gated_dev(p->det, p->img(0, 0), p->img_stride(), S, cfg->H, cfg->W, nullptr, 0, N,
+                                            p->cfg.st_quality, p->cfg.st_min_distance, p->cfg.st_block, p->d_st_xy, (size_t)N,
+                                            p->d_st_n, p->d_st_n + S, nullptr, p->st_rounds, VO_GFB_CANDIDATES, p->d_det_go);
+      if (rc != VO_OK) vo_set_error(ctx, rc, "pipeline: %s", vo_last_error(p->det));
+    }
+    if (rc == VO_OK && hipStreamSynchronize(p->det->stream) != hipSuccess) rc = vo_set_error(ctx, VO_EHIP, "pipeline: the detection stream failed");
+    if (rc != VO_OK) {
+      vo_pipeline_destroy(p);
+      return rc;
     }
   }
   if (const char* e = getenv("VO_HOST_THREADS_BUDGET")) p->threads_budget = atoi(e) <= 1 ? 1 : 2;

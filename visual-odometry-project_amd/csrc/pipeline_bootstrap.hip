@@ -178,6 +178,7 @@ __global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args g,
     h.n = a_n;
     h.n2 = a_n;
     h.num_features = a_num_features;
+    h.nf[0] = h.nf[1] = a_num_features;
     h.raw_pos = raw_pos;
     h.n_iterations = n_it;
     h.outlier_ratio = orat;

@@ -29,6 +29,7 @@ __global__ __launch_bounds__(64) void ctl_rewind_kernel(vo_seq_ctl* __restrict__
   c.outlier_ratio = ctl[q].outlier_ratio;
   c.raw_pos = ctl[q].raw_pos;
   c.step = ctl[q].step;
+  c.nf[0] = c.nf[1] = c.num_features;     // (whichever parity the next step has: vo_seq_ctl.nf)
   ctl[q] = c;
 }
 
@@ -117,6 +118,7 @@ static int upload_state(vo_pipeline* p, int seq, int n, const double* kp, const 
   h.n = n;
   h.n2 = n;
   h.num_features = num_features;
+  h.nf[0] = h.nf[1] = num_features;
   h.raw_pos = raw_pos;
   if (keep_ransac) {
     h.n_iterations = n_it;
@@ -409,6 +411,34 @@ int vo_pipeline_get_detection(vo_pipeline* p, double* kp_xy) {
     }
   }
   VO_HIP_TRY(ctx, mcpy(ctx->stream, kp_xy, p->kp(0, p->slot), (size_t)p->cfg.n_keypoints * 16, hipMemcpyDeviceToHost));
+  return VO_OK;
+}
+
+int vo_pipeline_get_detection_seq(vo_pipeline* p, int seq, double* kp_xy, int32_t* n_out) {
+  if (!p || !kp_xy || !n_out) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_get_detection: bad sequence index");
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_get_detection: %d submitted step(s) not collected", p->n_flight);
+  VO_REQUIRE(ctx, !p->idle[seq], "pipeline_get_detection: sequence %d is idle", seq);
+  VO_TRY(worker_idle(p));
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (p->have_state && !p->primed) VO_TRY(prime(p));
+  VO_HIP_TRY(ctx, hipEventSynchronize(p->evDet[p->slot]));
+  int ran = 0;
+  VO_HIP_TRY(ctx, mcpy(ctx->stream, &ran, p->d_det_go + (size_t)p->slot * p->S + seq, 4, hipMemcpyDeviceToHost));
+  if (!ran) {                            // the frame's detection was skipped: made now, for this sequence
+    VO_TRY(enqueue_detection(p, p->prev_frame, p->slot, true, nullptr, seq, 1));
+    VO_HIP_TRY(ctx, hipStreamSynchronize(p->det->stream));
+  }
+  int32_t n = p->cfg.n_keypoints;
+  if (p->d_det_cnt) {
+    VO_HIP_TRY(ctx, mcpy(ctx->stream, &n, p->d_det_cnt + (size_t)p->slot * p->S + seq, 4, hipMemcpyDeviceToHost));
+    if (n < 0)
+      return vo_set_error(ctx, VO_ECAPACITY, "pipeline: the Shi-Tomasi candidate lists of frame %d overflowed (sequence %d)",
+                          p->prev_frame, seq);
+  }
+  *n_out = n;
+  if (n > 0) VO_HIP_TRY(ctx, mcpy(ctx->stream, kp_xy, p->kp(seq, p->slot), (size_t)n * 16, hipMemcpyDeviceToHost));
   return VO_OK;
 }
 

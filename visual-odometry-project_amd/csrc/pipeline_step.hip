@@ -5,7 +5,8 @@
 // Streams of one step (frame k-1 -> k):
 //   main   : regroup -> hypotheses+counts -> replay+refine+candidates+landmarks+record
 //   tracker: pyramid(k) -> KLT(k)           needs regroup(k-1) only: runs beside the pose estimation of step k-1
-//   detect : Harris response + NMS on k     (enqueued by a worker thread; consumed by the NEXT step's re-detect.
+//   detect : Harris response + NMS on k -- or, vo_pipeline_config.detector = 1, the reference's own Shi-Tomasi corners and
+//            their count -- (enqueued by a worker thread; consumed by the NEXT step's re-detect.
 //            The reference runs its detector only when fewer than 80 % of the tracks are left, klt.py:207-230; whether
 //            that will be so for frame k is known one step too late for a launch without a host turn, so the chain is
 //            launched for every frame and each sequence sits it out unless its track count is within `detect_margin`
@@ -36,6 +37,8 @@ namespace {
 // on 26 % of the forward stream's frames for the 4 % that re-detect; 2.5 and 0.01: 15-18 %, still no frame caught without
 // its keypoints in ~4000 sequence-steps; 2 and 0.005: 12-14 % and one such frame.)  (The fields are read while a regroup may be writing them: any
 // mix of old and new values is a usable guess, and a wrong guess is caught by the step that needs the keypoints.)
+// n_det: what a re-detect step appended -- the detector's fixed count, or (< 0: a detector that counts its corners) the
+// count itself, which _num_features has been since (klt.py:114).
 __global__ __launch_bounds__(64) void detect_decide_kernel(const vo_seq_ctl* __restrict__ ctl, int S, double limit, int n_det,
                                                            int force, int* __restrict__ go, double losses) {
   const int q = blockIdx.x * 64 + threadIdx.x;
@@ -45,7 +48,7 @@ __global__ __launch_bounds__(64) void detect_decide_kernel(const vo_seq_ctl* __r
     return;
   }
   const int n2 = ctl[q].n2;
-  const int lost = max(ctl[q].n_in - (ctl[q].redetected ? n_det : 0) - n2, 0);
+  const int lost = max(ctl[q].n_in - (ctl[q].redetected ? (n_det < 0 ? ctl[q].num_features : n_det) : 0) - n2, 0);
   go[q] = (force || limit < 0.0 || (limit > 0.0 && (double)n2 - losses * (double)lost < (double)ctl[q].num_features * limit)) ? 1 : 0;
 }
 
@@ -98,6 +101,24 @@ __global__ __launch_bounds__(256) void desc_gather_kernel(const uint8_t* __restr
       reinterpret_cast<const unsigned*>(src)[(size_t)src_row[row] * row_words + k];
 }
 
+// Shi-Tomasi re-detect (vo_pipeline_config.detector = 1), the chain's last kernel: the batched detector's corners of
+// sequence blockIdx.y as the float64 pairs of its keypoint slot (whole pixel positions: exact), and its count -- -1 for a
+// frame whose candidate lists overflowed (verdict != 0), which the step that needs the corners turns into a capacity fault.
+// A sequence that sat the detection out keeps what its slot held.
+__global__ __launch_bounds__(256) void st_close_kernel(const float* __restrict__ xy, size_t xy_stride, const int32_t* __restrict__ n,
+                                                       const int32_t* __restrict__ over, const int* __restrict__ go, int cap,
+                                                       double* __restrict__ kp, size_t kp_stride, int32_t* __restrict__ cnt) {
+  const size_t q = blockIdx.y;
+  if (!go[q]) return;
+  const int m = over[q] ? -1 : min(n[q], cap);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < m) {
+    kp[q * kp_stride + 2 * i] = (double)xy[q * xy_stride + 2 * i];
+    kp[q * kp_stride + 2 * i + 1] = (double)xy[q * xy_stride + 2 * i + 1];
+  }
+  if (i == 0) cnt[q] = m;
+}
+
 // the caller's context's profiling flags onto side context q (whose launches this thread makes, or an idle worker)
 void copy_prof(vo_ctx* q, const vo_ctx* from) {
   q->prof_on = from->prof_on;
@@ -123,7 +144,8 @@ static int launch_error(vo_pipeline* p, char* err_buf, int rc, const char* what,
 
 // ---- launches; (q0, Sn): sequences q0 .. q0 + Sn - 1 (all of them, or one when a step is redone) ----
 
-// Harris + NMS of frame slot `frame` into keypoint slot `s` on the detection stream; evDet[s] when done (err_buf: see
+// Harris + NMS (detector 1: Shi-Tomasi corners and their count, vo_good_features_batch_gated_dev + st_close_kernel, no mask:
+// klt.py:216-222) of frame slot `frame` into keypoint slot `s` on the detection stream; evDet[s] when done (err_buf: see
 // launch_error).  (q0, Sn): sequences q0 .. q0 + Sn - 1 (Sn = 0: all of them); an idle sequence's detector does not run
 // (detect_decide_kernel), a forced one runs and says so in d_det_go
 int enqueue_detection(vo_pipeline* p, int frame, int s, bool force, char* err_buf, int q0, int Sn) {
@@ -138,8 +160,26 @@ int enqueue_detection(vo_pipeline* p, int frame, int s, bool force, char* err_bu
   if (wait_ok && p->n_pinned[frame] > 0) wait_ok = hipStreamWaitEvent(det->stream, p->evUp[frame], 0) == hipSuccess;   // (pinned)
   if (!wait_ok) return launch_error(p, err_buf, VO_EHIP, "detection", "hipStreamWaitEvent failed");
   hipLaunchKernelGGL(detect_decide_kernel, dim3(vo_cdiv(Sn, 64)), dim3(64), 0, det->stream, p->d_ctl + q0, Sn, p->detect_limit,
-                     c.n_keypoints, force ? 1 : 0, go, p->detect_losses);
+                     c.detector == 1 ? -1 : c.n_keypoints, force ? 1 : 0, go, p->detect_losses);
   int rc = vo_check_launch(det, "detect_decide_kernel");
+  if (c.detector == 1) {
+    vo_prof_scope ps(det, VO_K_SHI_TOMASI_CHAIN);      // (the whole chain, executing or gated out)
+    const int N = c.n_keypoints;
+    float* xy = p->d_st_xy + (size_t)q0 * N * 2;
+    int32_t *n = p->d_st_n + q0, *over = p->d_st_n + p->S + q0;
+    if (rc == VO_OK)
+      rc = vo_good_features_batch_gated_dev(det, p->img(q0, frame), p->img_stride(), Sn, c.H, c.W, nullptr, 0, N, c.st_quality,
+                                            c.st_min_distance, c.st_block, xy, (size_t)N, n, over, nullptr, p->st_rounds,
+                                            VO_GFB_CANDIDATES, go);
+    if (rc == VO_OK) {
+      hipLaunchKernelGGL(st_close_kernel, dim3(vo_cdiv(N, 256), Sn), dim3(256), 0, det->stream, (const float*)xy, (size_t)N * 2,
+                         (const int32_t*)n, (const int32_t*)over, (const int*)go, N, p->kp(q0, s), p->det_stride(),
+                         p->d_det_cnt + (size_t)s * p->S + q0);
+      rc = vo_check_launch(det, "st_close_kernel");
+    }
+    if (rc == VO_OK && hipEventRecord(p->evDet[s], det->stream) != hipSuccess) rc = VO_EHIP;
+    return rc != VO_OK ? launch_error(p, err_buf, rc, "detection", vo_last_error(det)) : VO_OK;
+  }
   if (rc == VO_OK)
     rc = vo_harris_response_batch_dev(det, p->img(q0, frame), p->img_stride(), Sn, c.H, c.W, c.harris_patch, c.harris_kappa,
                                       scores, go);
@@ -247,6 +287,10 @@ static int enqueue_tracker(vo_pipeline* p, const vo_pipeline::flight_t& f, bool 
   src.frac = c.redetect_fraction;
   src.det_kp = p->kp(q0, f.a);
   src.n_det = c.n_keypoints;
+  if (p->d_det_cnt) {                // (Shi-Tomasi re-detect: the slot's corner count, and the step's _num_features word)
+    src.n_det_dev = p->d_det_cnt + (size_t)f.a * p->S + q0;
+    src.num_features = &ctl->nf[f.k & 1];
+  }
   src.ts = &ctl->ts[0];
   src.det_go = p->d_det_go + (size_t)f.a * p->S + q0;
   vo_klt_batch kb;
@@ -295,6 +339,10 @@ static int enqueue_chain(vo_pipeline* p, const vo_pipeline::flight_t& f, bool fi
   ap.pose_mode = c.redetect_start_pose;
   ap.debug_fault_every = debug_fault_every > 0 ? debug_fault_every : 0;
   ap.det_go = p->d_det_go + (size_t)f.a * p->S + q0;
+  if (p->d_det_cnt) {
+    ap.n_det_dev = p->d_det_cnt + (size_t)f.a * p->S + q0;
+    ap.nf_par = (int)(f.k & 1);
+  }
   ctx->next_stop = p->evRegroup[f.k & 1];
   VO_TRY(vo_state_regroup_klt(ctx, ctl, A, B, p->d_next + q * p->cap * 2, p->d_status + q * p->cap, p->d_err + q * p->cap,
                               (float)c.klt_err_threshold, ap, p->cap, Sn));
@@ -728,6 +776,20 @@ static int wait_record(vo_pipeline* p, int rslot, int q, unsigned seq, uint64_t 
   }
 }
 
+// The text of a re-detect that does not fit: n features and the detector's keypoints of the step's `prev` frame -- n_keypoints
+// of them, or (Shi-Tomasi) the count the detection left in the slot; a frame whose Shi-Tomasi lists overflowed says so.
+static int capacity_error(vo_pipeline* p, const vo_pipeline::flight_t& f, int q, int n) {
+  vo_ctx* ctx = p->ctx;
+  int32_t n_det = p->cfg.n_keypoints;
+  if (p->d_det_cnt) {
+    VO_HIP_TRY(ctx, mcpy(ctx->stream, &n_det, p->d_det_cnt + (size_t)f.a * p->S + q, 4, hipMemcpyDeviceToHost));
+    if (n_det < 0)
+      return vo_set_error(ctx, VO_ECAPACITY, "pipeline: the Shi-Tomasi candidate lists of frame %d overflowed (sequence %d)",
+                          f.prev_idx, q);
+  }
+  return vo_set_error(ctx, VO_ECAPACITY, "pipeline: %d features + %d new keypoints exceed the capacity %d", n, n_det, p->cap);
+}
+
 // Sequence q's step of flight f raised a fault: nothing persistent of that sequence was touched, so the step is run
 // again from its first main-stream kernel (for that sequence alone) with the sequential sampler and the reference's
 // loop on the host (ransac.py:90-121), then handed back to the device for the refinement and the bookkeeping.
@@ -751,9 +813,7 @@ static int recover_step(vo_pipeline* p, const vo_pipeline::flight_t& f, int q, v
       return vo_set_error(ctx, VO_ECAPACITY, "pipeline: frame %d has %d SIFT keypoints, more than the feature capacity %d",
                           f.next_idx, v[1], p->cap);
   }
-  if (h.fault & VO_FAULT_CAPACITY)
-    return vo_set_error(ctx, VO_ECAPACITY, "pipeline: %d features + %d new keypoints exceed the capacity %d", h.n,
-                        c.n_keypoints, p->cap);
+  if (h.fault & VO_FAULT_CAPACITY) return capacity_error(p, f, q, h.n);
   const int zero = 0;
   VO_HIP_TRY(ctx, mcpy(st, &ctl->fault, &zero, 4, hipMemcpyHostToDevice));
   // The tracker reads its feature count from n2, which the step's own regroup has replaced by the NEW frame's count
@@ -775,9 +835,7 @@ static int recover_step(vo_pipeline* p, const vo_pipeline::flight_t& f, int q, v
     if (!(h.fault & VO_FAULT_NO_DETECTION) || attempt > 0) break;
     VO_HIP_TRY(ctx, mcpy(st, &ctl->fault, &zero, 4, hipMemcpyHostToDevice));
   }
-  if (h.fault & VO_FAULT_CAPACITY)
-    return vo_set_error(ctx, VO_ECAPACITY, "pipeline: %d features + %d new keypoints exceed the capacity %d", h.n,
-                        c.n_keypoints, p->cap);
+  if (h.fault & VO_FAULT_CAPACITY) return capacity_error(p, f, q, h.n);
   if (h.fault & VO_FAULT_NO_DETECTION) return vo_set_error(ctx, VO_EHIP, "pipeline: the detector's keypoints are missing");
   const int n = h.n_tri;
   if (n < 4) return vo_set_error(ctx, VO_ETRACKING, "pipeline: only %d triangulated tracks survive, no pose", n);

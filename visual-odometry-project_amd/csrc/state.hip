@@ -267,8 +267,15 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
   const int n = ctl->n;
   if (ap.debug_fault_every > 0 && (ctl->step % ap.debug_fault_every) == ap.debug_fault_every - 1) fault |= VO_FAULT_FORCED;
   // `length < self._num_features * 0.8` (klt.py:208-212)
-  const bool redetect = !fault && (double)n < (double)ctl->num_features * ap.frac;
-  if (redetect && n + ap.n_det > cap) fault |= VO_FAULT_CAPACITY;
+  const int nf = ap.n_det_dev ? ctl->nf[ap.nf_par] : ctl->num_features;
+  const bool redetect = !fault && (double)n < (double)nf * ap.frac;
+  int n_det = ap.n_det;
+  if (ap.n_det_dev) {                  // a detector that counts its keypoints (Shi-Tomasi): what it found, if it ran
+    const int c = redetect && (!ap.det_go || ap.det_go[blockIdx.y]) ? ap.n_det_dev[blockIdx.y] : 0;
+    if (c < 0) fault |= VO_FAULT_CAPACITY;        // (the frame's candidate lists overflowed: never a truncated list)
+    n_det = max(c, 0);
+  }
+  if (redetect && n + n_det > cap) fault |= VO_FAULT_CAPACITY;
   if (redetect && ap.det_go && !ap.det_go[blockIdx.y]) fault |= VO_FAULT_NO_DETECTION;
   if (fault) {
     if (blockIdx.x == 0 && tid == 0) {
@@ -282,7 +289,7 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
     }
     return;
   }
-  const int n_in = n + (redetect ? ap.n_det : 0);
+  const int n_in = n + (redetect ? n_det : 0);
   if (start >= n_in && blockIdx.x != 0) return;
   // The flags of the first 16 x 256 items and this work item's own feature are requested together, ahead of the counting:
   // this kernel sits on the main chain AND in front of the tracker, and each dependent round trip here (there were up to
@@ -422,6 +429,11 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
     ctl->n_in = n_in;
     ctl->redetected = redetect ? 1 : 0;
     ctl->det_ran = ap.det_go ? ap.det_go[blockIdx.y] : 1;
+    if (ap.n_det_dev) {                // `self._num_features = pts.shape[0]` (klt.py:114 via :224), for the next step
+      const int nf_next = redetect ? n_det : nf;
+      ctl->nf[ap.nf_par ^ 1] = nf_next;
+      ctl->num_features = nf_next;
+    }
     ctl->n2 = T0 + T1 + T2;
     ctl->n_tri = T0;
     ctl->n_mat = T1;

@@ -209,6 +209,16 @@ extern "C" int vo_good_features_batch_rounds_dev(vo_ctx* ctx, const uint8_t* d_i
                                                  const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
                                                  double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n,
                                                  int32_t* d_over, int32_t* d_info, int n_rounds, int cand_limit);
+constexpr int VO_GFB_ROUNDS = 24, VO_GFB_CANDIDATES = 131072;      // what the ABI call passes for the two
+// ... and with a gate per image: d_go (optional, S ints on the device) -- an image whose word is 0 is left out of the map
+// and the candidate kernels, has no candidates, and every later stage falls through for it (no sort work, no rounds, no
+// walk); its d_n / d_over are 0.  The frame loop's re-detect (pipeline_step.hip, vo_pipeline_config.detector = 1).
+int vo_good_features_batch_gated_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                                     const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
+                                     double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over,
+                                     int32_t* d_info, int n_rounds, int cand_limit, const int* d_go);
+// the argument checks of the batched forms alone (what vo_pipeline_create refuses a Shi-Tomasi configuration with)
+int vo_good_features_batch_check(vo_ctx* ctx, int S, int H, int W, double quality, double min_dist, int block);
 //   hypotheses: samples (host, Hyp x 8, checked against N) are the only array uploaded; counts (host, Hyp) the only one
 //   downloaded; d_F Hyp x 9, d_counts Hyp, d_masks Hyp x cdiv(N, 64) words (nullable) are the caller's device buffers
 int vo_fundamental_hypotheses_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const int32_t* samples, int Hyp,
@@ -282,6 +292,8 @@ struct vo_klt_source {
   int n_det = 0;
   unsigned long long* ts = nullptr;   // (optional) receives wall_clock64() when the kernel's first work item starts
   const int* det_go = nullptr;        // (optional, one int per sequence) 0: det_kp was not produced, nothing is appended
+  const int32_t* n_det_dev = nullptr; // (optional, one int per sequence) the detector's count read on the device instead of
+                                      // n_det (a Shi-Tomasi re-detect; below 0: the detector failed, nothing is appended)
 };
 // several sequences per launch (grid.y = sequence): element strides from one sequence's block to the next
 struct vo_klt_batch {

@@ -85,6 +85,11 @@ struct vo_seq_ctl {
   // wall_clock64() (100 MHz) when the first work item of each kernel of the chain started: tracker, regroup,
   // hypotheses, pose, landmarks, and when the landmarks kernel's last workgroup wrote the record
   unsigned long long ts[8];
+  // KLTTracker._num_features when a re-detect may change it (vo_pipeline_config.detector = 1: klt.py:114 sets it to the
+  // count find_corners returned).  Step k reads nf[k & 1] -- tracker and regroup alike -- and its regroup writes
+  // nf[(k + 1) & 1]: the regroup's other workgroups, and a step redone after a fault, never read a word this step wrote.
+  // num_features above follows as a copy (what vo_pipeline_get_state returns).  A state hand-over sets all three.
+  int32_t nf[2];
 };
 
 struct vo_cam {
@@ -103,6 +108,10 @@ struct vo_append {
   int pose_mode;            // vo_pipeline_config.redetect_start_pose
   int debug_fault_every;
   const int* det_go;        // per sequence: 1 = the detector ran on the frame det_kp belongs to (NULL: it always does)
+  const int32_t* n_det_dev = nullptr; // per sequence, NULL or: the detector's count on the device (Shi-Tomasi: 0 .. n_det corners;
+                            // below 0: the frame's candidate lists overflowed, a capacity fault) -- what is appended instead
+                            // of n_det, and what KLTTracker._num_features becomes (klt.py:114)
+  int nf_par = 0;           // with n_det_dev: the step's parity, see vo_seq_ctl.nf
 };
 
 struct vo_replay_args {

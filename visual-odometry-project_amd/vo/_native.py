@@ -20,6 +20,7 @@ _CODES = {VO_EINVAL: "VO_EINVAL", VO_ENOMEM: "VO_ENOMEM", VO_EHIP: "VO_EHIP", VO
 # kernel ids (vo_hip.h)
 K_HARRIS_RESPONSE, K_NMS_CANDIDATES, K_NMS_THRESHOLD, K_NMS_COMPACT, K_NMS_SELECT = 0, 1, 2, 3, 4
 K_PATCH_DESC, K_PYR_DOWN, K_KLT_TRACK, K_DLT, K_P3P_SOLVE, K_P3P_SCORE, K_REPROJ, K_MATCH = 5, 6, 7, 8, 9, 10, 11, 12
+K_SHI_TOMASI_CHAIN = 27
 K_COUNT = 32
 
 
@@ -72,7 +73,9 @@ class PipelineConfig(C.Structure):
                 ("bearing_threshold", C.c_double), ("redetect_fraction", C.c_double),
                 ("debug_fault_every", C.c_int32), ("redetect_start_pose", C.c_int32), ("detect_margin", C.c_double),
                 ("debug_never_detect", C.c_int32), ("detect_losses", C.c_double), ("sequences", C.c_int32),
-                ("tracker_mode", C.c_int32), ("sift_cap", C.c_int32), ("match_ratio", C.c_double)]
+                ("tracker_mode", C.c_int32), ("sift_cap", C.c_int32), ("match_ratio", C.c_double),
+                ("detector", C.c_int32), ("st_block", C.c_int32), ("st_quality", C.c_double),
+                ("st_min_distance", C.c_double)]
 
 
 class StepResult(C.Structure):
@@ -210,6 +213,7 @@ _SIGS = {
     "vo_pipeline_feature_cap": (_i, [_vp]),
     "vo_pipeline_get_state": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_pipeline_get_detection": (_i, [_vp, _vp]),
+    "vo_pipeline_get_detection_seq": (_i, [_vp, _i, _vp, _vp]),
     "vo_pipeline_step": (_i, [_vp, _i, _i, _vp]),
     "vo_pipeline_submit": (_i, [_vp, _i, _i]),
     "vo_pipeline_collect": (_i, [_vp, _vp]),

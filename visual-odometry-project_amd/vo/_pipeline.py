@@ -23,13 +23,17 @@ def _as_4x4(pose):
     return np.ascontiguousarray(pose)
 
 
+DETECTORS = {"harris": 0, "shi-tomasi": 1}       # vo_pipeline_config.detector
+
+
 class Pipeline:
     def __init__(self, ctx, H, W, n_frames, K, n_keypoints=2000, harris_patch=9, harris_kappa=0.09, nms_radius=5,
                  klt_win=15, klt_max_level=2, klt_max_iter=10, klt_eps=0.03, klt_min_eig=1e-4,
                  klt_err_threshold=100.0, hyp=1000, p3p_threshold=1.0, outlier_ratio=0.9, confidence=0.99,
                  max_iterations=1000, seed=2023, refine_iters=0, feature_cap=0, bearing_threshold=0.0075,
                  redetect_fraction=0.8, debug_fault_every=0, redetect_start_pose="identity", sequences=1,
-                 detect_margin=0.01, debug_never_detect=0, detect_losses=2.5, tracker="klt", sift_cap=0, match_ratio=0.0):
+                 detect_margin=0.01, debug_never_detect=0, detect_losses=2.5, tracker="klt", sift_cap=0, match_ratio=0.0,
+                 detector="harris", st_quality=0.0, st_min_distance=0.0, st_block=0):
         from vo import _native
         self.ctx = ctx
         self.cfg = _native.PipelineConfig()
@@ -54,6 +58,11 @@ class Pipeline:
         c.tracker_mode = {"klt": 0, "sift": 1, "harris": 2}[tracker]         # src/vo/features/tracker.py:54-63
         c.sift_cap = int(sift_cap)   # SIFT mode: -1 every keypoint (<= feature_cap), 0 n_keypoints, 1..4000 the strongest
         c.match_ratio = float(match_ratio)
+        # KLT mode's re-detect: "harris" (response + NMS, exactly n_keypoints) or "shi-tomasi" (the reference's
+        # cv2.goodFeaturesToTrack with maxCorners = n_keypoints; st_* left at 0: klt.py:24-26's 0.01 / 8 / 7)
+        c.detector = DETECTORS[detector]
+        c.st_quality, c.st_min_distance, c.st_block = float(st_quality), float(st_min_distance), int(st_block)
+        self.detector = detector
         self.tracker = tracker
         self.sequences = int(sequences)
         K = np.asarray(K, np.float64).reshape(3, 3)
@@ -272,10 +281,13 @@ class Pipeline:
         f.state, f.tracks, f.poses, f.candidate_mask = s["state"], s["tracks"], s["poses"], s["candidate_mask"]
         return f
 
-    def get_detection(self):
+    def get_detection(self, seq=0):
+        """The detector's keypoints of the frame submitted last, sequence `seq`: (n, 2) float64 -- n_keypoints rows with
+        the Harris detector, the frame's corner count with Shi-Tomasi (nothing in flight)."""
         kp = np.empty((self.cfg.n_keypoints, 2), np.float64)
-        self.ctx._chk(self.ctx._lib.vo_pipeline_get_detection(self._h, _ptr(kp)))
-        return kp
+        n = C.c_int32()
+        self.ctx._chk(self.ctx._lib.vo_pipeline_get_detection_seq(self._h, int(seq), _ptr(kp), C.byref(n)))
+        return kp[:n.value].copy()
 
     # ---- frames ----
     def step(self, prev_idx, next_idx):

@@ -108,7 +108,7 @@ def _gray(image):
 def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
                   klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                   redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
-                  bootstrap_threshold: float = 0.25, bootstrap: str = "host"):
+                  bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris"):
     """Same loop, same bootstrap, but the steady state runs as the device-resident pipeline (vo_pipeline_*):
     after the host bootstrap the Features / State arrays are handed to the GPU once, every later frame costs one
     image upload and one call, and nothing but the pose record comes back.  KLT tracker mode with the Harris
@@ -119,6 +119,9 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     update_features (klt.py:148-153: re-detected keypoints start their track at np.eye(4), so away from the origin
     they triangulate against a wrong baseline and can take the estimate with them); "current" starts them at the
     pose of the frame they were found on.
+    detector: what refills the feature set -- "harris" (response + NMS, n_keypoints keypoints) or "shi-tomasi", the
+    reference's cv2.goodFeaturesToTrack (klt.py:24-26, maxCorners = n_keypoints): as many corners as the frame has, and
+    the re-detect limit follows that count (klt.py:114).
     bootstrap: "host" -- the bootstrap through the drop-in classes, handed over with set_state; "device" -- frames 0 and 2
     go into two slots of the frame store and the pipeline bootstraps itself from them (Pipeline.bootstrap,
     vo_pipeline_bootstrap_seq): same kernels, same result, no array brought back in between."""
@@ -131,7 +134,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
         img0, img = _bootstrap_frames(sequence)
         H, W = img.shape
         pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(None, n_keypoints, klt_win, klt_max_level, hyp,
-                                                                         redetect_start_pose))
+                                                                         redetect_start_pose, detector))
         pipe.set_frame(1, img0)                          # (slot 1 takes frame 3 next: the bootstrap is done with it by then)
         pipe.set_frame(0, img)
         boot = pipe.bootstrap(1, 0, **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
@@ -145,7 +148,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
         img = _gray(frame.image)
         H, W = img.shape
         pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp,
-                                                                         redetect_start_pose))
+                                                                         redetect_start_pose, detector))
         pipe.set_frame(0, img)
         pipe.set_state(0, frame.features, state.curr_pose, state.prev_pose, num_features=tracker._tracker._num_features)
         trajectory = [np.eye(4), state.get_pose()]
@@ -250,14 +253,14 @@ def _bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win, bootst
                 threshold_px=bootstrap_threshold)
 
 
-def _pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose):
+def _pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector="harris"):
     """The pipeline's configuration for the steady state of main.py:194-201 (what run_on_device documents).  state: the
     bootstrap's State (its bearing threshold), None: State's default."""
     if state is None:
         state = State(None)
     return dict(n_keypoints=n_keypoints, klt_win=klt_win, klt_max_level=klt_max_level, hyp=hyp, p3p_threshold=1.25 ** 2,
                 outlier_ratio=0.9, confidence=0.9999, max_iterations=10000, refine_iters=20,
-                bearing_threshold=state._bearing_threshold, redetect_start_pose=redetect_start_pose)
+                bearing_threshold=state._bearing_threshold, redetect_start_pose=redetect_start_pose, detector=detector)
 
 
 def lane_schedule(lengths, lanes):
@@ -326,7 +329,7 @@ def _frame_shape(sequence):
 def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
                         klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
-                        bootstrap_threshold: float = 0.25, bootstrap: str = "host"):
+                        bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris"):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
     as run_on_device does it; when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
@@ -336,7 +339,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     bootstrap="device": a lane's recording starts from its frames 0 and 2 inside the pipeline instead: for a change of
     recording the lane goes idle, frame 0 goes into the slot after the current one and frame 2 into the current one; the
     lanes that start at the same step (all of them at step 0) then go through ONE call (Pipeline.bootstrap_lanes).  (A
-    recording without a steady-state step never holds a lane: host route.)
+    recording without a steady-state step never holds a lane: host route.)  detector: as in run_on_device, for every lane.
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
     each step the recording took part in).  Each lane computes what run_on_device computes for its recording alone."""
@@ -383,7 +386,8 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
         K0 = np.asarray(sequences[first].get_camera().intrinsic_matrix, np.float64)
         SLOTS = 4
         pipe = _native.Pipeline(ctx, H, W, SLOTS, K0, sequences=lanes,
-                                **_pipeline_kwargs(state0, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose))
+                                **_pipeline_kwargs(state0, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose,
+                                                   detector))
         ring = [[ctx.pinned_empty((H, W)) for _ in range(SLOTS)] for _ in range(lanes)]
         taken = [0] * len(sequences)
 
