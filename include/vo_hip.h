@@ -664,6 +664,39 @@ int vo_pipeline_frame_uploaded(vo_pipeline* p, int idx, int wait);
 int vo_pipeline_prepare(vo_pipeline* p, int idx);
 int vo_host_alloc(vo_ctx* ctx, size_t bytes, void** out);
 int vo_host_free(vo_ctx* ctx, void* p);          /* ctx may be NULL */
+/* ---- frame ingest: three-channel frames and lens undistortion on the device ------------------------------------
+ * What a frame goes through between a camera's buffer and a frame slot.  Both operations are defined in integers and
+ * float64, and tests/frame_ingest_oracle.py computes the same bytes (OpenCV parity is not claimed).
+ *   grey:      g = (1868 B + 9617 G + 4899 R + 8192) >> 14, channels in the order B, G, R -- what cv2.imread hands the
+ *              reference and its cvtColor call sites convert [ref: src/vo/features/klt.py:58-62, harris.py:41-48].
+ *   undistort: the reference's Camera takes distortion coefficients and leaves undistort / distort_points empty
+ *              [ref: src/vo/sensors/camera.py:38-54].  Here: dist = (k1, k2, p1, p2, k3), K the pinhole camera of the
+ *              output, K_raw the intrinsics of the distorted image (NULL: K).  For output pixel (u, v), in float64 without
+ *              contraction:  x = (u - cx) / fx, y = (v - cy) / fy, r2 = x x + y y,
+ *                kr = 1 + ((k3 r2 + k2) r2 + k1) r2,
+ *                xd = (x kr + p1 (2 x) y) + p2 (r2 + 2 x x),  yd = (y kr + p1 (r2 + 2 y y)) + p2 (2 x) y,
+ *                us = fx_raw xd + cx_raw, vs = fy_raw yd + cy_raw;
+ *              the source position is rounded to 1/32 pixel (ties to even, clamped to +-2^24 / 32 first) and the four
+ *              neighbours are blended with the integer weights (32 - a)(32 - b), a (32 - b), (32 - a) b, a b, + 512, >> 10;
+ *              a neighbour outside the image counts as 0.  Non-finite coefficients or intrinsics: VO_EINVAL.
+ * vo_gray_from_bgr / vo_undistort_image: one image, host arrays (bgr H x W x 3, the others H x W bytes).
+ * vo_pipeline_set_distortion_seq: lane seq's coefficients (5 doubles) and K_raw from now on; the pinhole camera is the
+ *   lane's K (vo_pipeline_set_camera_seq), with K_raw NULL also the distorted image's, as it is at each upload.  dist NULL
+ *   or all zero with K_raw NULL: no undistortion.  Nothing may be in flight.  Applies to frames uploaded after the call;
+ *   slots already filled keep their contents.
+ * vo_pipeline_set_frame_bgr_seq / _bgr_pinned: vo_pipeline_set_frame_seq / _pinned for an H x W x 3 image -- same slot
+ *   rules, same events, same pinned bookkeeping.  The slot receives undistort(gray(image)).  The DMA lands in a raw buffer
+ *   (one per stream, made on first use) and the ingest kernel follows it on the same stream -- the tracker's for the plain
+ *   call, the upload stream for the pinned one; what waits for the upload waits for the kernel.  The grey entry points
+ *   undistort too when the lane has coefficients; without them they are one copy and no kernel, as before.
+ * vo_pipeline_get_frame_seq: downloads slot idx of lane seq (H x W bytes).  Nothing may be in flight.               */
+int vo_gray_from_bgr(vo_ctx* ctx, const uint8_t* bgr, int H, int W, uint8_t* gray);
+int vo_undistort_image(vo_ctx* ctx, const uint8_t* img, int H, int W, const double K[9], const double dist[5],
+                       const double K_raw[9], uint8_t* out);
+int vo_pipeline_set_distortion_seq(vo_pipeline* p, int seq, const double dist[5], const double K_raw[9]);
+int vo_pipeline_set_frame_bgr_seq(vo_pipeline* p, int seq, int idx, const uint8_t* bgr);
+int vo_pipeline_set_frame_bgr_pinned(vo_pipeline* p, int seq, int idx, const uint8_t* bgr_pinned);
+int vo_pipeline_get_frame_seq(vo_pipeline* p, int seq, int idx, uint8_t* out);
 int vo_pipeline_set_state_seq(vo_pipeline* p, int seq, int idx, int n, const double* kp, const uint8_t* state,
                               const double* landmarks, const double* tracks, const double* poses,
                               const double* T_wc, const double* T_cw, const double* T_wc_prev,

@@ -68,6 +68,19 @@ struct vo_pipeline {
   std::vector<hipEvent_t> evUp;
   std::vector<char> pinned, plain_used;
   std::vector<int> n_pinned;
+  // Frame ingest (ingest.hip; vo_pipeline_set_frame_bgr_seq / _pinned, vo_pipeline_set_distortion_seq): a frame that is not a
+  // finished grey image is copied into a raw buffer and the ingest kernel writes the slot behind the copy, on the same
+  // stream; evImg / evUp are recorded behind the kernel.  One raw buffer per stream (d_raw[0]: the tracker's, d_raw[1]:
+  // up_stream), reused in stream order; h_bgr: the plain three-channel call's pinned staging, evBgr: its last DMA has read
+  // it.  All of it is made on first use: a pipeline fed grey frames of a pinhole camera has none of it.
+  struct lens_t {
+    bool on = false, have_raw = false;
+    double dist[5] = {0, 0, 0, 0, 0}, K_raw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  };
+  std::vector<lens_t> lens;          // [S] once a lane has been given coefficients (empty: no lane has)
+  uint8_t* d_raw[2] = {nullptr, nullptr};
+  uint8_t* h_bgr = nullptr;
+  hipEvent_t evBgr = nullptr;
   // vo_pipeline_prepare: the pyramid of frame slot prepared_idx sits in pyramid slot prepared_slot, built behind the
   // previous tracker -- the next submit whose `next` is that frame does not build it again (-1: none)
   int prepared_idx = -1, prepared_slot = -1;

@@ -165,6 +165,7 @@ void vo_pipeline_destroy(vo_pipeline* p) {
   (void)hipStreamSynchronize(p->ctx->stream);
   for (vo_ctx* q : {p->det, p->trk})
     if (q) (void)hipStreamSynchronize(q->stream);
+  if (p->up_stream) (void)hipStreamSynchronize(p->up_stream);
   dbg_stage("destroy: streams idle");
   vo_pipeline_boot_free(p);
   for (void* q : p->dev_mem) (void)hipFree(q);
@@ -471,50 +472,134 @@ static int check_frame_slot(vo_pipeline* p, const char* who, int seq, int idx, c
   return VO_OK;
 }
 
+// One frame into slot idx of sequence seq: `channels` = 1 (grey) or 3 (B, G, R) [ref: the cvtColor call sites,
+// src/vo/features/klt.py:58-62, harris.py:41-48], from the caller's pageable (plain) or pinned buffer.
+//   plain:  through a pinned staging buffer -- of this (sequence, slot) for a grey image, one of its own for a
+//           three-channel one --, as one DMA queued on the tracker's stream, in front of the pyramid that reads the slot;
+//           the detector's stream waits for evImg.  The call does not wait for the GPU (the runtime's pageable-memory path
+//           did, and drained the tracker's stream on top: 0.9 ms per frame through the Python API); the caller's buffer is
+//           free on return.
+//   pinned: no staging copy, and the DMA runs on a stream of its own.  The buffer must stay as it is until the upload is
+//           over: vo_pipeline_frame_uploaded(idx), or the collect of a step that read the slot.
+// A grey image of a lane without distortion coefficients is copied straight into the slot.  Anything else lands in the
+// stream's raw buffer and the ingest kernel (ingest.hip) writes the slot behind it on the same stream; the slot's event
+// is recorded behind the kernel, so whoever waits for the upload waits for the ingest.
+static int upload_frame(vo_pipeline* p, const char* who, int seq, int idx, const uint8_t* src, int channels, bool from_pinned) {
+  vo_ctx* ctx = p->ctx;
+  VO_TRY(check_frame_slot(p, who, seq, idx, src));
+  const size_t at = (size_t)seq * p->cfg.n_frames + idx, bytes = (size_t)channels * p->px;
+  vo_undist und;
+  const bool lens = !p->lens.empty() && p->lens[(size_t)seq].on;
+  if (lens) {
+    const vo_pipeline::lens_t& L = p->lens[(size_t)seq];
+    VO_TRY(vo_undist_make(ctx, who, p->cams[(size_t)seq].K, L.dist, L.have_raw ? L.K_raw : nullptr, &und));
+  }
+  const bool direct = channels == 1 && !lens;
+  if (from_pinned && !p->up_stream) VO_HIP_TRY(ctx, hipStreamCreateWithFlags(&p->up_stream, hipStreamNonBlocking));
+  hipStream_t st = from_pinned ? p->up_stream : p->trk->stream;
+  uint8_t* raw = nullptr;
+  if (!direct) {
+    uint8_t*& buf = p->d_raw[from_pinned ? 1 : 0];
+    if (!buf) VO_TRY(dev_alloc(p, &buf, 3 * p->px + 4));
+    // (the grey kernel's dword loads: ingest.hip, vo_ingest_head)
+    raw = buf + (channels == 3 && !lens ? vo_ingest_head(p->img(seq, idx)) : 0);
+  }
+  if (!from_pinned) {
+    if (channels == 1) {
+      uint8_t*& stage = p->h_img[at];
+      if (!stage) VO_TRY(pin_alloc(p, &stage, p->px, hipHostMallocDefault));
+      VO_HIP_TRY(ctx, hipEventSynchronize(p->evImg[idx]));     // (the slot's previous upload has left the staging buffer)
+      memcpy(stage, src, bytes);
+      src = stage;
+    } else {
+      if (!p->h_bgr) VO_TRY(pin_alloc(p, &p->h_bgr, bytes, hipHostMallocDefault));
+      if (!p->evBgr) VO_TRY(make_event(p, &p->evBgr));
+      VO_HIP_TRY(ctx, hipEventSynchronize(p->evBgr));          // (its previous DMA has read it)
+      memcpy(p->h_bgr, src, bytes);
+      src = p->h_bgr;
+    }
+  }
+  char& pin = p->pinned[at];
+  if (from_pinned) {
+    // (a slot the tracker's stream filled last: that copy is in front of everything that read the slot; a step that read it
+    //  has been collected -- the check above --, so nothing on the GPU still reads what this upload overwrites)
+    if (!pin && p->plain_used[idx]) VO_HIP_TRY(ctx, hipStreamWaitEvent(st, p->evImg[idx], 0));   // (an upload the plain call queued)
+  } else if (pin) {
+    VO_HIP_TRY(ctx, hipStreamWaitEvent(st, p->evUp[idx], 0));                                    // (this one lands after the pinned one)
+  }
+  VO_HIP_TRY(ctx, hipMemcpyAsync(direct ? p->img(seq, idx) : raw, src, bytes, hipMemcpyHostToDevice, st));
+  if (!from_pinned && channels == 3) VO_HIP_TRY(ctx, hipEventRecord(p->evBgr, st));
+  int rc = VO_OK;
+  if (!direct) rc = vo_ingest_dev(ctx, st, raw, channels, p->cfg.H, p->cfg.W, lens ? &und : nullptr, p->img(seq, idx));
+  // (recorded even when the launch was refused: the copy above is queued, and the events must cover it)
+  VO_HIP_TRY(ctx, hipEventRecord(from_pinned ? p->evUp[idx] : p->evImg[idx], st));
+  if (from_pinned && !pin) {
+    pin = 1;
+    ++p->n_pinned[idx];
+  } else if (!from_pinned) {
+    if (pin) {
+      pin = 0;
+      --p->n_pinned[idx];
+    }
+    p->plain_used[idx] = 1;
+  }
+  if (p->prepared_idx == idx) p->prepared_idx = p->prepared_slot = -1;
+  return rc;
+}
+
 int vo_pipeline_set_frame_seq(vo_pipeline* p, int seq, int idx, const uint8_t* img) {
+  return p ? upload_frame(p, "pipeline_set_frame", seq, idx, img, 1, false) : VO_EINVAL;
+}
+
+int vo_pipeline_set_frame_pinned(vo_pipeline* p, int seq, int idx, const uint8_t* pinned_img) {
+  return p ? upload_frame(p, "pipeline_set_frame_pinned", seq, idx, pinned_img, 1, true) : VO_EINVAL;
+}
+
+int vo_pipeline_set_frame_bgr_seq(vo_pipeline* p, int seq, int idx, const uint8_t* bgr) {
+  return p ? upload_frame(p, "pipeline_set_frame_bgr", seq, idx, bgr, 3, false) : VO_EINVAL;
+}
+
+int vo_pipeline_set_frame_bgr_pinned(vo_pipeline* p, int seq, int idx, const uint8_t* bgr_pinned) {
+  return p ? upload_frame(p, "pipeline_set_frame_bgr_pinned", seq, idx, bgr_pinned, 3, true) : VO_EINVAL;
+}
+
+// Lane seq's lens from now on [ref: src/vo/sensors/camera.py:38-54: Camera takes distortion coefficients, and its two
+// methods are stubs]: frames uploaded after the call are undistorted into the lane's pinhole camera K (the camera at the
+// time of each upload when K_raw is NULL).  Slots already filled keep their contents.
+int vo_pipeline_set_distortion_seq(vo_pipeline* p, int seq, const double* dist, const double* K_raw) {
   if (!p) return VO_EINVAL;
   vo_ctx* ctx = p->ctx;
-  VO_TRY(check_frame_slot(p, "pipeline_set_frame", seq, idx, img));
-  // Through a pinned staging buffer of this (sequence, slot), as one DMA queued on the tracker's stream -- in front of
-  // the pyramid that reads the slot; the detector's stream waits for evImg.  The call does not wait for the GPU (the
-  // runtime's pageable-memory path did, and drained the tracker's stream on top: 0.9 ms per frame through the Python
-  // API); the caller's buffer is free on return.
-  uint8_t*& stage = p->h_img[(size_t)seq * p->cfg.n_frames + idx];
-  if (!stage) VO_TRY(pin_alloc(p, &stage, p->px, hipHostMallocDefault));
-  VO_HIP_TRY(ctx, hipEventSynchronize(p->evImg[idx]));       // (the slot's previous upload has left the staging buffer)
-  memcpy(stage, img, p->px);
-  char& pin = p->pinned[(size_t)seq * p->cfg.n_frames + idx];
-  if (pin) VO_HIP_TRY(ctx, hipStreamWaitEvent(p->trk->stream, p->evUp[idx], 0));   // (this copy lands after the pinned one)
-  VO_HIP_TRY(ctx, hipMemcpyAsync(p->img(seq, idx), stage, p->px, hipMemcpyHostToDevice, p->trk->stream));
-  VO_HIP_TRY(ctx, hipEventRecord(p->evImg[idx], p->trk->stream));
-  if (pin) {
-    pin = 0;
-    --p->n_pinned[idx];
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_set_distortion: bad sequence index");
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_set_distortion: %d submitted step(s) not collected", p->n_flight);
+  vo_undist und;      // (the checks alone)
+  VO_TRY(vo_undist_make(ctx, "pipeline_set_distortion", p->cams[(size_t)seq].K, dist, K_raw, &und));
+  bool any = false;
+  for (int i = 0; dist && i < 5; ++i) any |= dist[i] != 0.0;
+  vo_pipeline::lens_t L;
+  L.on = any || K_raw;
+  if (L.on && dist) memcpy(L.dist, dist, sizeof(L.dist));
+  if (L.on && K_raw) {
+    L.have_raw = true;
+    memcpy(L.K_raw, K_raw, sizeof(L.K_raw));
   }
-  p->plain_used[idx] = 1;
-  if (p->prepared_idx == idx) p->prepared_idx = p->prepared_slot = -1;
+  if (p->lens.empty()) {
+    if (!L.on) return VO_OK;
+    p->lens.assign((size_t)p->S, vo_pipeline::lens_t());
+  }
+  p->lens[(size_t)seq] = L;
   return VO_OK;
 }
 
-// The same from a buffer the caller holds in pinned memory (vo_host_alloc): no staging copy, and the DMA runs on a
-// stream of its own.  The buffer must stay as it is until the upload is over: vo_pipeline_frame_uploaded(idx), or the
-// collect of a step that read the slot.
-int vo_pipeline_set_frame_pinned(vo_pipeline* p, int seq, int idx, const uint8_t* pinned_img) {
+// what slot idx of sequence seq holds (H * W bytes), i.e. the frame as the tracker and the detector read it
+int vo_pipeline_get_frame_seq(vo_pipeline* p, int seq, int idx, uint8_t* out) {
   if (!p) return VO_EINVAL;
   vo_ctx* ctx = p->ctx;
-  VO_TRY(check_frame_slot(p, "pipeline_set_frame_pinned", seq, idx, pinned_img));
-  if (!p->up_stream) VO_HIP_TRY(ctx, hipStreamCreateWithFlags(&p->up_stream, hipStreamNonBlocking));
-  // (a slot the tracker's stream filled last: that copy is in front of everything that read the slot; a step that read it
-  //  has been collected -- the check above --, so nothing on the GPU still reads what this copy overwrites)
-  char& pin = p->pinned[(size_t)seq * p->cfg.n_frames + idx];
-  if (!pin && p->plain_used[idx]) VO_HIP_TRY(ctx, hipStreamWaitEvent(p->up_stream, p->evImg[idx], 0));   // (a copy vo_pipeline_set_frame queued)
-  VO_HIP_TRY(ctx, hipMemcpyAsync(p->img(seq, idx), pinned_img, p->px, hipMemcpyHostToDevice, p->up_stream));
-  VO_HIP_TRY(ctx, hipEventRecord(p->evUp[idx], p->up_stream));
-  if (!pin) {
-    pin = 1;
-    ++p->n_pinned[idx];
-  }
-  if (p->prepared_idx == idx) p->prepared_idx = p->prepared_slot = -1;
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S && idx >= 0 && idx < p->cfg.n_frames && out, "pipeline_get_frame: bad arguments");
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_get_frame: %d submitted step(s) not collected", p->n_flight);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  VO_HIP_TRY(ctx, hipEventSynchronize(p->evImg[idx]));
+  VO_HIP_TRY(ctx, hipEventSynchronize(p->evUp[idx]));
+  VO_HIP_TRY(ctx, mcpy(ctx->stream, out, p->img(seq, idx), p->px, hipMemcpyDeviceToHost));
   return VO_OK;
 }
 

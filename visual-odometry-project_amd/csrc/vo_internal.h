@@ -143,6 +143,21 @@ struct vo_cam2 {      // the two intrinsic matrices of the two-view bootstrap (b
 };
 
 // ---- internal entry points shared between translation units (not part of the C ABI) ----
+// Frame ingest (ingest.hip).  vo_undist: the undistortion of one camera as the kernel takes it, by value -- the pinhole
+// camera of the output (fx, fy, cx, cy), the intrinsics of the distorted image (..r) and (k1, k2, p1, p2, k3).
+struct vo_undist {
+  double fx, fy, cx, cy, fxr, fyr, cxr, cyr, k1, k2, p1, p2, k3;
+};
+// K, K_raw (NULL: K) row-major 3x3, dist 5 coefficients (NULL: none); refuses non-finite values and a singular K
+int vo_undist_make(vo_ctx* ctx, const char* who, const double* K, const double* dist, const double* K_raw, vo_undist* out);
+// The pixels in front of the first 4-byte boundary of an output image.  The grey kernel loads and stores dwords: a
+// three-channel input goes to its buffer's (4-byte aligned) start + vo_ingest_head(out), so that the first whole group of
+// four pixels starts on a dword in both images (head + 3 * head = 4 * head).
+static inline size_t vo_ingest_head(const void* out) { return (size_t)((4 - ((uintptr_t)out & 3)) & 3); }
+// One launch on `st`: d_in (channels = 1: H x W grey, 3: H x W x 3 B, G, R) -> d_out (H x W grey), undistorted when und is
+// given.  channels = 1 needs und (a plain copy is the caller's).  No synchronisation; ctx only receives an error text.
+int vo_ingest_dev(vo_ctx* ctx, hipStream_t st, const uint8_t* d_in, int channels, int H, int W, const vo_undist* und,
+                  uint8_t* d_out);
 // How a context's own stream is created.  cu_lo..cu_hi: its kernels run on those compute units only (cu_hi < cu_lo: no
 // mask); priority: -1 / +1 the least / greatest the device offers, 0 the default -- a mask wins over a priority.
 struct vo_stream_cfg {

@@ -230,6 +230,12 @@ _SIGS = {
     "vo_pipeline_prepare": (_i, [_vp, _i]),
     "vo_host_alloc": (_i, [_vp, C.c_size_t, C.POINTER(C.c_void_p)]),
     "vo_host_free": (_i, [_vp, _vp]),
+    "vo_gray_from_bgr": (_i, [_vp, _vp, _i, _i, _vp]),
+    "vo_undistort_image": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "vo_pipeline_set_distortion_seq": (_i, [_vp, _i, _vp, _vp]),
+    "vo_pipeline_set_frame_bgr_seq": (_i, [_vp, _i, _i, _vp]),
+    "vo_pipeline_set_frame_bgr_pinned": (_i, [_vp, _i, _i, _vp]),
+    "vo_pipeline_get_frame_seq": (_i, [_vp, _i, _i, _vp]),
     "vo_pipeline_set_state_seq": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "vo_pipeline_get_state_seq": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_pipeline_get_rng_seq": (_i, [_vp, _i, _vp]),
@@ -243,6 +249,16 @@ _SIGS = {
     "vo_pipeline_bootstrap_lanes": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "vo_bootstrap_default_rng": (None, [_vp]),
 }
+
+
+def distortion_coefficients(dist):
+    """(k1, k2, p1, p2, k3) as five float64; None: zeros; four coefficients: k3 = 0.  The model has no more."""
+    d = np.zeros(5, np.float64) if dist is None else np.asarray(dist, np.float64).reshape(-1)
+    if d.size > 5:
+        raise ValueError("%d distortion coefficients: the model is (k1, k2, p1, p2, k3), five at most (four: k3 = 0)" % d.size)
+    if d.size not in (4, 5):
+        raise ValueError("%d distortion coefficients: the model takes (k1, k2, p1, p2) or (k1, k2, p1, p2, k3)" % d.size)
+    return np.ascontiguousarray(np.concatenate((d, np.zeros(5 - d.size))))
 
 
 def lib_path():
@@ -418,6 +434,29 @@ class Context:
         self._chk(self._lib.vo_match_knn2_ratio(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0],
                                                 max(q.shape[1], 1), float(ratio), _ptr(pairs), C.byref(n)))
         return pairs[: n.value].astype(np.int64)
+
+    # ---- frame ingest (csrc/ingest.hip) ----
+    def gray_from_bgr(self, bgr):
+        """(H, W, 3) uint8, channels B, G, R -> (H, W) uint8: (1868 B + 9617 G + 4899 R + 8192) >> 14."""
+        bgr = _c(bgr, np.uint8)
+        assert bgr.ndim == 3 and bgr.shape[2] == 3
+        H, W = bgr.shape[:2]
+        out = np.empty((H, W), np.uint8)
+        self._chk(self._lib.vo_gray_from_bgr(self._h, _ptr(bgr), H, W, _ptr(out)))
+        return out
+
+    def undistort_image(self, img, K, dist, K_raw=None):
+        """(H, W) uint8 of a camera with intrinsics K_raw (None: K) and distortion dist = (k1, k2, p1, p2[, k3]) -> the
+        image of the pinhole camera K (vo_undistort_image: 1/32-pixel bilinear taps, zero border)."""
+        img = _c(img, np.uint8)
+        assert img.ndim == 2
+        H, W = img.shape
+        K = _c(np.asarray(K, np.float64).reshape(3, 3), np.float64)
+        Kr = None if K_raw is None else _c(np.asarray(K_raw, np.float64).reshape(3, 3), np.float64)
+        d = distortion_coefficients(dist)
+        out = np.empty((H, W), np.uint8)
+        self._chk(self._lib.vo_undistort_image(self._h, _ptr(img), H, W, _ptr(K), _ptr(d), _ptr(Kr), _ptr(out)))
+        return out
 
     def pinned_empty(self, shape, dtype=np.uint8):
         """A NumPy array in pinned host memory (vo_host_alloc): what Pipeline.set_frame(..., pinned=True) uploads from

@@ -93,18 +93,37 @@ class Pipeline:
 
     # ---- inputs ----
     def set_frame(self, idx, img, seq=0, pinned=None):
-        """Frame slot idx <- img.  pinned: img lies in Context.pinned_empty memory and is uploaded from there (no staging
+        """Frame slot idx <- img: (H, W) grey or (H, W, 3) B, G, R, uint8.  The slot receives the grey image, undistorted
+        when the lane has coefficients (set_distortion): a three-channel or distorted frame is converted by the ingest
+        kernel behind its DMA.  pinned: img lies in Context.pinned_empty memory and is uploaded from there (no staging
         copy, DMA beside the kernels; img must stay unchanged until frame_uploaded(idx) or the collect of a step that
         read the slot); None: decided by where img lies."""
         img = _c(img, np.uint8)
-        assert img.shape == (self.cfg.H, self.cfg.W)
+        assert img.shape in ((self.cfg.H, self.cfg.W), (self.cfg.H, self.cfg.W, 3))
+        lib = self.ctx._lib
         if pinned is None:
             pinned = self.ctx.is_pinned(img)
         if pinned:
             self._pinned_src[(int(seq), int(idx))] = img          # (kept alive while the DMA may read it)
-            self.ctx._chk(self.ctx._lib.vo_pipeline_set_frame_pinned(self._h, int(seq), int(idx), _ptr(img)))
+            fn = lib.vo_pipeline_set_frame_pinned if img.ndim == 2 else lib.vo_pipeline_set_frame_bgr_pinned
         else:
-            self.ctx._chk(self.ctx._lib.vo_pipeline_set_frame_seq(self._h, int(seq), int(idx), _ptr(img)))
+            fn = lib.vo_pipeline_set_frame_seq if img.ndim == 2 else lib.vo_pipeline_set_frame_bgr_seq
+        self.ctx._chk(fn(self._h, int(seq), int(idx), _ptr(img)))
+
+    def set_distortion(self, seq, dist, K_raw=None):
+        """Lane `seq`'s lens (vo_pipeline_set_distortion_seq; nothing in flight): dist = (k1, k2, p1, p2[, k3]) or None,
+        K_raw the intrinsics of the distorted image (None: the lane's K).  Frames uploaded afterwards are undistorted
+        into the lane's pinhole camera; None / all zero without K_raw switches it off."""
+        from vo import _native
+        d = None if dist is None else _native.distortion_coefficients(dist)
+        Kr = None if K_raw is None else _c(np.asarray(K_raw, np.float64).reshape(3, 3), np.float64)
+        self.ctx._chk(self.ctx._lib.vo_pipeline_set_distortion_seq(self._h, int(seq), _ptr(d), _ptr(Kr)))
+
+    def get_frame(self, idx, seq=0):
+        """What frame slot idx of lane `seq` holds, (H, W) uint8 (nothing in flight)."""
+        out = np.empty((self.cfg.H, self.cfg.W), np.uint8)
+        self.ctx._chk(self.ctx._lib.vo_pipeline_get_frame_seq(self._h, int(seq), int(idx), _ptr(out)))
+        return out
 
     def prepare(self, idx):
         """Hint: frame slot idx is the `next` of the coming submit -- its pyramid is built now, off that step's critical

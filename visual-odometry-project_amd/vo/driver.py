@@ -124,17 +124,23 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     the re-detect limit follows that count (klt.py:114).
     bootstrap: "host" -- the bootstrap through the drop-in classes, handed over with set_state; "device" -- frames 0 and 2
     go into two slots of the frame store and the pipeline bootstraps itself from them (Pipeline.bootstrap,
-    vo_pipeline_bootstrap_seq): same kernels, same result, no array brought back in between."""
+    vo_pipeline_bootstrap_seq): same kernels, same result, no array brought back in between.
+    Frames are uploaded as the sequence delivers them, grey or B, G, R; the pipeline's ingest makes them grey on the device.
+    A camera with distortion_coeffs sets the lane's distortion (Pipeline.set_distortion: every frame is undistorted into
+    the pinhole camera K behind its upload); one that really distorts needs bootstrap="device"."""
     from vo import _native
     _check_bootstrap_route(bootstrap)
     ctx = context or _native.default_context()
     K = np.asarray(sequence.get_camera().intrinsic_matrix, np.float64)
+    dist = _lens_of(sequence, bootstrap)
     SLOTS = 4
     if bootstrap == "device":
-        img0, img = _bootstrap_frames(sequence)
-        H, W = img.shape
+        img0, img = _bootstrap_images(sequence)          # (as delivered: the pipeline's ingest makes them grey, undistorted)
+        H, W = img.shape[:2]
         pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(None, n_keypoints, klt_win, klt_max_level, hyp,
                                                                          redetect_start_pose, detector))
+        if dist is not None:
+            pipe.set_distortion(0, dist)
         pipe.set_frame(1, img0)                          # (slot 1 takes frame 3 next: the bootstrap is done with it by then)
         pipe.set_frame(0, img)
         boot = pipe.bootstrap(1, 0, **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
@@ -154,11 +160,12 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
         trajectory = [np.eye(4), state.get_pose()]
         n_landmarks = [len(frame.features.triangulated_inliers_landmarks)]
     seconds, results = [], []
-    # Frames go through a ring of pinned buffers (the grey conversion writes into them) and are uploaded on the
-    # pipeline's upload stream ONE STEP AHEAD of their use (vo_pipeline_set_frame_pinned): while step k -> k+1 runs,
-    # frame k+2 -- read ahead from the sequence, as a file or dataset reader can -- crosses PCIe beside it.  One frame
-    # of look-ahead on the results as before: the pose of frame k is read back after frame k+1 has been submitted.
-    ring = [ctx.pinned_empty((H, W)) for _ in range(SLOTS)]
+    # Frames go through a ring of pinned buffers AS DELIVERED (three channels where the sequence gives three: the grey
+    # conversion and the undistortion run on the device behind the DMA, csrc/ingest.hip) and are uploaded on the
+    # pipeline's upload stream ONE STEP AHEAD of their use (vo_pipeline_set_frame_pinned / _bgr_pinned): while step
+    # k -> k+1 runs, frame k+2 -- read ahead from the sequence, as a file or dataset reader can -- crosses PCIe beside it.
+    # One frame of look-ahead on the results as before: the pose of frame k is read back after frame k+1 has been submitted.
+    ring = [None] * SLOTS
     frames = iter(sequence)
     taken = 0
 
@@ -172,7 +179,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
         return f
 
     def put(s, f):
-        ring[s][...] = _gray(f.image)
+        _into_ring(ctx, ring, s, f.image)
         pipe.set_frame(s, ring[s], pinned=True)
 
     slot, pending = 0, 0
@@ -244,6 +251,32 @@ def _bootstrap_frames(sequence):
     first = next(sequence)
     next(sequence)
     return _gray(first.image), _gray(next(sequence).image)
+
+
+def _bootstrap_images(sequence):
+    """Frames 0 and 2 of a recording as the sequence delivers them (grey or three-channel)."""
+    first = next(sequence)
+    next(sequence)
+    return first.image, next(sequence).image
+
+
+def _into_ring(ctx, ring, s, image):
+    """image -> ring[s], a pinned buffer of its shape (made when the slot has none of that shape yet)."""
+    if ring[s] is None or ring[s].shape != image.shape:
+        ring[s] = ctx.pinned_empty(image.shape)
+    ring[s][...] = image
+
+
+def _lens_of(sequence, bootstrap):
+    """The distortion coefficients of a recording's camera (None: a pinhole camera, nothing to set).  The host bootstrap
+    works on the frames as delivered, so a camera that really distorts needs the device route, where the bootstrap's two
+    frames go through the pipeline's ingest like every other."""
+    cam = sequence.get_camera()
+    dist = getattr(cam, "distortion_coeffs", None)
+    if dist is not None and bootstrap != "device" and cam._distortion() is not None:
+        raise ValueError("a camera with distortion coefficients needs bootstrap='device': the host bootstrap does not "
+                         "undistort its frames")
+    return dist
 
 
 def _bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold):
@@ -336,6 +369,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     goes idle (vo_pipeline_set_active_seq) -- lane_schedule says when.  Frames go through one pinned ring per lane,
     uploaded a step ahead.  The steps in flight are drained before a lane changes recording (nothing may be in flight for
     the three calls), so each such step loses the look-ahead once.  All recordings must have the same frame size.
+    A recording whose camera has distortion_coeffs sets its lane's distortion (Pipeline.set_distortion) at every start.
     bootstrap="device": a lane's recording starts from its frames 0 and 2 inside the pipeline instead: for a change of
     recording the lane goes idle, frame 0 goes into the slot after the current one and frame 2 into the current one; the
     lanes that start at the same step (all of them at step 0) then go through ONE call (Pipeline.bootstrap_lanes).  (A
@@ -388,7 +422,14 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
         pipe = _native.Pipeline(ctx, H, W, SLOTS, K0, sequences=lanes,
                                 **_pipeline_kwargs(state0, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose,
                                                    detector))
-        ring = [[ctx.pinned_empty((H, W)) for _ in range(SLOTS)] for _ in range(lanes)]
+        ring = [[None] * SLOTS for _ in range(lanes)]      # (frames as delivered, see run_on_device)
+        lens = [_lens_of(s, bootstrap) for s in sequences]
+        any_lens = any(d is not None for d in lens)
+
+        def set_lens(lane, r):
+            # (every start: a lane that held a distorting camera's recording must lose its coefficients with it)
+            if any_lens:
+                pipe.set_distortion(lane, lens[r])
         taken = [0] * len(sequences)
 
         def next_frame(r):
@@ -396,15 +437,16 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
             return next(sequences[r])
 
         def put(lane, s, r):
-            ring[lane][s][...] = _gray(next_frame(r).image)
+            _into_ring(ctx, ring[lane], s, next_frame(r).image)
             pipe.set_frame(s, ring[lane][s], seq=lane, pinned=True)
 
         def start_on_device(starts, t, slot):
             """The lanes that start a recording at this step -- starts: (lane, recording) -- through ONE bootstrap call."""
             a = (slot + 1) % SLOTS                       # (the slot the recordings' next frames take afterwards)
             for lane, r in starts:
-                img0, img2 = _bootstrap_frames(sequences[r])
+                img0, img2 = _bootstrap_images(sequences[r])
                 pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
+                set_lens(lane, r)
                 if t > 0:
                     pipe.set_active(lane, False)         # (the lane's frame in the current slot can only be replaced while idle)
                 pipe.set_frame(a, img0, seq=lane, pinned=False)
@@ -423,6 +465,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
             open_result(r)
             frame = state.curr_frame
             pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
+            set_lens(lane, r)
             args = (frame.features, state.curr_pose, state.prev_pose)
             nf = tracker._tracker._num_features
             if t == 0:

@@ -29,11 +29,44 @@ class Camera:
         self._require_pose()
         return np.vstack((np.hstack((self.R, self.t)), [0, 0, 0, 1]))
 
-    def distort_points(self, points: np.ndarray) -> np.ndarray:      # camera.py:38-45 (unimplemented there too)
-        pass
+    def _distortion(self):
+        """(k1, k2, p1, p2, k3), or None for a pinhole camera (no coefficients, or all zero)."""
+        if self.distortion_coeffs is None:
+            return None
+        from vo._native import distortion_coefficients
+        d = distortion_coefficients(self.distortion_coeffs)
+        return d if np.any(d != 0.0) else None
 
-    def undistort(self, image: np.ndarray) -> np.ndarray:            # camera.py:47-54
-        pass
+    def distort_points(self, points: np.ndarray) -> np.ndarray:
+        """(N, 2, 1) ideal pixels -> (N, 2, 1) pixels of the distorted image, by the forward model
+        (k1, k2, p1, p2, k3) with the same intrinsics on both sides (camera.py:38-45 declares it and leaves it empty)."""
+        d = self._distortion()
+        if d is None:
+            return points
+        k1, k2, p1, p2, k3 = (float(v) for v in d)
+        K = np.asarray(self.intrinsic_matrix, np.float64)
+        fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        pts = np.asarray(points, np.float64)
+        x, y = (pts[:, 0, 0] - cx) / fx, (pts[:, 1, 0] - cy) / fy
+        x2, y2 = x * x, y * y
+        r2, _2xy = x2 + y2, (2 * x) * y
+        kr = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+        xd = (x * kr + p1 * _2xy) + p2 * (r2 + 2 * x2)
+        yd = (y * kr + p1 * (r2 + 2 * y2)) + p2 * _2xy
+        return np.stack((fx * xd + cx, fy * yd + cy), axis=1)[:, :, np.newaxis]
+
+    def undistort(self, image: np.ndarray, context=None) -> np.ndarray:
+        """The image of the pinhole camera K from one of this (distorted) camera, on the device (vo_undistort_image;
+        camera.py:47-54 declares it and leaves it empty): (H, W) uint8, or (H, W, C) channel by channel."""
+        d = self._distortion()
+        if d is None:
+            return image
+        from vo import _native
+        ctx = context or _native.default_context()
+        image = np.asarray(image)
+        if image.ndim == 2:
+            return ctx.undistort_image(image, self.intrinsic_matrix, d)
+        return np.stack([ctx.undistort_image(image[..., c], self.intrinsic_matrix, d) for c in range(image.shape[2])], axis=2)
 
     def project_points_world_frame(self, points_3d: np.ndarray) -> np.ndarray:
         """(N, 3, 1) world points -> (N, 2, 1) pixels (camera.py:56-65)."""
