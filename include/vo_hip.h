@@ -255,6 +255,19 @@ int vo_match_knn2_ratio(vo_ctx* ctx, const float* q, int nq, const float* t, int
                         double ratio, int32_t* pairs, int32_t* n_pairs);
 int vo_knn2_dev(vo_ctx* ctx, const float* d_q, int nq, const float* d_t, int nt, int D,
                 int32_t* d_best, double* d_d2);
+/* The two nearest neighbours themselves, before the ratio test
+ * [ref: src/vo/features/harris.py:246-249, src/vo/features/sift.py:38-44: the (m, n) pairs knnMatch returns].
+ * Host pointers, like vo_match_knn2_ratio, and the same choice of kernel: best: nq*2 train
+ * indices (nearest, second nearest; -1 where absent), d2: nq*2 squared distances as float64
+ * (0.0 where absent), ordered by (squared distance, train index).  *path: the kernel whose
+ * result was kept -- VO_MATCH_PATH_FLOAT (float64 accumulation in index order),
+ * VO_MATCH_PATH_BYTE_DOT (packed byte dot product) or VO_MATCH_PATH_MFMA (matrix cores,
+ * D = 128 or 361); -1 when nq or nt is 0 and no kernel ran.  vo_match_last_path: the same
+ * for the context's last vo_match_knn2_ratio / vo_match_knn2 call.                      */
+enum { VO_MATCH_PATH_FLOAT = 0, VO_MATCH_PATH_BYTE_DOT = 1, VO_MATCH_PATH_MFMA = 2 };
+int vo_match_knn2(vo_ctx* ctx, const float* q, int nq, const float* t, int nt, int D,
+                  int32_t* best, double* d2, int* path);
+int vo_match_last_path(vo_ctx* ctx);
 
 /* ---- Shi-Tomasi corners -----------------------------------------------------------
  * [ref: src/vo/features/klt.py:98]  cv2.goodFeaturesToTrack(img, mask, maxCorners,

@@ -30,30 +30,6 @@ def cameras():
             Camera(intrinsic_matrix=K, R=R, t=np.array([[1.0, 1.0, -1.0]]).T))
 
 
-# ---------------- matcher ----------------
-@pytest.mark.parametrize("nq,nt,D,ratio", [(300, 280, 361, 0.85), (500, 700, 128, 0.8), (5, 3, 128, 0.8), (40, 1, 16, 0.9)])
-def test_matcher_bytes_matches_oracle(ctx, nq, nt, D, ratio):
-    rng = np.random.default_rng(nq + D)
-    t = rng.integers(0, 256, size=(nt, D)).astype(np.float32)
-    q = t[rng.integers(0, nt, size=nq)] + rng.integers(-12, 13, size=(nq, D))
-    q = np.clip(q, 0, 255).astype(np.float32)
-    q[::7] = rng.integers(0, 256, size=q[::7].shape)                      # unrelated queries
-    q[1] = q[0]                                                           # duplicate query: uniqueness filter
-    ref, _, _ = native.match_knn2_ratio(q, t, ratio)
-    got = ctx.match_knn2_ratio(q, t, ratio)
-    assert np.array_equal(got, ref)
-    assert len(set(got[:, 1])) == len(got)
-
-
-def test_matcher_float_path_matches_oracle(ctx):
-    rng = np.random.default_rng(3)
-    t = rng.normal(size=(150, 32)).astype(np.float32)
-    q = (t[rng.integers(0, 150, size=120)] + rng.normal(scale=0.05, size=(120, 32))).astype(np.float32)
-    ref, _, _ = native.match_knn2_ratio(q, t, 0.8)
-    assert np.array_equal(ctx.match_knn2_ratio(q, t, 0.8), ref)
-    assert ctx.match_knn2_ratio(np.zeros((0, 8), np.float32), t[:, :8], 0.8).shape == (0, 2)
-
-
 # ---------------- Shi-Tomasi ----------------
 @pytest.mark.parametrize("shape,seed", [((120, 160), 1), ((240, 320), 2), ((97, 131), 3)])
 def test_good_features_match_oracle(ctx, shape, seed):

@@ -407,18 +407,17 @@ int vo_knn2_dev(vo_ctx* ctx, const float* d_q, int nq, const float* d_t, int nt,
   return vo_check_launch(ctx, "knn2_f32_kernel");
 }
 
-// Frame-pipeline form (SIFT / Harris tracker modes, sift.py:38-54, harris.py:246-262): descriptor rows of row_bytes
-// already on the device, the two counts too (d_nq, d_nt; the launches are sized for cap_q / cap_t).  Pairs (query, train)
-// in query order -> d_pairs (cap_q x 2), their number -> *d_npairs.  Asynchronous on the context's stream;
-// scratch[10..13] and match_arrived of the context.
-// S sequences in one launch each: sequence z's queries at d_q + z * q_stride (bytes), its query count at d_nq + z * nq_stride
-// (ints), its train rows / count likewise, its pairs at d_pairs + z * 2 * cap_q and its pair count at d_npairs[z].  Every
-// sequence is split and merged exactly as a one-sequence call of the same capacities.
-int vo_match_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride, int cap_q,
-                          const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride, int cap_t, int S,
-                          double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes) {
+// The 2-NN lists of the frame-pipeline form (SIFT / Harris tracker modes, sift.py:38-54, harris.py:246-262): descriptor
+// rows of row_bytes already on the device, the two counts too (d_nq, d_nt; the launch is sized for cap_q / cap_t).
+// S sequences in one launch: sequence z's queries at d_q + z * q_stride (bytes), its query count at d_nq + z * nq_stride
+// (ints), its train rows / count likewise; its lists at d_best / d_d2 + z * 2 * cap_q (nearest, second nearest train index,
+// -1 / 0.0 where absent; rows past the query count are not written).  Every sequence is split and merged exactly as a
+// one-sequence call of the same capacities.  Asynchronous on the context's stream; scratch[13] and match_arrived of the context.
+int vo_knn2_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride, int cap_q,
+                         const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride, int cap_t, int S,
+                         int row_bytes, int32_t* d_best, double* d_d2) {
   if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, d_q && d_nq && d_t && d_nt && d_pairs && d_npairs && cap_q >= 1 && cap_t >= 1 && S >= 1 && S <= 65535,
+  VO_REQUIRE(ctx, d_q && d_nq && d_t && d_nt && d_best && d_d2 && cap_q >= 1 && cap_t >= 1 && S >= 1 && S <= 65535,
              "match_u8_dev: bad arguments");
   VO_REQUIRE(ctx, row_bytes == 128 || row_bytes == 384, "match_u8_dev: rows of 128 (SIFT) or 384 (19x19 patches, padded) bytes");
   VO_REQUIRE(ctx, S == 1 || (q_stride >= (size_t)cap_q * row_bytes && t_stride >= (size_t)cap_t * row_bytes),
@@ -430,28 +429,48 @@ int vo_match_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, cons
   const int qblocks = vo_cdiv(cap_q, 32), ttiles = vo_cdiv(cap_t, 32);
   int splits = 1;
   while (qblocks * splits < 512 && ttiles / (splits * 2) >= 4) splits *= 2;
-  VO_TRY(vo_ensure(ctx, s[10], Sz * cap_q * 8));                          // best
-  VO_TRY(vo_ensure(ctx, s[11], Sz * cap_q * 16));                         // d2
-  VO_TRY(vo_ensure(ctx, s[12], Sz * cap_t * 4));                          // owner
   VO_TRY(vo_ensure(ctx, s[13], Sz * qblocks * splits * 64 * 8));          // partial top-2 lists
   if (ctx->match_arrived.cap < Sz * qblocks * 4) {                        // (zero once: the kernel leaves them at zero)
     VO_TRY(vo_ensure(ctx, ctx->match_arrived, Sz * qblocks * 4));
     VO_HIP_TRY(ctx, hipMemsetAsync(ctx->match_arrived.p, 0, ctx->match_arrived.cap, st));
   }
-  VO_HIP_TRY(ctx, hipMemsetAsync(s[12].p, 0x7f, Sz * cap_t * 4, st));
-  VO_HIP_TRY(ctx, hipMemsetAsync(d_npairs, 0, Sz * 4, st));
   {
     vo_prof_scope ps(ctx, VO_K_MATCH);
     if (row_bytes == 128)
       hipLaunchKernelGGL(knn2_mfma_kernel<4>, dim3(qblocks, splits, S), dim3(256), 0, st, d_q, cap_q, d_t, cap_t,
-                         (unsigned long long*)s[13].p, (unsigned*)ctx->match_arrived.p, (int*)s[10].p, (double*)s[11].p,
+                         (unsigned long long*)s[13].p, (unsigned*)ctx->match_arrived.p, (int*)d_best, d_d2,
                          (const int*)d_nq, (const int*)d_nt, q_stride, t_stride, nq_stride, nt_stride);
     else
       hipLaunchKernelGGL(knn2_mfma_kernel<12>, dim3(qblocks, splits, S), dim3(256), 0, st, d_q, cap_q, d_t, cap_t,
-                         (unsigned long long*)s[13].p, (unsigned*)ctx->match_arrived.p, (int*)s[10].p, (double*)s[11].p,
+                         (unsigned long long*)s[13].p, (unsigned*)ctx->match_arrived.p, (int*)d_best, d_d2,
                          (const int*)d_nq, (const int*)d_nt, q_stride, t_stride, nq_stride, nt_stride);
   }
-  VO_TRY(vo_check_launch(ctx, "knn2_mfma_kernel"));
+  return vo_check_launch(ctx, "knn2_mfma_kernel");
+}
+
+// ... followed by the ratio test and the uniqueness filter: pairs (query, train) in query order -> d_pairs + z * 2 * cap_q
+// (cap_q x 2 per sequence), their number -> d_npairs[z].  Asynchronous on the context's stream; scratch[10..13] and
+// match_arrived of the context.
+int vo_match_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride, int cap_q,
+                          const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride, int cap_t, int S,
+                          double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, d_q && d_nq && d_t && d_nt && d_pairs && d_npairs && cap_q >= 1 && cap_t >= 1 && S >= 1 && S <= 65535,
+             "match_u8_dev: bad arguments");
+  VO_REQUIRE(ctx, row_bytes == 128 || row_bytes == 384, "match_u8_dev: rows of 128 (SIFT) or 384 (19x19 patches, padded) bytes");
+  VO_REQUIRE(ctx, S == 1 || (q_stride >= (size_t)cap_q * row_bytes && t_stride >= (size_t)cap_t * row_bytes),
+             "match_u8_dev: per-sequence blocks overlap");        // (a refused call touches nothing)
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  vo_buf* s = ctx->scratch;
+  const size_t Sz = (size_t)S;
+  VO_TRY(vo_ensure(ctx, s[10], Sz * cap_q * 8));                          // best
+  VO_TRY(vo_ensure(ctx, s[11], Sz * cap_q * 16));                         // d2
+  VO_TRY(vo_ensure(ctx, s[12], Sz * cap_t * 4));                          // owner
+  VO_HIP_TRY(ctx, hipMemsetAsync(s[12].p, 0x7f, Sz * cap_t * 4, st));
+  VO_HIP_TRY(ctx, hipMemsetAsync(d_npairs, 0, Sz * 4, st));
+  VO_TRY(vo_knn2_u8_batch_dev(ctx, d_q, q_stride, d_nq, nq_stride, cap_q, d_t, t_stride, d_nt, nt_stride, cap_t, S, row_bytes,
+                              (int32_t*)s[10].p, (double*)s[11].p));
   hipLaunchKernelGGL(ratio_unique_kernel, dim3(S), dim3(RU_T), 0, st, (const int*)s[10].p, (const double*)s[11].p, cap_q,
                      ratio, (int*)s[12].p, (int*)d_pairs, (int*)d_npairs, (const int*)d_nq, cap_t, nq_stride);
   return vo_check_launch(ctx, "ratio_unique_kernel");
@@ -462,14 +481,19 @@ int vo_match_u8_dev(vo_ctx* ctx, const uint8_t* d_q, const int32_t* d_nq, int ca
   return vo_match_u8_batch_dev(ctx, d_q, 0, d_nq, 0, cap_q, d_t, 0, d_nt, 0, cap_t, 1, ratio, d_pairs, d_npairs, row_bytes);
 }
 
-int vo_match_knn2_ratio(vo_ctx* ctx, const float* q, int nq, const float* t, int nt, int D, double ratio,
-                        int32_t* pairs, int32_t* n_pairs) {
-  if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, pairs && n_pairs, "match_knn2_ratio: null pointer");
-  *n_pairs = 0;
-  VO_REQUIRE(ctx, nq >= 0 && nt >= 0 && D >= 1, "match_knn2_ratio: bad arguments");
-  if (nq == 0 || nt == 0) return VO_OK;
-  VO_REQUIRE(ctx, q && t, "match_knn2_ratio: null pointer");
+int vo_match_last_path(vo_ctx* ctx) { return ctx ? ctx->match_last_path : -1; }
+
+}  // extern "C"
+
+namespace {
+
+// What vo_match_knn2_ratio and vo_match_knn2 share: the descriptors go up, the kernel is chosen and launched -- the MFMA
+// kernel for D = 128 / 361, the byte-dot kernel for any other length, and the float kernel when the bytes cannot hold the
+// input (a value that is no whole number in 0..255, or a length whose distances pass 2^31).  The 2-NN lists of the result
+// that counts are left in scratch[2] (best) and scratch[3] (d2), the kernel that made them in *path and in the context
+// (vo_match_last_path).  With `ratio` given the ratio test and the uniqueness filter follow each kernel: pairs at
+// scratch[8], their number in *n_pairs.  Synchronises.
+int knn2_host(vo_ctx* ctx, const float* q, int nq, const float* t, int nt, int D, const double* ratio, int* n_pairs, int* path) {
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   vo_buf* s = ctx->scratch;
@@ -496,8 +520,9 @@ int vo_match_knn2_ratio(vo_ctx* ctx, const float* q, int nq, const float* t, int
   unsigned* d_flag = (unsigned*)(d_n + 1);
   VO_HIP_TRY(ctx, hipMemsetAsync(d_n, 0, 8, st));
   auto filter = [&]() -> int {
+    if (!ratio) return VO_OK;
     VO_HIP_TRY(ctx, hipMemsetAsync(s[7].p, 0x7f, (size_t)nt * 4, st));     // 0x7f7f7f7f: above every query index
-    hipLaunchKernelGGL(ratio_unique_kernel, dim3(1), dim3(RU_T), 0, st, (const int*)s[2].p, (const double*)s[3].p, nq, ratio,
+    hipLaunchKernelGGL(ratio_unique_kernel, dim3(1), dim3(RU_T), 0, st, (const int*)s[2].p, (const double*)s[3].p, nq, *ratio,
                        (int*)s[7].p, d_pairs, d_n);
     return vo_check_launch(ctx, "ratio_unique_kernel");
   };
@@ -547,12 +572,55 @@ int vo_match_knn2_ratio(vo_ctx* ctx, const float* q, int nq, const float* t, int
     VO_HIP_TRY(ctx, hipMemcpyAsync(host, d_n, 4, hipMemcpyDeviceToHost, st));
     VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   }
-  const int n = host[0];
+  *n_pairs = host[0];
+  *path = float_path ? VO_MATCH_PATH_FLOAT : mfma ? VO_MATCH_PATH_MFMA : VO_MATCH_PATH_BYTE_DOT;
+  ctx->match_last_path = *path;
+  return VO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vo_match_knn2_ratio(vo_ctx* ctx, const float* q, int nq, const float* t, int nt, int D, double ratio,
+                        int32_t* pairs, int32_t* n_pairs) {
+  if (!ctx) return VO_EINVAL;
+  ctx->match_last_path = -1;
+  VO_REQUIRE(ctx, pairs && n_pairs, "match_knn2_ratio: null pointer");
+  *n_pairs = 0;
+  VO_REQUIRE(ctx, nq >= 0 && nt >= 0 && D >= 1, "match_knn2_ratio: bad arguments");
+  if (nq == 0 || nt == 0) return VO_OK;
+  VO_REQUIRE(ctx, q && t, "match_knn2_ratio: null pointer");
+  int n = 0, path = -1;
+  VO_TRY(knn2_host(ctx, q, nq, t, nt, D, &ratio, &n, &path));
   if (n > 0) {
-    VO_HIP_TRY(ctx, hipMemcpyAsync(pairs, d_pairs, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+    VO_HIP_TRY(ctx, hipMemcpyAsync(pairs, ctx->scratch[8].p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    VO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   *n_pairs = n;
+  return VO_OK;
+}
+
+int vo_match_knn2(vo_ctx* ctx, const float* q, int nq, const float* t, int nt, int D, int32_t* best, double* d2, int* path) {
+  if (!ctx) return VO_EINVAL;
+  ctx->match_last_path = -1;
+  VO_REQUIRE(ctx, best && d2 && path, "match_knn2: null pointer");
+  *path = -1;
+  VO_REQUIRE(ctx, nq >= 0 && nt >= 0 && D >= 1, "match_knn2: bad arguments");
+  if (nq == 0) return VO_OK;
+  if (nt == 0) {                                          // no neighbour at all: no kernel runs
+    for (int i = 0; i < 2 * nq; ++i) {
+      best[i] = -1;
+      d2[i] = 0.0;
+    }
+    return VO_OK;
+  }
+  VO_REQUIRE(ctx, q && t, "match_knn2: null pointer");
+  int n = 0;
+  VO_TRY(knn2_host(ctx, q, nq, t, nt, D, nullptr, &n, path));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(best, ctx->scratch[2].p, (size_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(d2, ctx->scratch[3].p, (size_t)nq * 16, hipMemcpyDeviceToHost, ctx->stream));
+  VO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return VO_OK;
 }
 

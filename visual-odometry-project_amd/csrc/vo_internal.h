@@ -59,6 +59,7 @@ struct vo_ctx {
   float* nms_kp_f32 = nullptr;   // optional: the NMS also writes its keypoints as float pairs here (device)
   vo_buf scratch[16];
   vo_buf match_arrived;          // knn2_mfma_kernel's per-query-block arrival counters (zero between calls)
+  int match_last_path = -1;      // the kernel the last vo_match_knn2_ratio / vo_match_knn2 kept (VO_MATCH_PATH_*; -1: none ran)
   bool lds_opt_in[2] = {false, false};         // hipFuncSetAttribute is per device: remembered per context (response, NMS)
   hipStream_t aux_stream = nullptr;            // vo_sift: the octaves' last two layers and extrema run beside the next octave
   hipStream_t aux_stream2 = nullptr;           //          (octave 0 on the first, the smaller octaves on the second)
@@ -196,6 +197,13 @@ extern "C" int vo_match_u8_dev(vo_ctx* ctx, const uint8_t* d_q, const int32_t* d
 extern "C" int vo_match_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride,
                                      int cap_q, const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride,
                                      int cap_t, int S, double ratio, int32_t* d_pairs, int32_t* d_npairs, int row_bytes);
+// ... and its first half alone: the 2-NN lists (nearest, second nearest train index; squared distances as float64) of
+// sequence z at d_best / d_d2 + z * 2 * cap_q, rows past its query count not written.  Exported by libvo_hip.so without
+// being part of the C ABI of vo_hip.h (no stability promise): tests/test_gpu_matcher.py reaches both through
+// vo/_native.py's Context.knn2_u8_batch_dev / match_u8_batch_dev.
+extern "C" int vo_knn2_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride,
+                                    int cap_q, const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride,
+                                    int cap_t, int S, int row_bytes, int32_t* d_best, double* d_d2);
 // vo_sift_all_batch_dev (sift.hip) with d_found[q] (nullable): image q's keypoint count whether or not it fits `rows`, -1
 // when its candidate / keypoint lists overflowed -- what the SIFT tracker mode names when a frame does not fit
 extern "C" int vo_sift_all_found_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, int rows,

@@ -163,6 +163,8 @@ _SIGS = {
     "vo_refine_pose_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "vo_match_knn2_ratio": (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _vp, _vp]),
     "vo_knn2_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "vo_match_knn2": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, C.POINTER(_i)]),
+    "vo_match_last_path": (_i, [_vp]),
     "vo_good_features": (_i, [_vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _vp, _vp]),
     "vo_min_eigen_map": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "vo_good_features_capacity": (_i, [_i, _i, _i]),
@@ -251,6 +253,15 @@ _SIGS = {
 }
 
 
+# entry points libvo_hip.so exports without their being part of the C ABI of include/vo_hip.h (csrc/vo_internal.h)
+_INTERNAL_SIGS = {
+    "vo_knn2_u8_batch_dev": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "vo_match_u8_batch_dev": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _d, _vp, _vp, _i]),
+}
+
+MATCH_PATH_FLOAT, MATCH_PATH_BYTE_DOT, MATCH_PATH_MFMA = 0, 1, 2      # vo_match_knn2's *path (vo_hip.h)
+
+
 def distortion_coefficients(dist):
     """(k1, k2, p1, p2, k3) as five float64; None: zeros; four coefficients: k3 = 0.  The model has no more."""
     d = np.zeros(5, np.float64) if dist is None else np.asarray(dist, np.float64).reshape(-1)
@@ -275,7 +286,7 @@ def load():
                     "libvo_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; "
                     "g.build()'` (there is no CPU fallback)" % _LIB_PATH)
             lib = C.CDLL(_LIB_PATH)
-            for name, (res, args) in _SIGS.items():
+            for name, (res, args) in list(_SIGS.items()) + list(_INTERNAL_SIGS.items()):
                 fn = getattr(lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -434,6 +445,44 @@ class Context:
         self._chk(self._lib.vo_match_knn2_ratio(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0],
                                                 max(q.shape[1], 1), float(ratio), _ptr(pairs), C.byref(n)))
         return pairs[: n.value].astype(np.int64)
+
+    def match_knn2(self, q, t):
+        """The two nearest train rows of every query (vo_match_knn2): (best (nq, 2) int32, -1 where absent; d2 (nq, 2)
+        float64 squared distances, 0.0 where absent; path: the kernel that made them, MATCH_PATH_FLOAT / _BYTE_DOT / _MFMA,
+        -1 when q or t is empty)."""
+        q, t = np.asarray(q), np.asarray(t)
+        if len(q) == 0 or len(t) == 0:                      # (no distance is computed: the rows' length does not matter)
+            q, t = np.zeros((len(q), 1), np.float32), np.zeros((len(t), 1), np.float32)
+        else:
+            q, t = _c(q.reshape(len(q), -1), np.float32), _c(t.reshape(len(t), -1), np.float32)
+        assert q.shape[1] == t.shape[1]
+        best = np.empty((q.shape[0], 2), np.int32)
+        d2 = np.empty((q.shape[0], 2), np.float64)
+        path = C.c_int(-1)
+        self._chk(self._lib.vo_match_knn2(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], q.shape[1],
+                                          _ptr(best), _ptr(d2), C.byref(path)))
+        return best, d2, path.value
+
+    def match_last_path(self):
+        """The kernel the last match_knn2_ratio / match_knn2 call of this context kept (vo_match_last_path); -1: none ran."""
+        return int(self._lib.vo_match_last_path(self._h))
+
+    def knn2_u8_batch_dev(self, d_q, q_stride, d_nq, nq_stride, cap_q, d_t, t_stride, d_nt, nt_stride, cap_t, S, row_bytes,
+                          d_best, d_d2):
+        """vo_knn2_u8_batch_dev (csrc/vo_internal.h) on device pointers (to_device / alloc): the frame pipeline's 2-NN lists of
+        S sequences, enqueued on the context's stream."""
+        self._chk(self._lib.vo_knn2_u8_batch_dev(self._h, C.c_void_p(d_q), int(q_stride), C.c_void_p(d_nq), int(nq_stride),
+                                                 int(cap_q), C.c_void_p(d_t), int(t_stride), C.c_void_p(d_nt), int(nt_stride),
+                                                 int(cap_t), int(S), int(row_bytes), C.c_void_p(d_best), C.c_void_p(d_d2)))
+
+    def match_u8_batch_dev(self, d_q, q_stride, d_nq, nq_stride, cap_q, d_t, t_stride, d_nt, nt_stride, cap_t, S, ratio,
+                           d_pairs, d_npairs, row_bytes):
+        """vo_match_u8_batch_dev (csrc/vo_internal.h) on device pointers: the frame pipeline's matcher for S sequences,
+        enqueued on the context's stream."""
+        self._chk(self._lib.vo_match_u8_batch_dev(self._h, C.c_void_p(d_q), int(q_stride), C.c_void_p(d_nq), int(nq_stride),
+                                                  int(cap_q), C.c_void_p(d_t), int(t_stride), C.c_void_p(d_nt), int(nt_stride),
+                                                  int(cap_t), int(S), float(ratio), C.c_void_p(d_pairs), C.c_void_p(d_npairs),
+                                                  int(row_bytes)))
 
     # ---- frame ingest (csrc/ingest.hip) ----
     def gray_from_bgr(self, bgr):
