@@ -16,7 +16,8 @@
  * Grunert's elimination (same solution set): ratios u = s2/s1, v = s3/s1 of the
  * three depths, one quartic in v, closed-form (Ferrari) roots polished by
  * Newton, rigid alignment of the two point triads, fourth-point selection.
- * Checked against analytic ground truth (tests/test_oracle_p3p.py), and against
+ * Checked against the solution sets of an independent 60-digit solver, branch by branch
+ * (tests/test_p3p_reference_host.py, tools/make_p3p_cases.py), against analytic ground truth, and against
  * the reference's own tolerance (tests/test_p3p.py:93-98: R, t within 1e-3).
  *
  * Only +, -, *, /, sqrt are used so that a second implementation following the
@@ -26,6 +27,10 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+
+/* |Dd| at or below this share of its two terms: u comes from the quadratic, not from Nn / Dd (see the solve).
+ * csrc/p3p.hip and tools/make_p3p_cases.py hold the same number. */
+static const double P3P_DD_REL = 1e-4;
 
 static double cubic_eval(double A, double B, double C, double x) { return ((x + A) * x + B) * x + C; }
 
@@ -211,7 +216,8 @@ int oracle_p3p_solve(const double* X4, const double* x4, const double* K, double
   /* s2 = u s1, s3 = v s1;  a = d12^2/d13^2, b = d23^2/d13^2, q(v) = v^2 - 2 c13 v + 1
    *   u^2 - 2 c12 u + 1 - a q = 0,   u^2 - 2 c23 v u + v^2 - b q = 0
    * =>  u = Nn(v) / Dd(v),  Nn = v^2 - 1 + (a - b) q,  Dd = 2 (c23 v - c12)
-   * =>  Nn^2 - 2 c12 Nn Dd + (1 - a q) Dd^2 = 0   (quartic in v)                  */
+   * =>  Nn^2 - 2 c12 Nn Dd + (1 - a q) Dd^2 = 0   (quartic in v)
+   * (where Dd vanishes u comes from the first quadratic itself, see below)         */
   double a = d12s / d13s, b = d23s / d13s, g = a - b;
   double n2 = 1.0 + g, n1 = -2.0 * g * c13, n0 = g - 1.0;       /* Nn */
   double e1 = 2.0 * c23, e0 = -2.0 * c12;                         /* Dd */
@@ -237,12 +243,68 @@ int oracle_p3p_solve(const double* X4, const double* x4, const double* K, double
     double v = roots[i];
     if (!(v > 0.0)) continue;
     double Dd = e1 * v + e0;
-    if (fabs(Dd) < 1e-12) continue;
     double Nn = (n2 * v + n1) * v + n0;
-    double u = Nn / Dd;
-    if (!(u > 0.0)) continue;
     double qv = (v - 2.0 * c13) * v + 1.0;
     if (!(qv > 0.0)) continue;
+    double u;
+    if (fabs(Dd) <= P3P_DD_REL * (fabs(e1 * v) + fabs(e0))) { /* (<=: Dd == 0 with both its terms 0 comes here too) */
+      /* Nn and Dd vanish together where the two quadratics in u coincide (a symmetric view: the
+       * equilateral triangle seen from above its centroid has the common factor v - 1), and v is
+       * then a double root of the quartic that Newton leaves about 1e-8 off: Nn / Dd is 0/0 with
+       * an O(1) error.  Take u from the first quadratic and, of its two roots, the one that fits
+       * the second quadratic better.  The threshold comes from
+       * moving that camera sideways by d (1, 0.3, 0) at height 4: |Dd| / (|e1 v| + |e0|) is 0.02 d
+       * there, and Nn / Dd reprojects the three solved points 6e-8, 3e-5, 1e-3, 0.5, 5.6 px off at
+       * d = 1e-2 ... 1e-6 (f = 500; six times that at f = 2759): the error grows like 1 / Dd^2 and
+       * was at the 1e-3 px the tests allow by d = 1e-4.  1e-4 hands over near d = 5e-3, where
+       * Nn / Dd is still good to 1e-6 px; this route is below 1e-11 px from there all the way down.
+       * It is good only near the coincidence: its residual test tells the roots apart by |Dd|, and
+       * with the threshold at 1e-2 it returned 0.15 px on one of 1500 generic cases.  Between 1e-4
+       * and there its margin is not measured; away from symmetric views only three roots of the
+       * case table take it. */
+      const double w = 1.0 - a * qv;
+      const double disc = c12 * c12 - w;
+      if (disc < 0.0) continue; /* no real u at this v */
+      const double sq = sqrt(disc);
+      const double ua = c12 + sq, ub = c12 - sq;
+      const double k1 = 2.0 * c23 * v, k0 = v * v - b * qv;
+      const double ra = fabs((ua - k1) * ua + k0);
+      const double rb = fabs((ub - k1) * ub + k0);
+      /* both fit (the quadratics coincide: each root is a pose, and the double root comes twice): one
+       * each, by the parity of the root's index.  Ferrari's two quadratics list a double root at
+       * indices (0, 1) or (2, 3); the biquadratic path lists (s0, -s0, s1, -s1), a double root at 0
+       * and 2, and proposes only one of the two poses -- not met so far.  The root that does not
+       * belong misses the second quadratic by |Dd| |ua - ub|; below 1e-6 the Newton steps below
+       * still pull either start onto a pose (the two are then less than 1e-3 apart in v). */
+      if (ub > 0.0 && ra < 1e-6 && rb < 1e-6) u = (i & 1) ? ub : ua;
+      else u = (ub > 0.0 && rb < ra) ? ub : ua;
+      /* v itself is the double root's 1e-8 off.  Unlike the quartic, the pair of quadratics is regular in
+       * (u, v) there (its Jacobian is singular only where two poses really merge): two Newton steps on the
+       * pair, each kept only if it lowers the residual, bring both ratios to working precision. */
+      for (int it = 0; it < 2; ++it) {
+        const double qn = (v - 2.0 * c13) * v + 1.0, dq = 2.0 * v - 2.0 * c13;
+        const double E1 = (u - 2.0 * c12) * u + (1.0 - a * qn);
+        const double E2 = (u - 2.0 * c23 * v) * u + (v * v - b * qn);
+        const double j11 = 2.0 * u - 2.0 * c12, j12 = -a * dq;
+        const double j21 = 2.0 * u - 2.0 * c23 * v, j22 = 2.0 * v - 2.0 * c23 * u - b * dq;
+        const double det = j11 * j22 - j12 * j21;
+        if (det == 0.0) break;
+        const double un = u - (E1 * j22 - E2 * j12) / det;
+        const double vn = v - (j11 * E2 - j21 * E1) / det;
+        const double qm = (vn - 2.0 * c13) * vn + 1.0;
+        const double F1 = (un - 2.0 * c12) * un + (1.0 - a * qm);
+        const double F2 = (un - 2.0 * c23 * vn) * un + (vn * vn - b * qm);
+        if (!(fabs(F1) + fabs(F2) < fabs(E1) + fabs(E2))) break;
+        u = un;
+        v = vn;
+      }
+      if (!(v > 0.0)) continue;
+      qv = (v - 2.0 * c13) * v + 1.0;
+      if (!(qv > 0.0)) continue;
+    } else {
+      u = Nn / Dd;
+    }
+    if (!(u > 0.0)) continue;
     double s1 = sqrt(d13s / qv);
     double s2 = u * s1, s3 = v * s1;
     double C1[3] = {s1 * f[0][0], s1 * f[0][1], s1 * f[0][2]};

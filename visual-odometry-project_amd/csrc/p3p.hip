@@ -20,6 +20,8 @@
 
 namespace {
 
+constexpr double P3P_DD_REL = 1e-4;   // the oracle's: below it u = Nn / Dd gives way to the quadratic in u
+
 struct pose_t {
   double R[9];
   double t[3];
@@ -371,12 +373,50 @@ __device__ __forceinline__ void p3p_solve_quad(int gt, const double* __restrict_
       if (sub == 3) v = roots[3];
       if (!(v > 0.0)) break;
       const double Dd = e1 * v + e0;
-      if (fabs(Dd) < 1e-12) break;
       const double Nn = (n2 * v + n1) * v + n0;
-      const double u = Nn / Dd;
-      if (!(u > 0.0)) break;
-      const double qv = (v - 2.0 * c13) * v + 1.0;
+      double qv = (v - 2.0 * c13) * v + 1.0;
       if (!(qv > 0.0)) break;
+      double u;
+      if (fabs(Dd) <= P3P_DD_REL * (fabs(e1 * v) + fabs(e0))) {
+        // Nn / Dd is 0/0 at this root: u from the first quadratic, the root of it that fits the second one
+        // (oracle/csrc/p3p.c has the reasoning and the threshold).  Lane-local: no exchange before the quad
+        // meets again at the selection below.
+        const double w = 1.0 - a * qv;
+        const double disc = c12 * c12 - w;
+        if (disc < 0.0) break;
+        const double sq = sqrt(disc);
+        const double ua = c12 + sq, ub = c12 - sq;
+        const double k1 = 2.0 * c23 * v, k0 = v * v - b * qv;
+        const double ra = fabs((ua - k1) * ua + k0);
+        const double rb = fabs((ub - k1) * ub + k0);
+        // (both fit: the double root comes twice -- one candidate each, by the parity of the root's index)
+        if (ub > 0.0 && ra < 1e-6 && rb < 1e-6) u = (sub & 1) ? ub : ua;
+        else u = (ub > 0.0 && rb < ra) ? ub : ua;
+        // two guarded Newton steps on the pair of quadratics in (u, v)
+        for (int it = 0; it < 2; ++it) {
+          const double qn = (v - 2.0 * c13) * v + 1.0, dq = 2.0 * v - 2.0 * c13;
+          const double E1 = (u - 2.0 * c12) * u + (1.0 - a * qn);
+          const double E2 = (u - 2.0 * c23 * v) * u + (v * v - b * qn);
+          const double j11 = 2.0 * u - 2.0 * c12, j12 = -a * dq;
+          const double j21 = 2.0 * u - 2.0 * c23 * v, j22 = 2.0 * v - 2.0 * c23 * u - b * dq;
+          const double det = j11 * j22 - j12 * j21;
+          if (det == 0.0) break;
+          const double un = u - (E1 * j22 - E2 * j12) / det;
+          const double vn = v - (j11 * E2 - j21 * E1) / det;
+          const double qm = (vn - 2.0 * c13) * vn + 1.0;
+          const double F1 = (un - 2.0 * c12) * un + (1.0 - a * qm);
+          const double F2 = (un - 2.0 * c23 * vn) * un + (vn * vn - b * qm);
+          if (!(fabs(F1) + fabs(F2) < fabs(E1) + fabs(E2))) break;
+          u = un;
+          v = vn;
+        }
+        if (!(v > 0.0)) break;
+        qv = (v - 2.0 * c13) * v + 1.0;
+        if (!(qv > 0.0)) break;
+      } else {
+        u = Nn / Dd;
+      }
+      if (!(u > 0.0)) break;
       const double s1 = sqrt(d13s / qv);
       const double s2 = u * s1, s3 = v * s1;
       const double C1[3] = {s1 * f[0][0], s1 * f[0][1], s1 * f[0][2]};
@@ -460,7 +500,8 @@ __global__ __launch_bounds__(64) void p3p_solve_kernel(const double* __restrict_
 // sequences, 16 when a launch holds
 // several sequences (wave 0's 64 lanes all solve, half as many workgroups share the solve's latency: throughput).
 // Correspondences per thread and tile: 7 for HG = 8 (256 * 7 = 1792 = 28 mask words: one tile at every population the
-// frame loop sees), 4 for HG = 16, which with five waves per SIMD asked for (96 registers: the solve spills 11 words,
+// frame loop sees), 4 for HG = 16, which with five waves per SIMD asked for (96 registers: the solve spills 14 words --
+// 10 before the vanishing-denominator branch, by the compiler's resource report; its cost at 16 sequences is not re-timed --
 // the scoring loop none) puts the 72 x 16 workgroups of a 16-sequence launch on the chip in one round instead of two.
 template <int HG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HG == 16 ? 5 : 4, HG == 16 ? 5 : 4))) void
