@@ -7,7 +7,7 @@
  *                              criteria=(EPS|COUNT, 10, 0.03))        (klt.py:29-33)
  *     keep = status & (err < 100)                                      (klt.py:244-249)
  *
- * PARITY UNPINNED against OpenCV: the arithmetic lives in opencv-python==4.8.1.78
+ * BIT PARITY UNPINNED against OpenCV: the arithmetic lives in opencv-python==4.8.1.78
  * (environment.yml:22), absent here, and the reference has no KLT test.  This is
  * a restatement of the published algorithm as OpenCV's lkpyramid implements it
  * (Bouguet's pyramidal LK): 5-tap [1 4 6 4 1]/16 pyrDown with reflect-101
@@ -20,7 +20,10 @@
  * accumulated as exact integers and converted to float32 once, instead of
  * float32 accumulation whose rounding depends on OpenCV's SIMD build; this makes
  * the result independent of summation order (what the GPU needs for bit-parity).
- * Validated against the analytic flow of synthetic scenes (tests/).
+ * Pinned to the float64 definition of the same algorithm in tests/klt_reference.py
+ * (no fixed point, no stops) on the cases of tests/klt_cases.py: one Newton step and
+ * the fixed point within that file's quantisation bound, err, status and pyrDown
+ * (tests/test_klt_reference_host.py; the kernels: tests/test_gpu_klt_reference.py).
  */
 #include <math.h>
 #include <stdint.h>

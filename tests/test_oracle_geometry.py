@@ -1,5 +1,6 @@
 """Oracle checks without a GPU: DLT against the reference golden; P3P and KLT
-oracles (parity unpinned vs OpenCV) against analytic ground truth."""
+oracles against analytic ground truth.  (What pins them beyond that: tests/test_p3p_reference_host.py for P3P,
+tests/test_klt_reference_host.py -- a float64 definition of the tracker and of pyrDown -- for KLT.)"""
 import os
 
 import numpy as np
