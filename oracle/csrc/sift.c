@@ -5,7 +5,8 @@
  * Reference call site: src/vo/features/sift.py:10,17
  *     self.sift = cv2.SIFT_create();  kp, desc = self.sift.detectAndCompute(image, None)
  * (only kp.pt and the (n, 128) float32 descriptors are used, sift.py:18-19).
- * PARITY UNPINNED against OpenCV (opencv-python==4.8.1.78 is absent, the reference has no
+ * Pinned to the float64 definition of tests/sift_reference.py (tests/test_sift_reference_host.py); parity with OpenCV's
+ * own float32 order is still open (opencv-python==4.8.1.78 is absent, the reference has no
  * SIFT test).  This restates Lowe's algorithm with cv2.SIFT_create()'s defaults as OpenCV
  * structures it: image doubled (bilinear) and blurred to sigma 1.6; octaves of 3 layers
  * (6 Gaussian images, separable kernels of cvRound(8 sigma + 1) | 1 taps, reflect-101);
@@ -74,6 +75,7 @@ typedef struct {
   float x, y, size, angle, response;
   int octave, layer;    /* octave index in the (doubled) pyramid, layer 1..NOL */
   float oct_x, oct_y;   /* position in the octave image */
+  float xi;             /* refined layer offset */
 } kp_t;
 
 static int make_kernel(double sigma, float* w) {
@@ -193,6 +195,7 @@ static int refine(const octave_t* o, int octv, int* pl, int* pr, int* pc, kp_t* 
     kp->y = (r + xr) * (float)(1 << octv);
     kp->octave = octv;
     kp->layer = layer;
+    kp->xi = xi;
     kp->size = sigma * sift_exp(((layer + xi) / NOL) * 0.6931471805599453f) * (float)(1 << octv) * 2;
     kp->response = fabsf(contr);
   }
@@ -234,9 +237,8 @@ static float ori_hist(const float* g, int H, int W, int c, int r, int radius, fl
   return mx;
 }
 
-static void descriptor(const float* g, int H, int W, float px, float py, float ori_deg, float scl, float* dst) {
-  const int d = 4, n = 8;
-  const int pxi = (int)rintf(px), pyi = (int)rintf(py);
+/* sin and cos of an angle in degrees: reduced to [-pi/2, pi/2], odd / even Taylor polynomials */
+static void sift_sincos(float ori_deg, float* sin_out, float* cos_out) {
   const float rad = ori_deg * 0.017453292519943295f;
   /* sin/cos through the same exp-free route on both sides: use sinf/cosf replacement by polynomial of degrees */
   float cos_t, sin_t;
@@ -257,6 +259,15 @@ static void descriptor(const float* g, int H, int W, float px, float py, float o
     sin_t = a * (1.f + a2 * (-1.f / 6 + a2 * (1.f / 120 + a2 * (-1.f / 5040 + a2 * (1.f / 362880 + a2 * (-1.f / 39916800))))));
     cos_t = sgn * (1.f + a2 * (-0.5f + a2 * (1.f / 24 + a2 * (-1.f / 720 + a2 * (1.f / 40320 + a2 * (-1.f / 3628800 + a2 * (1.f / 479001600)))))));
   }
+  *sin_out = sin_t;
+  *cos_out = cos_t;
+}
+
+static void descriptor(const float* g, int H, int W, float px, float py, float ori_deg, float scl, float* dst) {
+  const int d = 4, n = 8;
+  const int pxi = (int)rintf(px), pyi = (int)rintf(py);
+  float cos_t, sin_t;
+  sift_sincos(ori_deg, &sin_t, &cos_t);
   const float bins_per_deg = n / 360.f;
   const float exp_scale = -1.f / (d * d * 0.5f);
   const float hist_width = 3.f * scl;
@@ -340,11 +351,65 @@ static int kp_less(const void* pa, const void* pb) {
   return 0;
 }
 
+/* final order, duplicate rule and cap on rows of 135 floats (6 keypoint fields, 128 descriptor entries, 1 spare), in place */
+static int finish_rows(float* rows, int n_all, int cap) {
+  qsort(rows, n_all, sizeof(float) * 135, kp_less);
+  /* exact duplicates (same x, y, size, angle) removed */
+  int n = 0;
+  for (int k = 0; k < n_all; ++k) {
+    float* row = rows + (size_t)k * 135;
+    if (n > 0) {
+      float* prev = rows + (size_t)(n - 1) * 135;
+      if (prev[0] == row[0] && prev[1] == row[1] && prev[2] == row[2] && prev[3] == row[3]) continue;
+    }
+    if (n != k) memmove(rows + (size_t)n * 135, row, sizeof(float) * 135);
+    ++n;
+  }
+  if (n > cap) {
+    /* keep the `cap` strongest by response (ties by sorted position), preserving the sorted order */
+    float* resp = (float*)malloc(sizeof(float) * n);
+    for (int k = 0; k < n; ++k) resp[k] = rows[(size_t)k * 135 + 4];
+    /* threshold = cap-th largest response */
+    float* cp = (float*)malloc(sizeof(float) * n);
+    memcpy(cp, resp, sizeof(float) * n);
+    for (int i = 0; i < cap; ++i) {   /* partial selection sort is fine for test sizes */
+      int m = i;
+      for (int j = i + 1; j < n; ++j)
+        if (cp[j] > cp[m]) m = j;
+      float t = cp[i];
+      cp[i] = cp[m];
+      cp[m] = t;
+    }
+    float thr = cp[cap - 1];
+    int above = 0;
+    for (int k = 0; k < n; ++k) above += resp[k] > thr;
+    int ties = cap - above, m = 0;
+    for (int k = 0; k < n; ++k) {
+      int keep = resp[k] > thr || (resp[k] == thr && ties-- > 0);
+      if (keep) {
+        if (m != k) memmove(rows + (size_t)m * 135, rows + (size_t)k * 135, sizeof(float) * 135);
+        ++m;
+      }
+    }
+    n = m;
+    free(resp);
+    free(cp);
+  }
+  return n;
+}
+
 /*
  * img: H x W uint8.  kp_out: cap x 6 float32 (x, y, size, angle, response, octave), desc_out: cap x 128 float32.
  * Returns the number of keypoints (<= cap; when more are found the `cap` strongest by response are kept).
  */
-int oracle_sift(const uint8_t* img, int H, int W, int cap, float* kp_out, float* desc_out) {
+/* what oracle_sift_stages records of one octave: the images, and each accepted keypoint before the sort */
+typedef struct {
+  int octave, cap, n, H, W, n_ext;   /* n_ext: extrema beyond the threshold, before refinement */
+  float *g, *d;        /* NG and NG - 1 images of H x W, or NULL */
+  float *kp, *hist;    /* cap x 12 (octave, layer, r, c, xi, xr, xc, peak bin, angle, size, response, radius), cap x 36 */
+} stages_t;
+
+static int sift_core(const uint8_t* img, int H, int W, int cap, float* kp_out, float* desc_out, stages_t* st) {
   const float sigma = 1.6f, contrast_thr = 0.04f, edge_thr = 10.f;
   const int W0 = W * 2, H0 = H * 2;
   float* base = (float*)malloc(sizeof(float) * (size_t)W0 * H0);
@@ -407,6 +472,12 @@ int oracle_sift(const uint8_t* img, int H, int W, int cap, float* kp_out, float*
     for (int i = 1; i < NG; ++i) blur(oct[o].g[i - 1], h, w, wk[i], rk[i], tmp, oct[o].g[i]);
     for (int i = 0; i < NG - 1; ++i)
       for (size_t p = 0; p < (size_t)w * h; ++p) oct[o].d[i][p] = oct[o].g[i + 1][p] - oct[o].g[i][p];
+    if (st && st->octave == o) {
+      st->H = h;
+      st->W = w;
+      for (int i = 0; i < NG && st->g; ++i) memcpy(st->g + (size_t)i * w * h, oct[o].g[i], sizeof(float) * (size_t)w * h);
+      for (int i = 0; i < NG - 1 && st->d; ++i) memcpy(st->d + (size_t)i * w * h, oct[o].d[i], sizeof(float) * (size_t)w * h);
+    }
     w /= 2;
     h /= 2;
   }
@@ -449,6 +520,7 @@ int oracle_sift(const uint8_t* img, int H, int W, int cap, float* kp_out, float*
               }
           }
           if (!is_ext) continue;
+          if (st && st->octave == o) ++st->n_ext;
           int l2 = layer, r2 = r, c2 = c;
           kp_t kp;
           if (!refine(&oct[o], o, &l2, &r2, &c2, &kp, contrast_thr, edge_thr, sigma)) continue;
@@ -463,6 +535,14 @@ int oracle_sift(const uint8_t* img, int H, int W, int cap, float* kp_out, float*
               bin = bin < 0 ? 36 + bin : (bin >= 36 ? bin - 36 : bin);
               float angle = 360.f - (360.f / 36) * bin;
               if (fabsf(angle - 360.f) < 1.1920929e-07f) angle = 0.f;
+              if (st && st->octave == o && st->n < st->cap) {
+                float* q = st->kp + (size_t)st->n * 12;
+                q[0] = (float)o, q[1] = (float)l2, q[2] = (float)r2, q[3] = (float)c2;
+                q[4] = kp.xi, q[5] = kp.oct_y - r2, q[6] = kp.oct_x - c2, q[7] = (float)j;
+                q[8] = angle, q[9] = kp.size, q[10] = kp.response, q[11] = rintf(4.5f * scl_octv);
+                memcpy(st->hist + (size_t)st->n * 36, hist, sizeof(float) * 36);
+                ++st->n;
+              }
               if (n_all < cap_all) {
                 kps[n_all] = kp;
                 kps[n_all].angle = angle;
@@ -490,48 +570,7 @@ int oracle_sift(const uint8_t* img, int H, int W, int cap, float* kp_out, float*
     descriptor(oct[q->octave].g[q->layer], oct[q->octave].H, oct[q->octave].W, q->oct_x, q->oct_y, ang, scl, row + 6);
     row[134] = 0;
   }
-  qsort(rows, n_all, sizeof(float) * 135, kp_less);
-  /* exact duplicates (same x, y, size, angle) removed */
-  int n = 0;
-  for (int k = 0; k < n_all; ++k) {
-    float* row = rows + (size_t)k * 135;
-    if (n > 0) {
-      float* prev = rows + (size_t)(n - 1) * 135;
-      if (prev[0] == row[0] && prev[1] == row[1] && prev[2] == row[2] && prev[3] == row[3]) continue;
-    }
-    if (n != k) memmove(rows + (size_t)n * 135, row, sizeof(float) * 135);
-    ++n;
-  }
-  if (n > cap) {
-    /* keep the `cap` strongest by response (ties by sorted position), preserving the sorted order */
-    float* resp = (float*)malloc(sizeof(float) * n);
-    for (int k = 0; k < n; ++k) resp[k] = rows[(size_t)k * 135 + 4];
-    /* threshold = cap-th largest response */
-    float* cp = (float*)malloc(sizeof(float) * n);
-    memcpy(cp, resp, sizeof(float) * n);
-    for (int i = 0; i < cap; ++i) {   /* partial selection sort is fine for test sizes */
-      int m = i;
-      for (int j = i + 1; j < n; ++j)
-        if (cp[j] > cp[m]) m = j;
-      float t = cp[i];
-      cp[i] = cp[m];
-      cp[m] = t;
-    }
-    float thr = cp[cap - 1];
-    int above = 0;
-    for (int k = 0; k < n; ++k) above += resp[k] > thr;
-    int ties = cap - above, m = 0;
-    for (int k = 0; k < n; ++k) {
-      int keep = resp[k] > thr || (resp[k] == thr && ties-- > 0);
-      if (keep) {
-        if (m != k) memmove(rows + (size_t)m * 135, rows + (size_t)k * 135, sizeof(float) * 135);
-        ++m;
-      }
-    }
-    n = m;
-    free(resp);
-    free(cp);
-  }
+  int n = finish_rows(rows, n_all, cap);
   for (int k = 0; k < n; ++k) {
     memcpy(kp_out + (size_t)k * 6, rows + (size_t)k * 135, sizeof(float) * 6);
     memcpy(desc_out + (size_t)k * 128, rows + (size_t)k * 135 + 6, sizeof(float) * 128);
@@ -546,3 +585,35 @@ int oracle_sift(const uint8_t* img, int H, int W, int cap, float* kp_out, float*
   free(oct);
   return n;
 }
+
+int oracle_sift(const uint8_t* img, int H, int W, int cap, float* kp_out, float* desc_out) {
+  return sift_core(img, H, W, cap, kp_out, desc_out, NULL);
+}
+
+/*
+ * One octave of the run oracle_sift makes: its NG Gaussian and NG - 1 DoG images (g_out, d_out: room for the octave's size,
+ * either may be NULL) and the keypoints accepted in it before the sort (st_kp: st_cap x 12, st_hist: st_cap x 36 smoothed
+ * histograms).  hw_out: the octave's height and width, and its number of extrema beyond the threshold (before refinement).  Returns the number of accepted keypoints of the octave, -1 when
+ * the image has no such octave.
+ */
+int oracle_sift_stages(const uint8_t* img, int H, int W, int octave, float* g_out, float* d_out, float* st_kp,
+                       float* st_hist, int st_cap, int* hw_out) {
+  stages_t st = {octave, st_cap, 0, 0, 0, 0, g_out, d_out, st_kp, st_hist};
+  float* kp = (float*)malloc(sizeof(float) * 6 * 65536);
+  float* desc = (float*)malloc(sizeof(float) * 128 * 65536);
+  sift_core(img, H, W, 65536, kp, desc, &st);
+  free(kp);
+  free(desc);
+  hw_out[0] = st.H;
+  hw_out[1] = st.W;
+  hw_out[2] = st.n_ext;
+  return st.H ? st.n : -1;
+}
+
+/* the final order, duplicate rule and cap alone, on n rows of 135 floats in place; returns the rows kept */
+int oracle_sift_finish(float* rows, int n, int cap) { return finish_rows(rows, n, cap); }
+
+/* the polynomial routines, for the tests that pin them against libm */
+float oracle_sift_exp(float x) { return sift_exp(x); }
+float oracle_sift_atan2(float y, float x) { return sift_atan2(y, x); }
+void oracle_sift_sincos(float deg, float* sin_out, float* cos_out) { sift_sincos(deg, sin_out, cos_out); }

@@ -143,3 +143,63 @@ def sift(img, cap=20000):
     f.restype = C.c_int
     n = f(_p(img), C.c_int(H), C.c_int(W), C.c_int(cap), _p(kp), _p(desc))
     return kp[:n].copy(), desc[:n].copy()
+
+
+def sift_stages(img, octave, cap=65536):
+    """One octave of the run sift() makes: (G (6, h, w), D (5, h, w), kp (n, 12), hist (n, 36), n_ext), kp rows being octave,
+    layer, r, c, xi, xr, xc, peak bin, angle, size, response, orientation radius of each accepted keypoint before the sort,
+    n_ext the octave's number of extrema beyond the threshold (the candidates refinement starts from).
+    None when the image has no such octave."""
+    img = np.ascontiguousarray(img, np.uint8)
+    H, W = img.shape
+    h, w = (2 * H) >> octave, (2 * W) >> octave
+    G = np.zeros((6, max(h, 1), max(w, 1)), np.float32)
+    D = np.zeros((5, max(h, 1), max(w, 1)), np.float32)
+    kp = np.zeros((cap, 12), np.float32)
+    hist = np.zeros((cap, 36), np.float32)
+    hw = np.zeros(3, np.int32)
+    f = lib().oracle_sift_stages
+    f.restype = C.c_int
+    n = f(_p(img), C.c_int(H), C.c_int(W), C.c_int(octave), _p(G), _p(D), _p(kp), _p(hist), C.c_int(cap), _p(hw))
+    if n < 0:
+        return None
+    assert (int(hw[0]), int(hw[1])) == (h, w)
+    return G, D, kp[:n].copy(), hist[:n].copy(), int(hw[2])
+
+
+def sift_finish(kp_rows, cap):
+    """The final order, duplicate rule and cap of sift() on (n, 6) keypoint rows alone: the indices of the rows kept, in
+    their final order."""
+    kp_rows = np.asarray(kp_rows, np.float32).reshape(-1, 6)
+    n = len(kp_rows)
+    rows = np.zeros((max(n, 1), 135), np.float32)
+    rows[:n, :6] = kp_rows
+    rows[:n, 6] = np.arange(n)
+    f = lib().oracle_sift_finish
+    f.restype = C.c_int
+    m = f(_p(rows), C.c_int(n), C.c_int(cap))
+    return rows[:m, 6].astype(np.int64)
+
+
+def sift_exp(x):
+    f = lib().oracle_sift_exp
+    f.restype, f.argtypes = C.c_float, [C.c_float]
+    return np.array([f(float(v)) for v in np.asarray(x, np.float32).ravel()], np.float32)
+
+
+def sift_atan2(y, x):
+    f = lib().oracle_sift_atan2
+    f.restype, f.argtypes = C.c_float, [C.c_float, C.c_float]
+    y, x = np.broadcast_arrays(np.asarray(y, np.float32), np.asarray(x, np.float32))
+    return np.array([f(float(a), float(b)) for a, b in zip(y.ravel(), x.ravel())], np.float32)
+
+
+def sift_sincos(deg):
+    f = lib().oracle_sift_sincos
+    f.restype, f.argtypes = None, [C.c_float, C.c_void_p, C.c_void_p]
+    s, c = C.c_float(), C.c_float()
+    out = []
+    for v in np.asarray(deg, np.float32).ravel():
+        f(float(v), C.byref(s), C.byref(c))
+        out.append((s.value, c.value))
+    return np.array(out, np.float32).reshape(-1, 2)
