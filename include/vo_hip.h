@@ -514,6 +514,11 @@ typedef struct vo_pipeline_config {
                                     0 = n_keypoints; -1 = every keypoint [ref: src/vo/features/sift.py:10, nfeatures = 0]
                                     up to feature_cap -- a frame with more, or whose SIFT lists overflow, fails its step
                                     with VO_ECAPACITY (never a truncated list).  Below -1: refused.                   */
+  int32_t track_ids;             /* 1: every feature carries a persistent track id (see "Track ids" below; the
+                                    vo_pipeline_*_track_ids_seq / _export_tracks_post_seq entry points).  0 = off: nothing
+                                    is allocated and the regroup kernels are the ones without a word of it.  (The field
+                                    takes the four bytes that were padding in front of match_ratio: every other field
+                                    keeps its offset and the structure its size.)                                     */
   double match_ratio;            /* 0 = the reference's: 0.8 in SIFT mode (sift.py:49), 0.85 in Harris mode (harris.py:255) */
   int32_t detector;              /* tracker_mode 0: what refills the feature set when fewer than redetect_fraction of the
                                     tracks are left.  0: Harris response + greedy NMS, exactly n_keypoints keypoints
@@ -651,6 +656,42 @@ int vo_pipeline_prof_reset(vo_pipeline* p);
 int vo_pipeline_export_state_post(vo_pipeline* p, const vo_step_result* r, int cap, double* d_record);
 int vo_pipeline_export_state_post_seq(vo_pipeline* p, int seq, const vo_step_result* r, int cap, double* d_record);
 int vo_pipeline_export_state_join(vo_pipeline* p, void* consumer);
+/* Track ids (vo_pipeline_config.track_ids = 1; every entry point below returns VO_EINVAL naming track_ids without it).
+ * The reference carries Features.uids [ref: src/vo/features/klt.py:49, 147, 228, 263-265; src/vo/primitives/features.py:255-256]
+ * drawn from NumPy's global generator and lost at every Matches regroup; what is kept here is their intent, a stable
+ * identity per image track, under a deterministic rule.  Per sequence every feature carries two int32 -- id, the track's
+ * identity, and born, the value of the sequence's step counter for the frame the track was first seen on -- and the
+ * sequence carries next_id:
+ *   hand-over (vo_pipeline_set_state(_seq), _restart_seq, _bootstrap, _bootstrap_seq, _bootstrap_lanes): the n features get
+ *     ids 0 .. n-1 in feature order, born = 0, next_id = n (vo_pipeline_set_track_ids_seq may replace them afterwards);
+ *   KLT mode, step k (k = steps completed before it): when the step re-detects, appended keypoint j (position n + j of the
+ *     tracker's input, either detector) gets id = next_id + j, born = k, and next_id grows by the appended count -- a
+ *     keypoint the KLT filter then drops has still used up its id; every survivor keeps id and born through the filter and
+ *     the regroup;
+ *   SIFT and Harris modes, step k: a feature written from pair (i1, i2) keeps the id and born of old feature i1; the
+ *     unmatched new keypoints, in ascending new-keypoint index (the order the regroup writes them), get id = next_id + r,
+ *     born = k + 1, and next_id grows by their count;
+ *   pose, reset_outliers, candidates, landmark insertion, the cheirality check: nothing moves, id and born stay (a track
+ *     whose landmark is reset is still the same image track);
+ *   a step that faults changes nothing, and a step that is redone (host path, a step enqueued again behind a continued
+ *     RANSAC loop, a forced fault of the regroup or of the pose kernel) issues the ids it would have issued the first time;
+ *   vo_pipeline_checkpoint / _rewind restore ids and next_id (ids issued after the checkpoint are issued again on the next
+ *     pass); born follows the step counter, which is not rewound.
+ * Ids are unique within a sequence between two hand-overs; sequences number independently.
+ *   _get_track_ids_seq: the current Features' ids / born (arrays of vo_pipeline_feature_cap int32; any pointer may be NULL),
+ *     *n_out the feature count, *next_id the next id to issue.  Nothing may be in flight.
+ *   _set_track_ids_seq: replaces them: n must be the sequence's feature count, ids distinct, >= 0 and < next_id; born NULL =
+ *     left as it is.  Nothing may be in flight; a refused call changes nothing.
+ *   _export_tracks_post_seq: queues, on the pipeline's stream, the observation record of the step collected last for
+ *     sequence seq (r: its result) into DEVICE memory: a 16-byte header {int32 n, step, next_id, seq} -- the feature count,
+ *     the step counter and next_id as that step left them -- then min(n, cap) rows of 48 bytes {int32 id, born; float32 x, y;
+ *     int32 state; int32 candidate; float64 X, Y, Z} in feature order, the landmark NaN where the feature has none (state
+ *     != 2).  d_record: 16-byte aligned, vo_pipeline_tracks_record_bytes(cap) bytes.  Like the shared-map record it may be
+ *     posted with one further step in flight; ordering against a consumer is vo_pipeline_export_state_join.            */
+size_t vo_pipeline_tracks_record_bytes(int cap);
+int vo_pipeline_get_track_ids_seq(vo_pipeline* p, int seq, int32_t* ids, int32_t* born, int32_t* n_out, int32_t* next_id);
+int vo_pipeline_set_track_ids_seq(vo_pipeline* p, int seq, const int32_t* ids, const int32_t* born, int n, int32_t next_id);
+int vo_pipeline_export_tracks_post_seq(vo_pipeline* p, int seq, const vo_step_result* r, int cap, void* d_record);
 /* the ransac.py:58-67 iteration bound through the pipeline's threshold table (what the device
  * evaluates); equals vo_ransac_num_iterations clipped to max_iterations                         */
 int64_t vo_pipeline_ransac_bound(vo_pipeline* p, double outlier_ratio);

@@ -122,6 +122,8 @@ struct vo_pipeline {
   std::vector<unsigned> slot_seq;    // [4][S]: the number sequence q's record in result slot r will carry
   std::vector<char> seq_state;       // [S]: a state was handed over before (the RANSAC object persists, ransac.py:47-56)
   int last_fbuf = 0;
+  long last_k = 0;                   // the flight number of the step collected last (track ids: its slot of vo_seq_ctl.next_id)
+  int ckpt_par = 0;                  // the parity of the step that followed the checkpoint (which next_id slot the copy's is)
   hipEvent_t evA = nullptr, evB = nullptr;
   double* d_newkp = nullptr;         // scratch of the bookkeeping entry point
   vo_pipeline_boot* boot = nullptr;  // vo_pipeline_bootstrap_seq's workspace (device memory in dev_mem; made at its first call)

@@ -18,7 +18,7 @@ uint32_t next_pow2(uint64_t v) {
 }
 
 // one Features buffer for S sequences of `cap` features: every array S * cap entries
-vo_feat carve(char*& q, int cap, int S) {
+vo_feat carve(char*& q, int cap, int S, bool ids) {
   vo_feat f;
   auto take = [&](size_t bytes) {
     void* r = q;
@@ -33,12 +33,13 @@ vo_feat carve(char*& q, int cap, int S) {
   f.track = (double*)take((size_t)cap * 16);
   f.pose = (double*)take((size_t)cap * 96);
   f.pitch = cap;
-  return f;
+  f.ids = ids ? (int2*)take((size_t)cap * 8) : nullptr;     // (vo_pipeline_config.track_ids; inside the block: checkpoint,
+  return f;                                                 //  rewind and the per-sequence strides cover it)
 }
 
-size_t feat_bytes(int cap, int S) {
+size_t feat_bytes(int cap, int S, bool ids) {
   char* q = nullptr;
-  carve(q, cap, S);
+  carve(q, cap, S, ids);
   return (size_t)(q - (char*)nullptr);
 }
 
@@ -202,6 +203,7 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
              "pipeline: sift_cap must be -1 (every keypoint), 0 (n_keypoints) or 1..4000, got %d", cfg->sift_cap);
   VO_REQUIRE(ctx, cfg->detector >= 0 && cfg->detector <= 1, "pipeline: detector must be 0 (harris) or 1 (shi-tomasi), got %d",
              cfg->detector);
+  VO_REQUIRE(ctx, cfg->track_ids == 0 || cfg->track_ids == 1, "pipeline: track_ids must be 0 (off) or 1 (on), got %d", cfg->track_ids);
   VO_REQUIRE(ctx, cfg->detector == 0 || cfg->tracker_mode == 0,
              "pipeline: the Shi-Tomasi detector (detector = 1) belongs to the KLT tracker mode (tracker_mode = 0)");
   if (cfg->detector == 1) {            // klt.py:24-26 where a field is 0; the rest is what the batched detector takes
@@ -290,15 +292,15 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
     PA(dev_alloc(p, &p->d_det_cnt, 3 * Sz));
   }
   {
-    const size_t fb = feat_bytes(cap, S);
+    const size_t fb = feat_bytes(cap, S, cfg->track_ids != 0);
     char* mem = nullptr;
     PA(dev_alloc(p, &mem, 2 * fb));
     p->feat_mem = mem;
     p->feat_block = fb;
     if (mem) {
       char* q = mem;
-      p->F[0] = carve(q, cap, S);
-      p->F[1] = carve(q, cap, S);
+      p->F[0] = carve(q, cap, S, cfg->track_ids != 0);
+      p->F[1] = carve(q, cap, S, cfg->track_ids != 0);
     }
   }
   PA(dev_alloc(p, &p->d_ctl, Sz));

@@ -140,6 +140,7 @@ __global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args g,
     F.kp64[2 * i] = kx;
     F.kp64[2 * i + 1] = ky;
     F.cand[i] = 0;
+    if (F.ids) F.ids[i] = make_int2(i, 0);     // (track ids: a hand-over numbers the features in their order, born 0)
     bool tri = mask[i] != 0;
     const double x = X[3 * i], y = X[3 * i + 1], z = X[3 * i + 2];
     if (tri) {
@@ -179,6 +180,7 @@ __global__ __launch_bounds__(256) void bootstrap_apply_kernel(boot_apply_args g,
     h.n2 = a_n;
     h.num_features = a_num_features;
     h.nf[0] = h.nf[1] = a_num_features;
+    h.next_id[0] = h.next_id[1] = a_n;
     h.raw_pos = raw_pos;
     h.n_iterations = n_it;
     h.outlier_ratio = orat;

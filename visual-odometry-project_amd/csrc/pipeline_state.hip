@@ -1,5 +1,7 @@
 // Frame pipeline: the state it carries -- seed, hand-over, descriptors, checkpoint / rewind, lanes, read-back,
 // bookkeeping and export.
+#include <algorithm>
+
 #include "pipeline.h"
 
 #pragma clang fp contract(off)
@@ -19,9 +21,35 @@ __global__ __launch_bounds__(256) void export_state_kernel(pose17 head, const do
   if (i < m) rec[17 + i] = land[i];
 }
 
+// The observation record of one step (vo_hip.h, "Track ids"): header {n, step, next_id, seq}, then a 48-byte row per feature,
+// written as six 8-byte words.  slot: where the collected step's regroup left next_id / the step counter (vo_seq_ctl.next_id).
+__global__ __launch_bounds__(256) void export_tracks_kernel(vo_feat F, const vo_seq_ctl* __restrict__ ctl, int slot, int n,
+                                                            int cap, int seq, unsigned long long* __restrict__ rec) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  auto pack = [](int lo, int hi) { return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32); };
+  if (i == 0) {
+    rec[0] = pack(n, ctl->id_step[slot]);
+    rec[1] = pack(ctl->next_id[slot], seq);
+  }
+  if (i >= min(n, cap)) return;
+  const int2 id = F.ids[i];
+  const float x = F.kp[2 * i], y = F.kp[2 * i + 1];
+  const int st = F.state[i], cd = F.cand[i];
+  double X[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) X[k] = F.land[3 * i + k];
+  unsigned long long* row = rec + 2 + (size_t)6 * i;
+  row[0] = pack(id.x, id.y);
+  row[1] = pack(__float_as_int(x), __float_as_int(y));
+  row[2] = pack(st, cd);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) row[3 + k] = (unsigned long long)__double_as_longlong(st == 2 ? X[k] : vo_state_dev::dnan());
+}
+
 // vo_pipeline_rewind: the control block as it was at the checkpoint, except what lives on the reference's estimator
 // object (RANSAC.n_iterations / outlier_ratio, ransac.py:47-56) and the generator position, which go on
-__global__ __launch_bounds__(64) void ctl_rewind_kernel(vo_seq_ctl* __restrict__ ctl, const vo_seq_ctl* __restrict__ saved, int S) {
+__global__ __launch_bounds__(64) void ctl_rewind_kernel(vo_seq_ctl* __restrict__ ctl, const vo_seq_ctl* __restrict__ saved, int S,
+                                                        int id_par) {
   const int q = blockIdx.x * 64 + threadIdx.x;
   if (q >= S) return;
   vo_seq_ctl c = saved[q];
@@ -30,6 +58,8 @@ __global__ __launch_bounds__(64) void ctl_rewind_kernel(vo_seq_ctl* __restrict__
   c.raw_pos = ctl[q].raw_pos;
   c.step = ctl[q].step;
   c.nf[0] = c.nf[1] = c.num_features;     // (whichever parity the next step has: vo_seq_ctl.nf)
+  c.next_id[0] = c.next_id[1] = saved[q].next_id[id_par];   // (the slot the step after the checkpoint was to read)
+  c.id_step[0] = c.id_step[1] = c.step;
   ctl[q] = c;
 }
 
@@ -108,6 +138,11 @@ static int upload_state(vo_pipeline* p, int seq, int n, const double* kp, const 
     VO_HIP_TRY(ctx, mcpy(st, F.track, tracks, (size_t)n * 16, hipMemcpyHostToDevice));
     for (int k = 0; k < 12; ++k)
       VO_HIP_TRY(ctx, mcpy(st, F.pose + (size_t)k * F.pitch, &pose12[(size_t)k * n], (size_t)n * 8, hipMemcpyHostToDevice));
+    if (F.ids) {
+      std::vector<int32_t> ids((size_t)n * 2, 0);
+      for (int i = 0; i < n; ++i) ids[(size_t)2 * i] = i;
+      VO_HIP_TRY(ctx, mcpy(st, F.ids, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    }
   }
   vo_seq_ctl h;
   VO_HIP_TRY(ctx, mcpy(st, &h, p->d_ctl + seq, sizeof(h), hipMemcpyDeviceToHost));
@@ -119,6 +154,7 @@ static int upload_state(vo_pipeline* p, int seq, int n, const double* kp, const 
   h.n2 = n;
   h.num_features = num_features;
   h.nf[0] = h.nf[1] = num_features;
+  h.next_id[0] = h.next_id[1] = n;       // (track ids: 0 .. n-1 in feature order, born 0)
   h.raw_pos = raw_pos;
   if (keep_ransac) {
     h.n_iterations = n_it;
@@ -238,6 +274,7 @@ extern "C" int vo_pipeline_checkpoint(vo_pipeline* p) {
   }
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   p->ckpt_frame = p->prev_frame;
+  p->ckpt_par = (int)(p->steps_submitted & 1);
   return VO_OK;
 }
 
@@ -255,7 +292,7 @@ extern "C" int vo_pipeline_rewind(vo_pipeline* p) {
   if (p->cfg.tracker_mode != 0)
     VO_HIP_TRY(ctx, hipMemcpyAsync(p->fdesc(p->cur, 0), p->d_ckpt_fdesc, (size_t)p->S * p->cap * p->desc_row,
                                    hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(ctl_rewind_kernel, dim3(vo_cdiv(p->S, 64)), dim3(64), 0, st, p->d_ctl, p->d_ckpt_ctl, p->S);
+  hipLaunchKernelGGL(ctl_rewind_kernel, dim3(vo_cdiv(p->S, 64)), dim3(64), 0, st, p->d_ctl, p->d_ckpt_ctl, p->S, p->ckpt_par);
   VO_TRY(vo_check_launch(ctx, "ctl_rewind_kernel"));
   // the next step's tracker waits for "the previous step's regroup": that event now stands for the restored state
   if (p->steps_submitted > 0) VO_HIP_TRY(ctx, hipEventRecord(p->evRegroup[(p->steps_submitted - 1) & 1], st));
@@ -458,7 +495,10 @@ int vo_pipeline_bookkeeping(vo_pipeline* p, int phases, const double* new_kp, in
                  "pipeline_bookkeeping: pair %d = (%d, %d) is out of range", k, (int)pairs[2 * k], (int)pairs[2 * k + 1]);
     VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_newkp, new_kp, (size_t)n2 * 16, hipMemcpyHostToDevice, st));
     VO_HIP_TRY(ctx, hipMemcpyAsync(p->d_pairs, pairs, (size_t)M * 8, hipMemcpyHostToDevice, st));
-    VO_TRY(vo_state_regroup_pairs(ctx, p->d_ctl, p->F[p->cur], p->F[1 - p->cur], p->d_pairs, M, p->d_newkp, n2, p->cap));
+    vo_pairs_batch bt;                 // (track ids: the slot the next submitted step reads)
+    bt.par = (int)(p->steps_submitted & 1);
+    VO_TRY(vo_state_regroup_pairs(ctx, p->d_ctl, p->F[p->cur], p->F[1 - p->cur], p->d_pairs, M, p->d_newkp, n2, p->cap, nullptr,
+                                  nullptr, nullptr, 1, &bt));
     VO_HIP_TRY(ctx, hipStreamSynchronize(st));
     p->cur = 1 - p->cur;
     vo_seq_ctl h;
@@ -466,6 +506,8 @@ int vo_pipeline_bookkeeping(vo_pipeline* p, int phases, const double* new_kp, in
     memcpy(h.T_in_wc, T_wc, 96);
     memcpy(h.T_in_cw, T_cw, 96);
     h.n_cand = h.n_dropped = h.n_land = h.done = 0;
+    h.next_id[bt.par] = h.next_id[bt.par ^ 1];     // (no step was submitted: the parity stays, the word moves)
+    h.id_step[bt.par] = h.id_step[bt.par ^ 1];
     VO_HIP_TRY(ctx, mcpy(st, p->d_ctl, &h, sizeof(h), hipMemcpyHostToDevice));
     std::vector<uint64_t> bits((size_t)p->words, ~0ull);
     if (p3p_inliers)
@@ -503,6 +545,95 @@ int vo_pipeline_export_state_post_seq(vo_pipeline* p, int seq, const vo_step_res
                        vo_feat_seq(p->F[p->last_fbuf], (size_t)seq).land, n, cap, d_record);
   }
   return vo_check_launch(ctx, "export_state_kernel");
+}
+
+// ---- track ids (vo_hip.h) ----
+
+static int check_track_ids(vo_pipeline* p, const char* who, int seq, bool idle_needed) {
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, p->cfg.track_ids != 0, "%s: the pipeline was created without track_ids", who);
+  VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "%s: bad sequence index", who);
+  if (idle_needed) VO_REQUIRE(ctx, p->n_flight == 0, "%s: %d submitted step(s) not collected", who, p->n_flight);
+  return VO_OK;
+}
+
+size_t vo_pipeline_tracks_record_bytes(int cap) { return (size_t)16 + (size_t)48 * (size_t)(cap > 0 ? cap : 0); }
+
+int vo_pipeline_get_track_ids_seq(vo_pipeline* p, int seq, int32_t* ids, int32_t* born, int32_t* n_out, int32_t* next_id) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_TRY(check_track_ids(p, "pipeline_get_track_ids", seq, true));
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  vo_seq_ctl h;
+  VO_HIP_TRY(ctx, mcpy(st, &h, p->d_ctl + seq, sizeof(h), hipMemcpyDeviceToHost));
+  const int n = std::max(0, std::min(h.n, p->cap));
+  if (n_out) *n_out = n;
+  if (next_id) *next_id = h.next_id[p->steps_submitted & 1];
+  if (n > 0 && (ids || born)) {
+    std::vector<int32_t> b((size_t)n * 2);
+    VO_HIP_TRY(ctx, mcpy(st, b.data(), vo_feat_seq(p->F[p->cur], (size_t)seq).ids, b.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+      if (ids) ids[i] = b[(size_t)2 * i];
+      if (born) born[i] = b[(size_t)2 * i + 1];
+    }
+  }
+  return VO_OK;
+}
+
+int vo_pipeline_set_track_ids_seq(vo_pipeline* p, int seq, const int32_t* ids, const int32_t* born, int n, int32_t next_id) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_TRY(check_track_ids(p, "pipeline_set_track_ids", seq, true));
+  VO_REQUIRE(ctx, p->have_state, "pipeline_set_track_ids: no state was handed over");
+  VO_REQUIRE(ctx, n >= 0 && (n == 0 || ids) && next_id >= 0, "pipeline_set_track_ids: bad arguments");
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  vo_seq_ctl h;
+  VO_HIP_TRY(ctx, mcpy(st, &h, p->d_ctl + seq, sizeof(h), hipMemcpyDeviceToHost));
+  VO_REQUIRE(ctx, n == h.n, "pipeline_set_track_ids: %d ids for the sequence's %d features", n, (int)h.n);
+  {
+    std::vector<int32_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int i = 0; i < n; ++i) {
+      VO_REQUIRE(ctx, sorted[i] >= 0 && sorted[i] < next_id, "pipeline_set_track_ids: id %d is not in 0 .. next_id - 1 = %d",
+                 (int)sorted[i], (int)next_id - 1);
+      VO_REQUIRE(ctx, i == 0 || sorted[i] != sorted[i - 1], "pipeline_set_track_ids: id %d is given twice", (int)sorted[i]);
+    }
+  }
+  const vo_feat F = vo_feat_seq(p->F[p->cur], (size_t)seq);
+  if (n > 0) {
+    std::vector<int32_t> b((size_t)n * 2);
+    VO_HIP_TRY(ctx, mcpy(st, b.data(), F.ids, b.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+      b[(size_t)2 * i] = ids[i];
+      if (born) b[(size_t)2 * i + 1] = born[i];
+    }
+    VO_HIP_TRY(ctx, mcpy(st, F.ids, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+  }
+  const int32_t both[2] = {next_id, next_id};
+  VO_HIP_TRY(ctx, mcpy(st, &p->d_ctl[seq].next_id[0], both, 8, hipMemcpyHostToDevice));
+  return VO_OK;
+}
+
+int vo_pipeline_export_tracks_post_seq(vo_pipeline* p, int seq, const vo_step_result* r, int cap, void* d_record) {
+  if (!p || !r || !d_record) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_TRY(check_track_ids(p, "pipeline_export_tracks", seq, false));
+  VO_REQUIRE(ctx, cap >= 0 && ((uintptr_t)d_record & 15) == 0, "pipeline_export_tracks: bad capacity or record alignment");
+  VO_REQUIRE(ctx, p->n_flight <= 1, "pipeline_export_tracks: the features of the step collected last are being overwritten");
+  const int n = std::max(0, std::min((int)r->n_tracked, p->cap));
+  // (the same buffer, and the same reasoning, as vo_pipeline_export_state_post_seq; the step collected last was flight
+  //  last_k, so its regroup left next_id and the step counter in slot (last_k + 1) & 1, which only the step after next rewrites)
+  {
+    vo_prof_scope ps(ctx, VO_K_EXPORT);
+    hipLaunchKernelGGL(export_tracks_kernel, dim3(vo_cdiv(std::max(std::min(n, cap), 1), 256)), dim3(256), 0, ctx->stream,
+                       vo_feat_seq(p->F[p->last_fbuf], (size_t)seq), (const vo_seq_ctl*)(p->d_ctl + seq),
+                       (int)((p->last_k + 1) & 1), n, cap, seq, (unsigned long long*)d_record);
+  }
+  return vo_check_launch(ctx, "export_tracks_kernel");
 }
 
 int vo_pipeline_export_state_post(vo_pipeline* p, const vo_step_result* r, int cap, double* d_record) {

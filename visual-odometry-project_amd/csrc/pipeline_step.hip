@@ -339,10 +339,8 @@ static int enqueue_chain(vo_pipeline* p, const vo_pipeline::flight_t& f, bool fi
   ap.pose_mode = c.redetect_start_pose;
   ap.debug_fault_every = debug_fault_every > 0 ? debug_fault_every : 0;
   ap.det_go = p->d_det_go + (size_t)f.a * p->S + q0;
-  if (p->d_det_cnt) {
-    ap.n_det_dev = p->d_det_cnt + (size_t)f.a * p->S + q0;
-    ap.nf_par = (int)(f.k & 1);
-  }
+  ap.nf_par = (int)(f.k & 1);
+  if (p->d_det_cnt) ap.n_det_dev = p->d_det_cnt + (size_t)f.a * p->S + q0;
   ctx->next_stop = p->evRegroup[f.k & 1];
   VO_TRY(vo_state_regroup_klt(ctx, ctl, A, B, p->d_next + q * p->cap * 2, p->d_status + q * p->cap, p->d_err + q * p->cap,
                               (float)c.klt_err_threshold, ap, p->cap, Sn));
@@ -467,6 +465,7 @@ static int enqueue_chain_desc(vo_pipeline* p, const vo_pipeline::flight_t& f, bo
   bt.M = 1;
   bt.n2 = 1;
   bt.debug_fault_every = debug_fault_every > 0 ? debug_fault_every : 0;
+  bt.par = (int)(f.k & 1);
   if (harris) {
     new_kp = p->kp(q0, f.b);           // the detector's keypoints are float64 pairs already
     bt.new_kp = p->det_stride();
@@ -1024,6 +1023,7 @@ int vo_pipeline_collect_all(vo_pipeline* p, vo_step_result* outs) {
   p->flight[0] = p->flight[1];
   --p->n_flight;
   p->last_fbuf = 1 - f.fcur;
+  p->last_k = f.k;
   return VO_OK;
 }
 

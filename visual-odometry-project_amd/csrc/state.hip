@@ -57,8 +57,11 @@ __device__ __forceinline__ unsigned long long block_scan_excl(unsigned long long
   return r;
 }
 
+// IDS: the track's (id, born) pair travels with its keypoint -- one 8-byte load, one 8-byte store
+template <bool IDS>
 __device__ __forceinline__ void write_group(const vo_feat& A, const vo_feat& B, int g, int src, int dst, double x,
                                             double y) {
+  if (IDS) B.ids[dst] = A.ids[src];
   B.kp[2 * dst] = (float)x;
   B.kp[2 * dst + 1] = (float)y;
   B.kp64[2 * dst] = x;
@@ -96,7 +99,10 @@ constexpr int RG_MAX_PER = 32;   // items per thread: capacity 32768
 //                 new keypoints without a match follow as the unmatched group.
 // PAIRS: one workgroup per sequence (blockIdx.x): its control block, Features blocks, pair list, new keypoints, counts and
 // src_row at the strides of `bt` (vo_state.h, vo_pairs_batch)
-template <bool PAIRS>
+// IDS (vo_pipeline_config.track_ids; PAIRS only): a feature written from pair (i1, i2) keeps the (id, born) of old feature i1;
+// the unmatched new keypoints, in the order they are written, get id = next_id + r and born = step + 1 (the new frame's
+// number), and next_id grows by their count (vo_seq_ctl.next_id: read from slot bt.par, written to the other).
+template <bool PAIRS, bool IDS>
 __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat A, vo_feat B,
                                                              const float* __restrict__ next_xy,
                                                              const uint8_t* __restrict__ status,
@@ -137,6 +143,7 @@ __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restr
     n2_in = min(*d_n2, cap);
   }
   const int n_items = PAIRS ? M : ctl->n_in;
+  const int nid = IDS ? ctl->next_id[bt.par] : 0, step_k = IDS ? ctl->step : 0;
   const int per = (n_items + RG_T - 1) / RG_T;
   const int j0 = tid * per, j1 = min(j0 + per, n_items);
   if (PAIRS) {
@@ -180,7 +187,7 @@ __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restr
       y = (double)next_xy[2 * j + 1];
     }
     if (PAIRS && src_row) src_row[pos[key]] = pairs[2 * j + 1];      // (which new keypoint ended up at this place)
-    write_group(A, B, key, src, pos[key]++, x, y);
+    write_group<IDS>(A, B, key, src, pos[key]++, x, y);
   }
   int n2 = T0 + T1 + T2;
   if (PAIRS) {
@@ -191,6 +198,7 @@ __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restr
     for (int k = k0; k < k1; ++k) c += ((s_matched[k >> 5] >> (k & 31)) & 1u) ? 0ull : 1ull;
     unsigned long long tot2;
     int p = n2 + (int)block_scan_excl(c, s_wave, &tot2);
+    const int id_off = nid - n2;       // (the r-th unmatched keypoint is written at n2 + r)
     const double nan = dnan();
     for (int k = k0; k < k1; ++k) {
       if ((s_matched[k >> 5] >> (k & 31)) & 1u) continue;
@@ -207,9 +215,14 @@ __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restr
 #pragma unroll
       for (int q = 0; q < 12; ++q) B.pose[(size_t)q * B.pitch + p] = nan;
       if (src_row) src_row[p] = k;
+      if (IDS) B.ids[p] = make_int2(id_off + p, step_k + 1);
       ++p;
     }
     n2 += (int)tot2;
+    if (IDS && tid == 0) {
+      ctl->next_id[bt.par ^ 1] = nid + (int)tot2;
+      ctl->id_step[bt.par ^ 1] = step_k + 1;
+    }
   }
   if (tid == 0) {
     ctl->n2 = n2;
@@ -238,6 +251,10 @@ __global__ __launch_bounds__(RG_T) void state_regroup_kernel(vo_seq_ctl* __restr
 // copy: when fewer than frac * _num_features features are left, items n .. n + n_det - 1 ARE the detector's
 // keypoints of the old frame (state 0, landmark NaN, track start = the keypoint, start pose np.eye(4)) -- the
 // tracker kernel read its points the same way (vo_klt_source).
+// IDS (vo_pipeline_config.track_ids): every survivor keeps its (id, born) pair; appended keypoint d gets id = next_id + d
+// and born = step, and next_id grows by the appended count whether or not the filter keeps them (vo_seq_ctl.next_id: every
+// workgroup reads slot ap.nf_par, block 0 writes the other).
+template <bool IDS>
 __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __restrict__ ctl, vo_feat A, vo_feat B,
                                                                 const float* __restrict__ next_xy,
                                                                 const uint8_t* __restrict__ status,
@@ -265,6 +282,7 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
   const int entry_fault = ctl->fault;
   int fault = entry_fault;
   const int n = ctl->n;
+  const int nid = IDS ? ctl->next_id[ap.nf_par] : 0, step_k = IDS ? ctl->step : 0;
   if (ap.debug_fault_every > 0 && (ctl->step % ap.debug_fault_every) == ap.debug_fault_every - 1) fault |= VO_FAULT_FORCED;
   // `length < self._num_features * 0.8` (klt.py:208-212)
   const int nf = ap.n_det_dev ? ctl->nf[ap.nf_par] : ctl->num_features;
@@ -318,6 +336,8 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
   }
 #pragma unroll
   for (int k = 0; k < 12; ++k) o_pose[k] = A.pose[(size_t)k * A.pitch + jq];
+  int2 o_id = make_int2(0, 0);
+  if (IDS) o_id = A.ids[jq];           // (with the loads above: one more request of the same round trip, not one behind it)
   auto key_of = [&](int j) -> int {      // 0 triangulated, 1 matched, 2 newly matched, 3 dropped
     // (unconditional loads at clamped indices, no short-circuit: the three requests of an item, and those of the
     //  following items, go out together instead of one dependent round trip after the other)
@@ -393,6 +413,7 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
       B.kp64[2 * dst] = x;
       B.kp64[2 * dst + 1] = y;
       B.cand[dst] = 0;
+      if (IDS) B.ids[dst] = o_id;
       if (my_key == 0) {       // triangulated: the landmark travels, the track data is over (matches.py:146-201)
         B.state[dst] = 2;
 #pragma unroll
@@ -416,6 +437,7 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
       B.kp64[2 * dst] = x;
       B.kp64[2 * dst + 1] = y;
       B.cand[dst] = 0;
+      if (IDS) B.ids[dst] = make_int2(nid + d, step_k);
       B.state[dst] = 1;
       B.land[3 * dst] = B.land[3 * dst + 1] = B.land[3 * dst + 2] = dnan();
       B.track[2 * dst] = (double)(float)ap.det_kp[2 * d];
@@ -433,6 +455,10 @@ __global__ __launch_bounds__(256) void state_regroup_klt_kernel(vo_seq_ctl* __re
       const int nf_next = redetect ? n_det : nf;
       ctl->nf[ap.nf_par ^ 1] = nf_next;
       ctl->num_features = nf_next;
+    }
+    if (IDS) {                         // (a keypoint the filter dropped has used up its id)
+      ctl->next_id[ap.nf_par ^ 1] = nid + (n_in - n);
+      ctl->id_step[ap.nf_par ^ 1] = step_k + 1;
     }
     ctl->n2 = T0 + T1 + T2;
     ctl->n_tri = T0;
@@ -799,8 +825,12 @@ int vo_state_regroup_klt(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, con
                          const uint8_t* d_status, const float* d_err, float err_thr, vo_append ap, int cap, int S) {
   {
     vo_prof_scope ps(ctx, VO_K_STATE_REGROUP);
-    vo_launch_stop(ctx, state_regroup_klt_kernel, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, A, B, d_next_xy,
-                   d_status, d_err, err_thr, ap, cap);
+    if (A.ids)
+      vo_launch_stop(ctx, state_regroup_klt_kernel<true>, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, A, B,
+                     d_next_xy, d_status, d_err, err_thr, ap, cap);
+    else
+      vo_launch_stop(ctx, state_regroup_klt_kernel<false>, dim3(vo_cdiv(cap, 256), S), dim3(256), 0, ctx->stream, ctl, A, B,
+                     d_next_xy, d_status, d_err, err_thr, ap, cap);
   }
   return vo_check_launch(ctx, "state_regroup_klt_kernel");
 }
@@ -813,7 +843,8 @@ int vo_state_regroup_pairs(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, c
   const vo_pairs_batch bt = batch ? *batch : vo_pairs_batch{};
   {
     vo_prof_scope ps(ctx, VO_K_STATE_REGROUP);
-    hipLaunchKernelGGL(state_regroup_kernel<true>, dim3(S), dim3(RG_T), 0, ctx->stream, ctl, A, B, (const float*)nullptr,
+    auto kernel = A.ids ? state_regroup_kernel<true, true> : state_regroup_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(S), dim3(RG_T), 0, ctx->stream, ctl, A, B, (const float*)nullptr,
                        (const uint8_t*)nullptr, (const float*)nullptr, 0.f, d_pairs, M, d_new_kp, n2_in, cap,
                        (const int*)d_M, (const int*)d_n2, (int*)d_src_row, bt);
   }

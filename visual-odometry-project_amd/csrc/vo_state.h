@@ -21,6 +21,8 @@ struct vo_feat {
   double* pose;      // 12 x pitch (component-major: entry k of feature i at pose[k * pitch + i]): rows 0..2 of the
                      // 4x4 camera-to-world pose at the track's start (NaN = none)
   int pitch;         // = capacity
+  int2* ids = nullptr;   // cap x (id, born): the track's identity and the step counter's value for the frame it was first seen
+                     // on (vo_hip.h, "track ids"); NULL unless vo_pipeline_config.track_ids
 };
 
 // Several sequences per launch: every array of a vo_feat holds S consecutive per-sequence blocks of `pitch`
@@ -34,6 +36,7 @@ __host__ __device__ inline vo_feat vo_feat_seq(vo_feat F, size_t q) {
   F.land += 3 * n;
   F.track += 2 * n;
   F.pose += 12 * n;
+  if (F.ids) F.ids += n;
   return F;
 }
 
@@ -90,6 +93,13 @@ struct vo_seq_ctl {
   // nf[(k + 1) & 1]: the regroup's other workgroups, and a step redone after a fault, never read a word this step wrote.
   // num_features above follows as a copy (what vo_pipeline_get_state returns).  A state hand-over sets all three.
   int32_t nf[2];
+  // Track ids (vo_pipeline_config.track_ids): the next id to issue, under the same discipline -- step k reads next_id[k & 1]
+  // and its regroup writes next_id[(k + 1) & 1], so a step that is redone (the host path after a fault of the regroup OR of
+  // the pose kernel, a step enqueued again behind a continued RANSAC loop) issues the ids it issued the first time.
+  // id_step: the step counter as it will stand when the step has closed, kept the same way -- what the observation record
+  // of step k reads from slot (k + 1) & 1 while step k + 1 may already have run.  A hand-over and a rewind set both slots.
+  int32_t next_id[2];
+  int32_t id_step[2];
 };
 
 struct vo_cam {
@@ -111,7 +121,7 @@ struct vo_append {
   const int32_t* n_det_dev = nullptr; // per sequence, NULL or: the detector's count on the device (Shi-Tomasi: 0 .. n_det corners;
                             // below 0: the frame's candidate lists overflowed, a capacity fault) -- what is appended instead
                             // of n_det, and what KLTTracker._num_features becomes (klt.py:114)
-  int nf_par = 0;           // with n_det_dev: the step's parity, see vo_seq_ctl.nf
+  int nf_par = 0;           // the step's parity, see vo_seq_ctl.nf (with n_det_dev) and vo_seq_ctl.next_id (track ids)
 };
 
 struct vo_replay_args {
@@ -158,6 +168,7 @@ int vo_frame_pose(vo_ctx* ctx, const vo_pose_job& job, int S = 1);   // S > 1: s
 // 4-group regroup of the new frame
 int vo_state_regroup_klt(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, const float* d_next_xy,
                          const uint8_t* d_status, const float* d_err, float err_thr, vo_append ap, int cap, int S = 1);
+// (both regroups: with A.ids != NULL the kernels that carry and issue track ids run, else the ones without a word of it)
 // matches.py:26-212 for an explicit match list (harris / sift trackers, tests)
 // d_M / d_n2 (optional): the pair count and the new frame's keypoint count read on the device (M and n2_in are then the
 // capacities); d_src_row (optional, cap ints): for every feature written to B, the new keypoint it is
@@ -168,6 +179,7 @@ struct vo_pairs_batch {
   size_t src_row = 0;            // d_src_row + q * src_row
   int M = 0, n2 = 0;             // d_M + q * M, d_n2 + q * n2
   int debug_fault_every = 0;     // test hook (vo_pipeline_config.debug_fault_every): the step faults here (VO_FAULT_FORCED)
+  int par = 0;                   // track ids: the step's parity, see vo_seq_ctl.next_id
 };
 int vo_state_regroup_pairs(vo_ctx* ctx, vo_seq_ctl* ctl, vo_feat A, vo_feat B, const int32_t* d_pairs, int M,
                            const double* d_new_kp, int n2_in, int cap, const int32_t* d_M = nullptr,

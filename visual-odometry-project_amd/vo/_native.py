@@ -73,7 +73,8 @@ class PipelineConfig(C.Structure):
                 ("bearing_threshold", C.c_double), ("redetect_fraction", C.c_double),
                 ("debug_fault_every", C.c_int32), ("redetect_start_pose", C.c_int32), ("detect_margin", C.c_double),
                 ("debug_never_detect", C.c_int32), ("detect_losses", C.c_double), ("sequences", C.c_int32),
-                ("tracker_mode", C.c_int32), ("sift_cap", C.c_int32), ("match_ratio", C.c_double),
+                ("tracker_mode", C.c_int32), ("sift_cap", C.c_int32), ("track_ids", C.c_int32),
+                ("match_ratio", C.c_double),
                 ("detector", C.c_int32), ("st_block", C.c_int32), ("st_quality", C.c_double),
                 ("st_min_distance", C.c_double)]
 
@@ -243,6 +244,10 @@ _SIGS = {
     "vo_pipeline_get_rng_seq": (_i, [_vp, _i, _vp]),
     "vo_pipeline_collect_all": (_i, [_vp, _vp]),
     "vo_pipeline_export_state_post_seq": (_i, [_vp, _i, _vp, _i, _vp]),
+    "vo_pipeline_tracks_record_bytes": (_sz, [_i]),
+    "vo_pipeline_get_track_ids_seq": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "vo_pipeline_set_track_ids_seq": (_i, [_vp, _i, _vp, _vp, _i, C.c_int32]),
+    "vo_pipeline_export_tracks_post_seq": (_i, [_vp, _i, _vp, _i, _vp]),
     "vo_pipeline_set_camera_seq": (_i, [_vp, _i, _vp, _vp]),
     "vo_pipeline_set_active_seq": (_i, [_vp, _i, _i]),
     "vo_pipeline_restart_seq": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

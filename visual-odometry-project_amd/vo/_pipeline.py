@@ -25,6 +25,30 @@ def _as_4x4(pose):
 
 DETECTORS = {"harris": 0, "shi-tomasi": 1}       # vo_pipeline_config.detector
 
+# one row of the observation record (vo_pipeline_export_tracks_post_seq): 48 bytes
+TRACK_ROW = np.dtype([("id", "<i4"), ("born", "<i4"), ("x", "<f4"), ("y", "<f4"), ("state", "<i4"), ("candidate", "<i4"),
+                      ("X", "<f8"), ("Y", "<f8"), ("Z", "<f8")])
+TRACK_HEADER = np.dtype([("n", "<i4"), ("step", "<i4"), ("next_id", "<i4"), ("seq", "<i4")])
+
+
+class TrackRecord(np.ndarray):
+    """The rows of one observation record (dtype TRACK_ROW) with the header's words as attributes: n (the step's feature
+    count; len() is min(n, cap)), step (the sequence's step counter after the step), next_id, seq."""
+    n = step = next_id = seq = 0
+
+    def __array_finalize__(self, obj):
+        for k in ("n", "step", "next_id", "seq"):
+            setattr(self, k, getattr(obj, k, 0))
+
+    @classmethod
+    def from_bytes(cls, raw, cap):
+        raw = np.ascontiguousarray(raw, np.uint8)
+        head = raw[:16].view(TRACK_HEADER)[0]
+        m = max(0, min(int(head["n"]), int(cap)))
+        rec = raw[16:16 + 48 * m].view(TRACK_ROW).copy().view(cls)
+        rec.n, rec.step, rec.next_id, rec.seq = (int(head[k]) for k in ("n", "step", "next_id", "seq"))
+        return rec
+
 
 class Pipeline:
     def __init__(self, ctx, H, W, n_frames, K, n_keypoints=2000, harris_patch=9, harris_kappa=0.09, nms_radius=5,
@@ -33,7 +57,7 @@ class Pipeline:
                  max_iterations=1000, seed=2023, refine_iters=0, feature_cap=0, bearing_threshold=0.0075,
                  redetect_fraction=0.8, debug_fault_every=0, redetect_start_pose="identity", sequences=1,
                  detect_margin=0.01, debug_never_detect=0, detect_losses=2.5, tracker="klt", sift_cap=0, match_ratio=0.0,
-                 detector="harris", st_quality=0.0, st_min_distance=0.0, st_block=0):
+                 detector="harris", st_quality=0.0, st_min_distance=0.0, st_block=0, track_ids=False):
         from vo import _native
         self.ctx = ctx
         self.cfg = _native.PipelineConfig()
@@ -62,6 +86,8 @@ class Pipeline:
         # cv2.goodFeaturesToTrack with maxCorners = n_keypoints; st_* left at 0: klt.py:24-26's 0.01 / 8 / 7)
         c.detector = DETECTORS[detector]
         c.st_quality, c.st_min_distance, c.st_block = float(st_quality), float(st_min_distance), int(st_block)
+        c.track_ids = 1 if track_ids else 0          # persistent track ids (vo_hip.h, "Track ids")
+        self.track_ids = bool(track_ids)
         self.detector = detector
         self.tracker = tracker
         self.sequences = int(sequences)
@@ -298,7 +324,45 @@ class Pipeline:
         s = self.get_state(seq)
         f = Features(keypoints=s["keypoints"], landmarks=s["landmarks"])
         f.state, f.tracks, f.poses, f.candidate_mask = s["state"], s["tracks"], s["poses"], s["candidate_mask"]
+        if self.track_ids:
+            f.uids = self.get_track_ids(seq)[0].astype(np.int64)
         return f
+
+    # ---- track ids ----
+    def get_track_ids(self, seq=0):
+        """(ids, born, next_id) of sequence `seq`'s current features (track_ids=True; nothing in flight): two int32 arrays
+        in feature order -- the track's identity and the step counter's value for the frame it was first seen on -- and the
+        next id the sequence will issue."""
+        ids, born = np.empty(self.cap, np.int32), np.empty(self.cap, np.int32)
+        n, nxt = C.c_int32(), C.c_int32()
+        self.ctx._chk(self.ctx._lib.vo_pipeline_get_track_ids_seq(self._h, int(seq), _ptr(ids), _ptr(born), C.byref(n),
+                                                                  C.byref(nxt)))
+        return ids[:n.value].copy(), born[:n.value].copy(), int(nxt.value)
+
+    def set_track_ids(self, ids, next_id, born=None, seq=0):
+        """Replaces the ids of sequence `seq`'s current features (one per feature, distinct, 0 <= id < next_id) and the next
+        id it issues; born: None leaves it as it is.  Nothing in flight; a refused call raises VoError and changes nothing."""
+        ids = _c(np.asarray(ids).reshape(-1), np.int32)
+        b = None if born is None else _c(np.asarray(born).reshape(-1), np.int32)
+        if b is not None and b.shape != ids.shape:
+            raise ValueError("set_track_ids: %d born values for %d ids" % (b.size, ids.size))
+        self.ctx._chk(self.ctx._lib.vo_pipeline_set_track_ids_seq(self._h, int(seq), _ptr(ids), _ptr(b), ids.size,
+                                                                  int(next_id)))
+
+    def tracks_record_bytes(self, cap):
+        return int(self.ctx._lib.vo_pipeline_tracks_record_bytes(int(cap)))
+
+    def export_tracks_post(self, result, cap, d_record, seq=0):
+        """Queues the observation record of the step collected last (`result`: its StepResult) of sequence `seq` on the
+        pipeline's stream into device memory d_record (tracks_record_bytes(cap) bytes, 16-byte aligned); no
+        synchronisation -- export_state_join orders it against a consumer."""
+        self.ctx._chk(self.ctx._lib.vo_pipeline_export_tracks_post_seq(self._h, int(seq), C.byref(result), int(cap),
+                                                                       C.c_void_p(d_record)))
+
+    def read_tracks_record(self, d_record, cap):
+        """Downloads a record the pipeline's stream has written (a blocking copy on that stream, so behind the kernel that
+        writes it) and returns it as a TrackRecord: a structured array of its min(n, cap) rows, the header as attributes."""
+        return TrackRecord.from_bytes(self.ctx.download(d_record, (self.tracks_record_bytes(cap),), np.uint8), cap)
 
     def get_detection(self, seq=0):
         """The detector's keypoints of the frame submitted last, sequence `seq`: (n, 2) float64 -- n_keypoints rows with

@@ -105,10 +105,69 @@ def _gray(image):
     return g(image)
 
 
+class _TrackTap:
+    """The observation records of the collected steps (Pipeline.export_tracks_post), without giving up the look-ahead: a
+    record is posted right after its step's collect -- behind the step in flight on the pipeline's stream --, ordered
+    before a side context's stream (export_state_join), and downloaded on that stream when the NEXT step is collected, by
+    which time it has long been written.  Two device buffers per lane, used in turn."""
+
+    def __init__(self, ctx, pipe, lanes=1):
+        from vo import _native
+        self.ctx, self.pipe = ctx, pipe
+        self.side = _native.Context(ctx.device)          # (its own stream: a copy on the pipeline's would wait for the step in flight)
+        self.nbytes = pipe.tracks_record_bytes(pipe.cap)
+        self.ring = [[ctx.alloc(self.nbytes) for _ in range(lanes)] for _ in range(2)]
+        self.turn = 0
+        self.posted = []                                 # (device buffer, the list the record is appended to)
+
+    def flush(self):
+        from vo._pipeline import TrackRecord
+        for d_rec, sink in self.posted:
+            sink.append(TrackRecord.from_bytes(self.side.download(d_rec, (self.nbytes,), np.uint8), self.pipe.cap))
+        self.posted = []
+
+    def post(self, items):
+        """items: (lane, the step's StepResult, the list its record goes to) of the step collected just now."""
+        self.flush()
+        for lane, r, sink in items:
+            d_rec = self.ring[self.turn][lane]
+            self.pipe.export_tracks_post(r, self.pipe.cap, d_rec, seq=lane)
+            self.posted.append((d_rec, sink))
+        self.pipe.export_state_join(self.side.stream)
+        self.turn ^= 1
+
+    def close(self):
+        self.flush()
+        for row in self.ring:
+            for d in row:
+                self.ctx.free(d)
+        self.side.close()
+
+
+def track_table(observations):
+    """What a back end ingests from the per-step observation records (run_on_device(..., tracks=True)["observations"]):
+    {id: dict(steps=(m,) int indices into `observations`, keypoints=(m, 2) float32, born=int, landmark=(3,) float64 -- the
+    last one the track had, NaN if it never had one)}.  Host arithmetic."""
+    table = {}
+    for t, rec in enumerate(observations):
+        for row in rec:
+            e = table.setdefault(int(row["id"]), dict(steps=[], keypoints=[], born=int(row["born"]),
+                                                       landmark=np.full(3, np.nan)))
+            e["steps"].append(t)
+            e["keypoints"].append((row["x"], row["y"]))
+            if row["state"] == 2:
+                e["landmark"] = np.array([row["X"], row["Y"], row["Z"]], np.float64)
+    for e in table.values():
+        e["steps"] = np.array(e["steps"], np.int64)
+        e["keypoints"] = np.array(e["keypoints"], np.float32).reshape(-1, 2)
+    return table
+
+
 def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
                   klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                   redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
-                  bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris"):
+                  bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
+                  tracks: bool = False):
     """Same loop, same bootstrap, but the steady state runs as the device-resident pipeline (vo_pipeline_*):
     after the host bootstrap the Features / State arrays are handed to the GPU once, every later frame costs one
     image upload and one call, and nothing but the pose record comes back.  KLT tracker mode with the Harris
@@ -127,7 +186,10 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     vo_pipeline_bootstrap_seq): same kernels, same result, no array brought back in between.
     Frames are uploaded as the sequence delivers them, grey or B, G, R; the pipeline's ingest makes them grey on the device.
     A camera with distortion_coeffs sets the lane's distortion (Pipeline.set_distortion: every frame is undistorted into
-    the pinhole camera K behind its upload); one that really distorts needs bootstrap="device"."""
+    the pinhole camera K behind its upload); one that really distorts needs bootstrap="device".
+    tracks: the pipeline keeps persistent track ids (Pipeline(track_ids=True)) and the result gains `observations`, one
+    TrackRecord per step (id, born, keypoint, state, candidate, landmark of every feature; track_table() turns them into
+    per-track observations) -- each posted behind its step and read back one collect later, so the look-ahead stays."""
     from vo import _native
     _check_bootstrap_route(bootstrap)
     ctx = context or _native.default_context()
@@ -137,8 +199,8 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     if bootstrap == "device":
         img0, img = _bootstrap_images(sequence)          # (as delivered: the pipeline's ingest makes them grey, undistorted)
         H, W = img.shape[:2]
-        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(None, n_keypoints, klt_win, klt_max_level, hyp,
-                                                                         redetect_start_pose, detector))
+        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, track_ids=tracks,
+                                **_pipeline_kwargs(None, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector))
         if dist is not None:
             pipe.set_distortion(0, dist)
         pipe.set_frame(1, img0)                          # (slot 1 takes frame 3 next: the bootstrap is done with it by then)
@@ -153,13 +215,19 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
         frame = state.curr_frame
         img = _gray(frame.image)
         H, W = img.shape
-        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, **_pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp,
-                                                                         redetect_start_pose, detector))
+        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, track_ids=tracks,
+                                **_pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector))
         pipe.set_frame(0, img)
         pipe.set_state(0, frame.features, state.curr_pose, state.prev_pose, num_features=tracker._tracker._num_features)
         trajectory = [np.eye(4), state.get_pose()]
         n_landmarks = [len(frame.features.triangulated_inliers_landmarks)]
-    seconds, results = [], []
+    seconds, results, observations = [], [], []
+    tap = _TrackTap(ctx, pipe) if tracks else None
+
+    def collect():
+        results.append(pipe.collect())
+        if tap:
+            tap.post([(0, results[-1], observations)])
     # Frames go through a ring of pinned buffers AS DELIVERED (three channels where the sequence gives three: the grey
     # conversion and the undistortion run on the device behind the DMA, csrc/ingest.hip) and are uploaded on the
     # pipeline's upload stream ONE STEP AHEAD of their use (vo_pipeline_set_frame_pinned / _bgr_pinned): while step
@@ -190,7 +258,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
         t0 = time.perf_counter()
         nxt = (slot + 1) % SLOTS
         if pending == 2:
-            results.append(pipe.collect())
+            collect()
             pending -= 1
         t1 = time.perf_counter()
         ahead = take()                                   # the frame of the NEXT step: its slot was read last by a collected step
@@ -204,8 +272,10 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
         slot = nxt
         seconds.append(time.perf_counter() - t0 - (t2 - t1))
     while pending:
-        results.append(pipe.collect())
+        collect()
         pending -= 1
+    if tap:
+        tap.close()
     for r in results:
         trajectory.append(r.pose_world_cam())
         n_landmarks.append(r.n_landmarks)
@@ -215,8 +285,11 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
                 ", re-detected" if r.redetected else ""))
     features = pipe.get_features()
     pipe.close()
-    return dict(trajectory=np.array(trajectory), n_landmarks=np.array(n_landmarks), frame_seconds=np.array(seconds),
-                results=results, features=features)
+    out = dict(trajectory=np.array(trajectory), n_landmarks=np.array(n_landmarks), frame_seconds=np.array(seconds),
+               results=results, features=features)
+    if tracks:
+        out["observations"] = observations
+    return out
 
 
 def _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold):
@@ -362,7 +435,8 @@ def _frame_shape(sequence):
 def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
                         klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
-                        bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris"):
+                        bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
+                        tracks: bool = False):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
     as run_on_device does it; when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
@@ -374,6 +448,8 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     recording the lane goes idle, frame 0 goes into the slot after the current one and frame 2 into the current one; the
     lanes that start at the same step (all of them at step 0) then go through ONE call (Pipeline.bootstrap_lanes).  (A
     recording without a steady-state step never holds a lane: host route.)  detector: as in run_on_device, for every lane.
+    tracks: as in run_on_device -- every recording's dict gains `observations`, one record per step it took (a lane's ids
+    start over with every recording: each start is a hand-over).
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
     each step the recording took part in).  Each lane computes what run_on_device computes for its recording alone."""
@@ -419,9 +495,10 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
         state0 = None if on_device else boot_of(first)[0]
         K0 = np.asarray(sequences[first].get_camera().intrinsic_matrix, np.float64)
         SLOTS = 4
-        pipe = _native.Pipeline(ctx, H, W, SLOTS, K0, sequences=lanes,
+        pipe = _native.Pipeline(ctx, H, W, SLOTS, K0, sequences=lanes, track_ids=tracks,
                                 **_pipeline_kwargs(state0, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose,
                                                    detector))
+        tap = _TrackTap(ctx, pipe, lanes) if tracks else None
         ring = [[None] * SLOTS for _ in range(lanes)]      # (frames as delivered, see run_on_device)
         lens = [_lens_of(s, bootstrap) for s in sequences]
         any_lens = any(d is not None for d in lens)
@@ -488,6 +565,9 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                     o["results"].append(rs[lane])
                     o["trajectory"].append(rs[lane].pose_world_cam())
                     o["n_landmarks"].append(rs[lane].n_landmarks)
+            if tap:
+                tap.post([(lane, rs[lane], out[e[0]].setdefault("observations", []))
+                          for lane, e in enumerate(steps[t]) if e is not None])
 
         events = {}
         for t, lane, r in plan["starts"]:
@@ -521,6 +601,8 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                 # a lane changes recording: drain, read what ends, then idle / restart (nothing in flight for either)
                 while pending:
                     collect_one()
+                if tap:
+                    tap.flush()                          # (a hand-over rewrites the buffers the posted records read)
                 for lane, r in sorted(events[t]):
                     prev = steps[t - 1][lane]
                     if prev is not None:
@@ -551,6 +633,8 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
         for lane, e in enumerate(steps[-1]):
             if e is not None:
                 finish(lane, e[0])
+        if tap:
+            tap.close()
         pipe.close()
     for o in out:
         o["trajectory"] = np.array(o["trajectory"])
