@@ -182,113 +182,34 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     reference's cv2.goodFeaturesToTrack (klt.py:24-26, maxCorners = n_keypoints): as many corners as the frame has, and
     the re-detect limit follows that count (klt.py:114).
     bootstrap: "host" -- the bootstrap through the drop-in classes, handed over with set_state; "device" -- frames 0 and 2
-    go into two slots of the frame store and the pipeline bootstraps itself from them (Pipeline.bootstrap,
-    vo_pipeline_bootstrap_seq): same kernels, same result, no array brought back in between.
+    go into two slots of the frame store and the pipeline bootstraps itself from them (Pipeline.bootstrap_lanes with the
+    one lane, vo_pipeline_bootstrap_lanes): same kernels, same result, no array brought back in between.
     Frames are uploaded as the sequence delivers them, grey or B, G, R; the pipeline's ingest makes them grey on the device.
     A camera with distortion_coeffs sets the lane's distortion (Pipeline.set_distortion: every frame is undistorted into
     the pinhole camera K behind its upload); one that really distorts needs bootstrap="device".
     tracks: the pipeline keeps persistent track ids (Pipeline(track_ids=True)) and the result gains `observations`, one
     TrackRecord per step (id, born, keypoint, state, candidate, landmark of every feature; track_table() turns them into
-    per-track observations) -- each posted behind its step and read back one collect later, so the look-ahead stays."""
-    from vo import _native
-    _check_bootstrap_route(bootstrap)
-    ctx = context or _native.default_context()
-    K = np.asarray(sequence.get_camera().intrinsic_matrix, np.float64)
-    dist = _lens_of(sequence, bootstrap)
-    SLOTS = 4
-    if bootstrap == "device":
-        img0, img = _bootstrap_images(sequence)          # (as delivered: the pipeline's ingest makes them grey, undistorted)
-        H, W = img.shape[:2]
-        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, track_ids=tracks,
-                                **_pipeline_kwargs(None, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector))
-        if dist is not None:
-            pipe.set_distortion(0, dist)
-        pipe.set_frame(1, img0)                          # (slot 1 takes frame 3 next: the bootstrap is done with it by then)
-        pipe.set_frame(0, img)
-        boot = pipe.bootstrap(1, 0, **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
-                                                        bootstrap_max_level, bootstrap_threshold))
-        trajectory = [np.eye(4), pipe.get_state()["curr_pose"]]
-        n_landmarks = [boot.n_landmarks]
-    else:
-        state, tracker = _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level,
-                                           bootstrap_threshold)
-        frame = state.curr_frame
-        img = _gray(frame.image)
-        H, W = img.shape
-        pipe = _native.Pipeline(ctx, H, W, SLOTS, K, track_ids=tracks,
-                                **_pipeline_kwargs(state, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector))
-        pipe.set_frame(0, img)
-        pipe.set_state(0, frame.features, state.curr_pose, state.prev_pose, num_features=tracker._tracker._num_features)
-        trajectory = [np.eye(4), state.get_pose()]
-        n_landmarks = [len(frame.features.triangulated_inliers_landmarks)]
-    seconds, results, observations = [], [], []
-    tap = _TrackTap(ctx, pipe) if tracks else None
+    per-track observations) -- each posted behind its step and read back one collect later, so the look-ahead stays.
 
-    def collect():
-        results.append(pipe.collect())
-        if tap:
-            tap.post([(0, results[-1], observations)])
-    # Frames go through a ring of pinned buffers AS DELIVERED (three channels where the sequence gives three: the grey
-    # conversion and the undistortion run on the device behind the DMA, csrc/ingest.hip) and are uploaded on the
-    # pipeline's upload stream ONE STEP AHEAD of their use (vo_pipeline_set_frame_pinned / _bgr_pinned): while step
-    # k -> k+1 runs, frame k+2 -- read ahead from the sequence, as a file or dataset reader can -- crosses PCIe beside it.
-    # One frame of look-ahead on the results as before: the pose of frame k is read back after frame k+1 has been submitted.
-    ring = [None] * SLOTS
-    frames = iter(sequence)
-    taken = 0
-
-    def take():
-        nonlocal taken
-        if max_frames is not None and taken >= max_frames:
-            return None
-        f = next(frames, None)
-        if f is not None:
-            taken += 1
-        return f
-
-    def put(s, f):
-        _into_ring(ctx, ring, s, f.image)
-        pipe.set_frame(s, ring[s], pinned=True)
-
-    slot, pending = 0, 0
-    ahead = take()
-    if ahead is not None:
-        put(1, ahead)
-    while ahead is not None:
-        t0 = time.perf_counter()
-        nxt = (slot + 1) % SLOTS
-        if pending == 2:
-            collect()
-            pending -= 1
-        t1 = time.perf_counter()
-        ahead = take()                                   # the frame of the NEXT step: its slot was read last by a collected step
-        t2 = time.perf_counter()                         # (reading / decoding / rendering the frame is the sequence's time, not the loop's)
-        if ahead is not None:
-            put((slot + 2) % SLOTS, ahead)
-        pipe.submit(slot, nxt)
-        if ahead is not None:
-            pipe.prepare((slot + 2) % SLOTS)            # its pyramid too, behind this step's tracker
-        pending += 1
-        slot = nxt
-        seconds.append(time.perf_counter() - t0 - (t2 - t1))
-    while pending:
-        collect()
-        pending -= 1
-    if tap:
-        tap.close()
-    for r in results:
-        trajectory.append(r.pose_world_cam())
-        n_landmarks.append(r.n_landmarks)
-        if verbose:
+    This is run_batch_on_device([sequence], lanes=1, ...)[0], the same loop (_DeviceRun) with one lane, and what comes
+    with that: the lane's camera is set once more at the start (Pipeline.set_camera with the constructor's K, so the
+    same values); steps are collected with collect_all (one record); the number of steps is the recording's length
+    (`len(sequence)`, `increment`) capped by max_frames, and the frame size comes from _frame_shape; a recording with no
+    frame after its bootstrap gets the host bootstrap and no pipeline, and its `features` are the bootstrap's own.
+    frame_seconds differs from the batch driver's: it leaves out the time the sequence takes to deliver a frame
+    (reading / decoding / rendering inside next() is the sequence's time, not the loop's)."""
+    run = _DeviceRun([sequence], 1, max_frames, context, bootstrap, tracks,
+                     (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
+                     (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector))
+    out = run.run()[0]
+    out["frame_seconds"] = out["frame_seconds"] - np.array(run.read_seconds)
+    if tracks:
+        out.setdefault("observations", [])
+    if verbose:
+        for r in out["results"]:
             print("%4d in, %4d tracked, %4d landmarks, %4d inliers, %3d candidates%s" % (
                 r.n_features_in, r.n_tracked, r.n_landmarks, r.n_inliers, r.n_candidates,
                 ", re-detected" if r.redetected else ""))
-    features = pipe.get_features()
-    pipe.close()
-    out = dict(trajectory=np.array(trajectory), n_landmarks=np.array(n_landmarks), frame_seconds=np.array(seconds),
-               results=results, features=features)
-    if tracks:
-        out["observations"] = observations
     return out
 
 
@@ -432,6 +353,207 @@ def _frame_shape(sequence):
     return tuple(_gray(sequence.get_frame(0).image).shape[:2])
 
 
+class _DeviceRun:
+    """The device-resident frame loop of run_batch_on_device, and of run_on_device as its one-lane case.
+
+    Frames go through one ring of pinned buffers per lane AS DELIVERED (three channels where the sequence gives three: the
+    grey conversion and the undistortion run on the device behind the DMA, csrc/ingest.hip) and are uploaded on the
+    pipeline's upload stream ONE STEP AHEAD of their use (vo_pipeline_set_frame_pinned / _bgr_pinned): while step
+    k -> k+1 runs, frame k+2 -- read ahead from the sequence, as a file or dataset reader can -- crosses PCIe beside it.
+    One step of look-ahead on the results too: the record of step k is read back after step k+1 has been submitted.
+
+    boot_args: _device_bootstrap's / _bootstrap_kwargs' arguments, pipe_args: _pipeline_kwargs' after the state."""
+    SLOTS = 4
+
+    def __init__(self, sequences, lanes, max_frames, context, bootstrap, tracks, boot_args, pipe_args):
+        _check_bootstrap_route(bootstrap)
+        self.sequences = sequences = list(sequences)
+        self.on_device, self.context, self.tracks = bootstrap == "device", context, tracks
+        self.boot_args, self.pipe_args = boot_args, pipe_args
+        self.shapes = [_frame_shape(s) for s in sequences]
+        if len(set(self.shapes)) > 1:
+            raise ValueError("run_batch_on_device: the recordings' frame sizes differ (%s); one pipeline takes one H x W"
+                             % sorted(set(self.shapes)))
+        self.lens = [_lens_of(s, bootstrap) for s in sequences]
+        self.lengths = [_steady_frames(s) for s in sequences]
+        if max_frames is not None:
+            self.lengths = [min(n, int(max_frames)) for n in self.lengths]
+        self.lanes = int(lanes) if lanes else max(1, min(len(sequences), 16))
+        plan = lane_schedule(self.lengths, self.lanes)
+        self.steps = plan["steps"]
+        self.first = plan["starts"][0][2] if self.steps else None       # (lane 0's recording at step 0)
+        self.events = {}                                 # step -> (lane, the recording it starts, or None: it goes idle)
+        for t, lane, r in plan["starts"]:
+            self.events.setdefault(t, []).append((lane, r))
+        for t, lane in plan["idles"]:
+            self.events.setdefault(t, []).append((lane, None))
+        self.boot = {}                                   # recording -> its host bootstrap (state, tracker)
+        self.out = [None] * len(sequences)
+        self.ctx = self.pipe = self.tap = self.ring = None
+        self.pending, self.slot = [], 0                  # steps submitted and not collected; the `prev` of the next submit
+        # per step of the RUN, all lanes together: the part of its wall time spent inside next(sequence).  Only run_on_device
+        # reads it: with one recording on one lane the run's steps are the recording's, entry for entry of frame_seconds
+        self.reading, self.read_seconds = 0.0, []
+
+    def boot_of(self, r):
+        if r not in self.boot:
+            self.boot[r] = _device_bootstrap(self.sequences[r], *self.boot_args)
+        return self.boot[r]
+
+    def open_result(self, r):
+        state, tracker = self.boot_of(r)
+        self.out[r] = dict(trajectory=[np.eye(4), state.get_pose()],
+                           n_landmarks=[len(state.curr_frame.features.triangulated_inliers_landmarks)], frame_seconds=[],
+                           results=[], features=state.curr_frame.features)
+
+    def camera_of(self, r):
+        return np.asarray(self.sequences[r].get_camera().intrinsic_matrix, np.float64)
+
+    def open_pipeline(self):
+        from vo import _native
+        self.ctx = self.context or _native.default_context()
+        state0 = None if self.on_device else self.boot_of(self.first)[0]
+        H, W = self.shapes[self.first]
+        self.pipe = _native.Pipeline(self.ctx, H, W, self.SLOTS, self.camera_of(self.first), sequences=self.lanes,
+                                     track_ids=self.tracks, **_pipeline_kwargs(state0, *self.pipe_args))
+        self.tap = _TrackTap(self.ctx, self.pipe, self.lanes) if self.tracks else None
+        self.ring = [[None] * self.SLOTS for _ in range(self.lanes)]
+
+    def set_camera(self, lane, r):
+        self.pipe.set_camera(self.camera_of(r), lane)
+        # (the lens at every start: a lane that held a distorting camera's recording must lose its coefficients with it)
+        if any(d is not None for d in self.lens):
+            self.pipe.set_distortion(lane, self.lens[r])
+
+    def put(self, lane, s, r):
+        """Recording r's next frame -> slot s of its lane, through the lane's pinned ring."""
+        t0 = time.perf_counter()
+        frame = next(self.sequences[r])
+        self.reading += time.perf_counter() - t0
+        _into_ring(self.ctx, self.ring[lane], s, frame.image)
+        self.pipe.set_frame(s, self.ring[lane][s], seq=lane, pinned=True)
+
+    def start(self, lane, r, t):
+        """Host route: the lane takes recording r from its host bootstrap (step 0: a hand-over, later: a restart)."""
+        state, tracker = self.boot_of(r)
+        self.open_result(r)
+        frame = state.curr_frame
+        self.set_camera(lane, r)
+        args = (frame.features, state.curr_pose, state.prev_pose)
+        nf = tracker._tracker._num_features
+        if t == 0:
+            self.pipe.set_frame(self.slot, _gray(frame.image), seq=lane, pinned=False)
+            self.pipe.set_state(self.slot, *args, num_features=nf, seq=lane)
+        else:
+            self.pipe.restart(lane, self.slot, *args, num_features=nf, image=_gray(frame.image))
+
+    def start_on_device(self, starts, t):
+        """Device route: the lanes that start a recording at this step -- starts: (lane, recording) -- through ONE
+        bootstrap call, from frames 0 and 2 as delivered (the pipeline's ingest makes them grey, undistorted)."""
+        from vo import _native
+        a = (self.slot + 1) % self.SLOTS                 # (the slot the recordings' next frames take afterwards)
+        for lane, r in starts:
+            img0, img2 = _bootstrap_images(self.sequences[r])
+            self.set_camera(lane, r)
+            if t > 0:
+                self.pipe.set_active(lane, False)        # (the lane's frame in the current slot can only be replaced while idle)
+            self.pipe.set_frame(a, img0, seq=lane, pinned=False)
+            self.pipe.set_frame(self.slot, img2, seq=lane, pinned=False)
+        results = self.pipe.bootstrap_lanes(a, self.slot, [lane for lane, _ in starts],
+                                            **_bootstrap_kwargs(*self.boot_args))
+        for (lane, r), res in zip(starts, results):
+            if res.status != 0:
+                raise _native.VoError(res.status, "the bootstrap of recording %d (lane %d) failed" % (r, lane))
+            self.out[r] = dict(trajectory=[np.eye(4), self.pipe.get_state(lane)["curr_pose"]],
+                               n_landmarks=[res.n_landmarks], frame_seconds=[], results=[], features=None)
+
+    def finish(self, lane, r):
+        self.out[r]["features"] = self.pipe.get_features(lane)
+
+    def collect_one(self):
+        row = self.steps[self.pending.pop(0)]
+        rs = self.pipe.collect_all()
+        taken = [(lane, rs[lane], self.out[e[0]]) for lane, e in enumerate(row) if e is not None]
+        for lane, r, o in taken:
+            o["results"].append(r)                       # (run() reads the poses and counts out of them after the loop)
+        if self.tap:
+            self.tap.post([(lane, r, o.setdefault("observations", [])) for lane, r, o in taken])
+
+    def change(self, t):
+        """Step t's events -- lanes going idle, lanes starting a recording (the host route one by one, the device route
+        all of them in one call) -- with nothing in flight: drain, read what ends, then idle / start, and the first
+        frame after the bootstrap of every recording that starts goes into the slot after the current one."""
+        events = sorted(self.events[t])
+        if t > 0:
+            while self.pending:
+                self.collect_one()
+            if self.tap:
+                self.tap.flush()                         # (a hand-over rewrites the buffers the posted records read)
+            for lane, _ in events:
+                prev = self.steps[t - 1][lane]
+                if prev is not None:
+                    self.finish(lane, prev[0])
+        starts = [(lane, r) for lane, r in events if r is not None]
+        for lane, r in events:
+            if r is None:
+                self.pipe.set_active(lane, False)
+            elif not self.on_device:
+                self.start(lane, r, t)
+        if self.on_device and starts:
+            self.start_on_device(starts, t)
+        for lane, r in starts:
+            self.put(lane, (self.slot + 1) % self.SLOTS, r)
+
+    def step(self, t):
+        """Step t, slot -> slot + 1: the oldest of two pending steps is collected, the frames of step t + 1 (for lanes that
+        keep their recording) go into slot + 2 -- read last by a collected step --, the step is submitted, and the pyramid
+        of slot + 2 is hinted behind its tracker."""
+        if t in self.events:
+            self.change(t)
+        t0 = time.perf_counter()
+        self.reading = 0.0
+        nxt, after = (self.slot + 1) % self.SLOTS, (self.slot + 2) % self.SLOTS
+        if len(self.pending) == 2:
+            self.collect_one()
+        ahead = []                                       # (lane, recording) of the lanes that keep theirs at step t + 1
+        if t + 1 < len(self.steps):
+            ahead = [(lane, e[0]) for lane, e in enumerate(self.steps[t + 1]) if e is not None and e[1] > 0]
+        for lane, r in ahead:
+            self.put(lane, after, r)
+        self.pipe.submit(self.slot, nxt)
+        if ahead:
+            self.pipe.prepare(after)
+        self.pending.append(t)
+        self.slot = nxt
+        seconds = time.perf_counter() - t0
+        self.read_seconds.append(self.reading)
+        for e in self.steps[t]:
+            if e is not None:
+                self.out[e[0]]["frame_seconds"].append(seconds)
+
+    def run(self):
+        for r, n in enumerate(self.lengths):             # (recordings without a steady-state step: the bootstrap is all there is)
+            if n == 0:
+                self.open_result(r)
+        if self.steps:
+            self.open_pipeline()
+            for t in range(len(self.steps)):
+                self.step(t)
+            while self.pending:
+                self.collect_one()
+            for lane, e in enumerate(self.steps[-1]):
+                if e is not None:
+                    self.finish(lane, e[0])
+            if self.tap:
+                self.tap.close()
+            self.pipe.close()
+        for o in self.out:
+            o["trajectory"] = np.array(o["trajectory"] + [r.pose_world_cam() for r in o["results"]])
+            o["n_landmarks"] = np.array(o["n_landmarks"] + [r.n_landmarks for r in o["results"]])
+            o["frame_seconds"] = np.array(o["frame_seconds"])
+        return self.out
+
+
 def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_keypoints: int = 2000, klt_win: int = 17,
                         klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
@@ -439,7 +561,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                         tracks: bool = False):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
-    as run_on_device does it; when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
+    (_device_bootstrap); when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
     goes idle (vo_pipeline_set_active_seq) -- lane_schedule says when.  Frames go through one pinned ring per lane,
     uploaded a step ahead.  The steps in flight are drained before a lane changes recording (nothing may be in flight for
     the three calls), so each such step loses the look-ahead once.  All recordings must have the same frame size.
@@ -452,195 +574,13 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     start over with every recording: each start is a hand-over).
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
-    each step the recording took part in).  Each lane computes what run_on_device computes for its recording alone."""
-    from vo import _native
-    _check_bootstrap_route(bootstrap)
-    on_device = bootstrap == "device"
-    sequences = list(sequences)
-    if not sequences:
-        return []
-    shapes = [_frame_shape(s) for s in sequences]
-    if any(sh != shapes[0] for sh in shapes):
-        raise ValueError("run_batch_on_device: the recordings' frame sizes differ (%s); one pipeline takes one H x W"
-                         % sorted(set(shapes)))
-    H, W = shapes[0]
-    lengths = [_steady_frames(s) for s in sequences]
-    if max_frames is not None:
-        lengths = [min(n, int(max_frames)) for n in lengths]
-    lanes = int(lanes) if lanes else max(1, min(len(sequences), 16))
-    plan = lane_schedule(lengths, lanes)
-    steps = plan["steps"]
-    ctx = context or _native.default_context()
-    boot = {}
-
-    def boot_of(r):
-        if r not in boot:
-            boot[r] = _device_bootstrap(sequences[r], n_keypoints, klt_win, klt_max_level, bootstrap_win,
-                                        bootstrap_max_level, bootstrap_threshold)
-        return boot[r]
-
-    out = [None] * len(sequences)
-
-    def open_result(r):
-        state, tracker = boot_of(r)
-        out[r] = dict(trajectory=[np.eye(4), state.get_pose()],
-                      n_landmarks=[len(state.curr_frame.features.triangulated_inliers_landmarks)], frame_seconds=[],
-                      results=[], features=state.curr_frame.features)
-
-    for r in range(len(sequences)):            # (recordings without a steady-state step: the bootstrap is all there is)
-        if lengths[r] == 0:
-            open_result(r)
-    if steps:
-        first = next(r for (_, _, r) in plan["starts"])
-        state0 = None if on_device else boot_of(first)[0]
-        K0 = np.asarray(sequences[first].get_camera().intrinsic_matrix, np.float64)
-        SLOTS = 4
-        pipe = _native.Pipeline(ctx, H, W, SLOTS, K0, sequences=lanes, track_ids=tracks,
-                                **_pipeline_kwargs(state0, n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose,
-                                                   detector))
-        tap = _TrackTap(ctx, pipe, lanes) if tracks else None
-        ring = [[None] * SLOTS for _ in range(lanes)]      # (frames as delivered, see run_on_device)
-        lens = [_lens_of(s, bootstrap) for s in sequences]
-        any_lens = any(d is not None for d in lens)
-
-        def set_lens(lane, r):
-            # (every start: a lane that held a distorting camera's recording must lose its coefficients with it)
-            if any_lens:
-                pipe.set_distortion(lane, lens[r])
-        taken = [0] * len(sequences)
-
-        def next_frame(r):
-            taken[r] += 1
-            return next(sequences[r])
-
-        def put(lane, s, r):
-            _into_ring(ctx, ring[lane], s, next_frame(r).image)
-            pipe.set_frame(s, ring[lane][s], seq=lane, pinned=True)
-
-        def start_on_device(starts, t, slot):
-            """The lanes that start a recording at this step -- starts: (lane, recording) -- through ONE bootstrap call."""
-            a = (slot + 1) % SLOTS                       # (the slot the recordings' next frames take afterwards)
-            for lane, r in starts:
-                img0, img2 = _bootstrap_images(sequences[r])
-                pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
-                set_lens(lane, r)
-                if t > 0:
-                    pipe.set_active(lane, False)         # (the lane's frame in the current slot can only be replaced while idle)
-                pipe.set_frame(a, img0, seq=lane, pinned=False)
-                pipe.set_frame(slot, img2, seq=lane, pinned=False)
-            results = pipe.bootstrap_lanes(a, slot, [lane for lane, _ in starts],
-                                           **_bootstrap_kwargs(n_keypoints, klt_win, klt_max_level, bootstrap_win,
-                                                               bootstrap_max_level, bootstrap_threshold))
-            for (lane, r), res in zip(starts, results):
-                if res.status != 0:
-                    raise _native.VoError(res.status, "the bootstrap of recording %d (lane %d) failed" % (r, lane))
-                out[r] = dict(trajectory=[np.eye(4), pipe.get_state(lane)["curr_pose"]], n_landmarks=[res.n_landmarks],
-                              frame_seconds=[], results=[], features=None)
-
-        def start(lane, r, t, slot):
-            state, tracker = boot_of(r)
-            open_result(r)
-            frame = state.curr_frame
-            pipe.set_camera(np.asarray(sequences[r].get_camera().intrinsic_matrix, np.float64), lane)
-            set_lens(lane, r)
-            args = (frame.features, state.curr_pose, state.prev_pose)
-            nf = tracker._tracker._num_features
-            if t == 0:
-                pipe.set_frame(slot, _gray(frame.image), seq=lane, pinned=False)
-                pipe.set_state(slot, *args, num_features=nf, seq=lane)
-            else:
-                pipe.restart(lane, slot, *args, num_features=nf, image=_gray(frame.image))
-
-        def finish(lane, r):
-            out[r]["features"] = pipe.get_features(lane)
-
-        pending = []
-
-        def collect_one():
-            t = pending.pop(0)
-            rs = pipe.collect_all()
-            for lane, e in enumerate(steps[t]):
-                if e is not None:
-                    o = out[e[0]]
-                    o["results"].append(rs[lane])
-                    o["trajectory"].append(rs[lane].pose_world_cam())
-                    o["n_landmarks"].append(rs[lane].n_landmarks)
-            if tap:
-                tap.post([(lane, rs[lane], out[e[0]].setdefault("observations", []))
-                          for lane, e in enumerate(steps[t]) if e is not None])
-
-        events = {}
-        for t, lane, r in plan["starts"]:
-            events.setdefault(t, []).append((lane, r))
-        for t, lane in plan["idles"]:
-            events.setdefault(t, []).append((lane, None))
-        slot = 0
-
-        def change(t, slot):
-            """Step t's events: lanes going idle, lanes starting a recording (the host route one by one, the device route
-            all of them in one call)."""
-            starts = [(lane, r) for lane, r in sorted(events[t]) if r is not None]
-            for lane, r in sorted(events[t]):
-                if r is None:
-                    pipe.set_active(lane, False)
-                elif not on_device:
-                    start(lane, r, t, slot)
-            if on_device and starts:
-                start_on_device(starts, t, slot)
-            return starts
-
-        if 0 in events:
-            change(0, slot)
-            del events[0]
-        for lane, e in enumerate(steps[0]):
-            if e is not None:
-                put(lane, 1, e[0])
-        seconds = []
-        for t, row in enumerate(steps):
-            if t in events:
-                # a lane changes recording: drain, read what ends, then idle / restart (nothing in flight for either)
-                while pending:
-                    collect_one()
-                if tap:
-                    tap.flush()                          # (a hand-over rewrites the buffers the posted records read)
-                for lane, r in sorted(events[t]):
-                    prev = steps[t - 1][lane]
-                    if prev is not None:
-                        finish(lane, prev[0])
-                for lane, r in change(t, slot):
-                    put(lane, (slot + 1) % SLOTS, r)
-            t0 = time.perf_counter()
-            nxt = (slot + 1) % SLOTS
-            if len(pending) == 2:
-                collect_one()
-            ahead = False
-            if t + 1 < len(steps):                       # the frames of the NEXT step, for lanes that keep their recording
-                for lane, e in enumerate(steps[t + 1]):
-                    if e is not None and e[1] > 0:
-                        put(lane, (slot + 2) % SLOTS, e[0])
-                        ahead = True
-            pipe.submit(slot, nxt)
-            if ahead:
-                pipe.prepare((slot + 2) % SLOTS)
-            pending.append(t)
-            slot = nxt
-            seconds.append(time.perf_counter() - t0)
-            for e in row:
-                if e is not None:
-                    out[e[0]]["frame_seconds"].append(seconds[-1])
-        while pending:
-            collect_one()
-        for lane, e in enumerate(steps[-1]):
-            if e is not None:
-                finish(lane, e[0])
-        if tap:
-            tap.close()
-        pipe.close()
-    for o in out:
-        o["trajectory"] = np.array(o["trajectory"])
-        o["n_landmarks"] = np.array(o["n_landmarks"])
-        o["frame_seconds"] = np.array(o["frame_seconds"])
-        if verbose:
+    each step the recording took part in, the delivery of the next step's frames included).  run_on_device is this
+    function with one recording and one lane; each lane computes what it computes for the lane's recording alone."""
+    out = _DeviceRun(sequences, lanes, max_frames, context, bootstrap, tracks,
+                     (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
+                     (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector)).run()
+    if verbose:
+        for o in out:
             print("%d steps, %d landmarks at the end" % (len(o["results"]), o["n_landmarks"][-1]))
     return out
 
