@@ -271,10 +271,13 @@ int vo_match_last_path(vo_ctx* ctx);
 
 /* ---- Shi-Tomasi corners -----------------------------------------------------------
  * [ref: src/vo/features/klt.py:98]  cv2.goodFeaturesToTrack(img, mask, maxCorners,
- * qualityLevel, minDistance, blockSize).  xy: max_corners*2 float32 (or H*W/4*2 when
- * max_corners <= 0); n: corners found.  vo_min_eigen_map exposes the H*W float32 map.
- * All stages run on the device: eigenvalue map, thresholded 3x3 maxima, descending order
- * (value, then address) and the greedy minimum-distance walk over OpenCV's cell grid.     */
+ * qualityLevel, minDistance, blockSize).  xy: vo_good_features_capacity(H, W, max_corners)
+ * rows of 2 float32 -- max_corners, or (H*W+3)/4 + 64 when max_corners <= 0; n: corners
+ * found.  vo_min_eigen_map exposes the H*W float32 map.  All stages run on the device:
+ * eigenvalue map, thresholded 3x3 maxima, descending order (value, then address) and the
+ * greedy minimum-distance rule over OpenCV's cell grid, as parallel rounds over all
+ * candidates (one launch per round) or, where those cannot take the image, as one
+ * workgroup's walk: the stages of vo_good_features_batch_dev below for one image.         */
 int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_t* mask,
                      int max_corners, double quality, double min_dist, int block, float* xy,
                      int32_t* n);

@@ -201,6 +201,31 @@ def test_plateau_image_exceeds_the_candidate_capacity():
     assert take.sum() > cases.candidate_capacity(img.shape)
 
 
+def test_one_image_call_cases_are_what_they_claim():
+    """The images of the GPU tests of the one-image call (the sort the host sizes): nothing to sort, a candidate count that
+    is no multiple of a workgroup, a cell on either side of the cell lists' length, the sorted list's head."""
+    from scenarios import synthetic_image
+    img = synthetic_image(120, 160, 1, block=9)
+    n, quality, min_dist, block = cases.DEFAULTS
+    flat = cases.flat_image((96, 128))
+    assert cases.local_maxima(flat, None, quality, block).sum() == 0 and len(native.good_features(flat, None, *cases.DEFAULTS)) == 0
+    empty = np.zeros((120, 160), np.uint8)
+    assert cases.local_maxima(img, empty, cases.MASKED[1], cases.MASKED[3]).sum() == 0
+    assert len(native.good_features(img, empty, *cases.MASKED)) == 0
+    mid = synthetic_image(240, 320, 2, block=9)
+    assert cases.local_maxima(mid, None, quality, block).sum() == 1235 == 2 * 512 + 211
+    assert len(native.good_features(mid, None, *cases.DEFAULTS)) == 493
+    n, quality, min_dist, block = cases.CROWDED
+    small = synthetic_image(97, 131, 3, block=9)
+    assert cases.max_per_cell(cases.local_maxima(img, None, quality, block), min_dist) == 33 > cases.CELL_LIST
+    assert cases.max_per_cell(cases.local_maxima(small, None, quality, block), min_dist) == 29 <= cases.CELL_LIST
+    assert len(native.good_features(img, None, *cases.CROWDED)) == 9 and len(native.good_features(small, None, *cases.CROWDED)) == 8
+    assert len(native.good_features(img, None, 30, 0.01, 0, 7)) == 30 and len(native.good_features(img, None, 0, 0.01, 0, 7)) == 310
+    plateau = cases.plateau_image((96, 128))
+    assert cases.local_maxima(plateau, None, cases.PLATEAU[1], cases.PLATEAU[3]).sum() == 11318
+    assert cases.candidate_capacity((96, 128)) == 3136
+
+
 def test_bootstrap_frames_yield_eight_corners():
     """Frame a of every lane of the 4-lane bootstrap test: at least 8 corners, and four different scenes."""
     from test_gpu_pipeline_bootstrap import SMALL, boot_kwargs

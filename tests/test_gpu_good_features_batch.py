@@ -104,9 +104,13 @@ def test_five_images_equal_the_oracle_and_take_the_rounds_path(ctx):
 
 
 def test_batch_equals_the_one_image_call(ctx):
-    """2. the same batch through Context.good_features one by one."""
+    """2. the same batch through Context.good_features one by one; both are the oracle's (the one-image call runs the batched
+    stages, so it is no independent witness)."""
     imgs = cases.ordinary_images()
     one = [ctx.good_features(img, None, *cases.DEFAULTS) for img in imgs]
+    ref = oracle_each(imgs, None, *cases.DEFAULTS)
+    same_lists(one, ref, "one by one against the oracle")
+    same_lists(ctx.good_features_batch(imgs, None, *cases.DEFAULTS), ref, "the batch against the oracle")
     same_lists(ctx.good_features_batch(imgs, None, *cases.DEFAULTS), one)
     same_lists(ctx.good_features_batch(np.stack(imgs), None, *cases.DEFAULTS), one, "a 3-D array")
 
@@ -268,3 +272,54 @@ def test_an_image_beyond_the_candidate_capacity_fails_alone(ctx):
     assert e.value.code == ECAPACITY
     same_lists(ctx.good_features_batch([imgs[0], imgs[2]], None, *cases.PLATEAU),
                oracle_each([imgs[0], imgs[2]], None, *cases.PLATEAU), "after the failure")
+
+
+# ---- the one-image call: the batched stages at S = 1 behind a device-wide sort of exactly the candidates the host read
+# back, which no batched call reaches (the cases' counts are checked on the CPU in tests/test_good_features_batch_host.py) ----
+
+def test_one_image_call_with_nothing_to_sort(ctx):
+    """No candidate at all -- a flat image, an all-zero mask -- skips the sort: no corners, and the next call is the oracle's."""
+    from scenarios import synthetic_image
+    img = synthetic_image(120, 160, 1, block=9)
+    for got in (ctx.good_features(cases.flat_image((96, 128)), None, *cases.DEFAULTS),
+                ctx.good_features(img, np.zeros((120, 160), np.uint8), *cases.MASKED)):
+        assert got.shape == (0, 2) and got.dtype == np.float32
+    assert np.array_equal(ctx.good_features(img, None, *cases.DEFAULTS), native.good_features(img, None, *cases.DEFAULTS))
+
+
+def test_one_image_call_over_several_workgroups_with_a_remainder(ctx):
+    """1 235 candidates: three workgroups of 512 per round, the last with 211."""
+    from scenarios import synthetic_image
+    img = synthetic_image(240, 320, 2, block=9)
+    ref = native.good_features(img, None, *cases.DEFAULTS)
+    got = ctx.good_features(img, None, *cases.DEFAULTS)
+    assert got.dtype == np.float32 and got.shape == ref.shape == (493, 2)
+    assert np.array_equal(got, ref)
+
+
+@pytest.mark.parametrize("shape,seed,params", [
+    ((120, 160), 1, cases.CROWDED),          # 33 candidates in the fullest cell: prep hands the image to the walk
+    ((97, 131), 3, cases.CROWDED),           # 29: it stays on the rounds
+    ((120, 160), 1, (30, 0.01, 0, 7)),       # no minimum distance: the sorted list's head, cut at 30 ...
+    ((120, 160), 1, (0, 0.01, 0, 7)),        # ... and whole
+], ids=["walk", "rounds", "sorted-30", "sorted-all"])
+def test_one_image_call_takes_every_path(ctx, shape, seed, params):
+    from scenarios import synthetic_image
+    img = synthetic_image(shape[0], shape[1], seed, block=9)
+    ref = native.good_features(img, None, *params)
+    got = ctx.good_features(img, None, *params)
+    assert got.dtype == np.float32 and got.shape == ref.shape and len(ref) > 0
+    assert np.array_equal(got, ref)
+
+
+def test_one_image_call_beyond_the_candidate_capacity(ctx):
+    """The plateau image's 11 318 maxima against a capacity of 3 136: VO_ECAPACITY in the one-image call's words, and the
+    context works on."""
+    from scenarios import synthetic_image
+    from vo import _native
+    with pytest.raises(_native.VoError) as e:
+        ctx.good_features(cases.plateau_image((96, 128)), None, *cases.PLATEAU)
+    assert e.value.code == ECAPACITY
+    assert str(e.value).startswith("VO_ECAPACITY (-4): good_features: "), str(e.value)      # (code name, code, the library's text)
+    img = synthetic_image(96, 128, 31, block=9)
+    assert np.array_equal(ctx.good_features(img, None, *cases.PLATEAU), native.good_features(img, None, *cases.PLATEAU))

@@ -2,7 +2,7 @@
 otherwise, for S = 1, 4, 16 distinct synthetic frames, in one process, alternating:
   batch_dev  one vo_good_features_batch_dev call, frames and corners resident in device memory (nothing crosses PCIe)
   batch      one vo_good_features_batch call (frames up, corners down)
-  one_each   S vo_good_features calls (the one-image path: frames up, two count read-backs and the corners down, each)
+  one_each   S vo_good_features calls (frames up, one count read-back that sizes the sort, counts and corners down, each)
 Times are device events on the context's stream (a stream of torch's, handed to the context) around each case, read after
 a synchronise; per case --warmup untimed calls, then --repeats timed ones: median and spread.  batch against one_each is
 the like-for-like pair (both move the frames and the corners); batch_dev is what a device-resident caller pays.

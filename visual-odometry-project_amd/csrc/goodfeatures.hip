@@ -7,12 +7,14 @@
 // block x block structure tensor of 3x3 Sobel gradients (reflect-101 borders, exact
 // integer sums scaled once), quality threshold against the masked maximum, 3x3 local
 // maxima, descending order, greedy minimum-distance selection.
-// Everything on the device: eigenvalue map, maximum, thresholded local maxima -> candidate keys
-// (value | address), descending radix sort (rocPRIM), then the greedy minimum-distance rule itself,
-// walked by one workgroup in blocks of 512 candidates: a candidate is tested against the accepted
-// corners of earlier blocks through a cell grid (cell side = minDistance, as OpenCV keeps it) and
-// against the earlier candidates of its own block by the rule's own recursion -- accepted when every
-// earlier neighbour is rejected, rejected when one is accepted -- which settles in a few sweeps.
+// Everything on the device, as a fixed sequence of launches for S images of one size: eigenvalue map and masked maximum,
+// thresholded local maxima -> candidate keys (value | address), descending radix sort (rocPRIM), then the greedy
+// minimum-distance rule.  The rule's recursion -- a candidate is accepted when every earlier candidate within minDistance
+// is rejected, rejected when one of them is accepted -- is run over all candidates at once, one launch per round, through
+// a cell grid (cell side = minDistance, as OpenCV keeps it); an image the rounds cannot take is walked by one workgroup in
+// blocks of 512 candidates instead.  The one-image host call is the S = 1 case with one difference: it reads the
+// candidate count back and sorts exactly that many keys device-wide, where the batched forms sort capacity-sized segments
+// without a host turn (the stages and their callers are at the end of the file).
 #include <algorithm>
 #include <cmath>
 
@@ -43,7 +45,7 @@ __device__ __forceinline__ float key_float(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// (one 64 x 16 tile of one image: the body of min_eig_kernel and of min_eig_batch_kernel)
+// (one 64 x 16 tile of one image: the body of min_eig_batch_kernel)
 __device__ __forceinline__ void min_eig_tile(const uint8_t* __restrict__ img, int H, int W, int block, float s2,
                                              const uint8_t* __restrict__ mask, float* __restrict__ eig,
                                              unsigned* __restrict__ max_key) {
@@ -109,12 +111,6 @@ __device__ __forceinline__ void min_eig_tile(const uint8_t* __restrict__ img, in
   if (tid == 0 && s_max) atomicMax(max_key, s_max);
 }
 
-__global__ __launch_bounds__(GT) void min_eig_kernel(const uint8_t* __restrict__ img, int H, int W, int block,
-                                                     float s2, const uint8_t* __restrict__ mask,
-                                                     float* __restrict__ eig, unsigned* __restrict__ max_key) {
-  min_eig_tile(img, H, W, block, s2, mask, eig, max_key);
-}
-
 __device__ __forceinline__ void corner_candidates_tile(const float* __restrict__ eig, int H, int W,
                                                        const uint8_t* __restrict__ mask,
                                                        const unsigned* __restrict__ max_key, double quality,
@@ -174,17 +170,9 @@ __device__ __forceinline__ void corner_candidates_tile(const float* __restrict__
   }
 }
 
-__global__ __launch_bounds__(GT) void corner_candidates_kernel(const float* __restrict__ eig, int H, int W,
-                                                               const uint8_t* __restrict__ mask,
-                                                               const unsigned* __restrict__ max_key, double quality,
-                                                               unsigned long long* __restrict__ keys,
-                                                               unsigned* __restrict__ count, unsigned cap) {
-  corner_candidates_tile(eig, H, W, mask, max_key, quality, keys, count, cap);
-}
-
 // The greedy rule over the sorted candidates, one workgroup.  Cell grid in global memory: per cell a count and up to
 // GRID_SLOTS accepted corners (x | y << 16); accepted corners are >= minDistance apart, so a cell of that side holds
-// at most four -- more than GRID_SLOTS raises `fault` and the caller falls back to nothing (an error).
+// at most four -- more than GRID_SLOTS raises the fault word and the image fails (VO_ECAPACITY in the host forms).
 constexpr int GF_T = 512, GF_NB = 24, GRID_SLOTS = 8;
 enum { GF_UNDECIDED = 0, GF_ACCEPTED = 1, GF_REJECTED = 2 };
 
@@ -310,186 +298,18 @@ __device__ __forceinline__ void greedy_distance_walk(const unsigned long long* _
   if (t == 0) ctl[2] = (unsigned)n_acc;
 }
 
-__global__ __launch_bounds__(GF_T) void greedy_distance_kernel(const unsigned long long* __restrict__ keys, unsigned nc,
-                                                               int W, int cell, int gw, int gh, double md2, int max_corners,
-                                                               unsigned* __restrict__ cell_cnt,
-                                                               unsigned* __restrict__ cell_pts, float* __restrict__ xy,
-                                                               unsigned* __restrict__ ctl /* [2] n_out, [3] fault */) {
-  greedy_distance_walk(keys, nc, W, cell, gw, gh, md2, max_corners, cell_cnt, cell_pts, xy, ctl);
-}
-
-// The same rule over all candidates at once, by up to GC_WG workgroups of one launch: a candidate is accepted as soon as
-// every earlier (higher-priority) candidate within minDistance is rejected, rejected as soon as one of them is accepted --
-// the sequential walk decides exactly that, and decisions never change, so a candidate may read any mix of its
-// neighbours' old and new states.  Rounds are separated by a barrier over the launch (all workgroups are resident: at most
-// one per CU); the walk above takes 40 blocks of 14 us for the 20-30 thousand candidates of a 1376x1241 frame, this
-// ~15 rounds of a few microseconds.
-//   prep   every candidate enters the cell grid (cell side = minDistance, as in the walk)
-//   lists  its earlier candidates within minDistance in the 3x3 cells around it (up to GC_NB; more: the cells are
-//          walked again in every round)
-//   rounds until no candidate is undecided
-//   ranks  accepted candidates in priority order; the first max_corners are the corners
-// A cell with more than GC_CCAP candidates, or more candidates than GC_WG workgroups hold, raises ctl[3]: the caller
-// runs the one-workgroup walk instead.
+// The same rule over all candidates at once (the gfb_* kernels below): a candidate is accepted as soon as every earlier
+// (higher-priority) candidate within minDistance is rejected, rejected as soon as one of them is accepted -- the
+// sequential walk decides exactly that, and decisions never change, so a candidate may read any mix of its neighbours'
+// old and new states.  The walk above takes 40 blocks of 14 us for the 20-30 thousand candidates of a 1376x1241 frame,
+// this ~15 rounds of a few microseconds.  GC_T work items per workgroup and at most GC_WG workgroups per image (more
+// candidates: the walk), GC_NB listed neighbours per candidate, GC_CCAP candidates per cell (more: the walk).
 constexpr int GC_T = 512, GC_WG = 256, GC_NB = 24, GC_CCAP = 32;
-enum { GC_BAR = 4, GC_OPEN = 5 /* .. 8 */, GC_WGCNT = 16 /* .. 16 + GC_WG */, GC_WORDS = 16 + GC_WG };
 
-// (a wait is bounded: a workgroup that has not been joined within ~0.2 s of device clock -- workgroups that are not all
-//  resident, which the launch's size rules out -- raises *fault and goes on; every workgroup of the launch then runs out of
-//  its waits the same way, and the caller, seeing the flag, runs the one-workgroup walk)
-__device__ __forceinline__ void grid_barrier(unsigned* counter, unsigned& target, unsigned n_wg, unsigned* fault) {
-  __syncthreads();
-  target += n_wg;
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long t0 = wall_clock64();
-    while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(2);
-      if (wall_clock64() - t0 > 20000000ull) {
-        atomicOr(fault, 8u);
-        break;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(GC_T) void greedy_distance_rounds_kernel(const unsigned long long* __restrict__ keys, unsigned nc,
-                                                                      int W, int cell, int gw, int gh, double md2,
-                                                                      int max_corners, unsigned* __restrict__ cell_cnt,
-                                                                      unsigned* __restrict__ cell_items,
-                                                                      unsigned* __restrict__ state,
-                                                                      unsigned* __restrict__ nb, float* __restrict__ xy,
-                                                                      unsigned* __restrict__ ctl) {
-  __shared__ unsigned s_open, s_red[GC_T / 64], s_base;
-  const int t = threadIdx.x;
-  const unsigned n_wg = gridDim.x, k = blockIdx.x * GC_T + t;
-  unsigned target = 0;
-  const bool valid = k < nc;
-  int x = 0, y = 0;
-  if (valid) {
-    const unsigned id = (unsigned)(keys[k] & 0xffffffffull);
-    y = (int)(id / (unsigned)W);
-    x = (int)(id - (unsigned)y * (unsigned)W);
-    const unsigned c = (unsigned)(y / cell) * gw + (x / cell);
-    const unsigned slot = atomicAdd(&cell_cnt[c], 1u);
-    if (slot < (unsigned)GC_CCAP) cell_items[c * GC_CCAP + slot] = k;
-    else atomicOr(&ctl[3], 2u);
-    state[k] = GF_UNDECIDED;
-  }
-  grid_barrier(ctl + GC_BAR, target, n_wg, ctl + 3);
-  if (__hip_atomic_load(&ctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;   // (uniform: read behind the barrier)
-  // earlier candidates within minDistance
-  const int cx = x / cell, cy = y / cell;
-  auto walk = [&](auto&& visit) {
-    for (int yy = max(0, cy - 1); yy <= min(gh - 1, cy + 1); ++yy)
-      for (int xx = max(0, cx - 1); xx <= min(gw - 1, cx + 1); ++xx) {
-        const unsigned c = (unsigned)yy * gw + xx;
-        const unsigned m = min(cell_cnt[c], (unsigned)GC_CCAP);
-        for (unsigned j = 0; j < m; ++j) {
-          const unsigned q = cell_items[c * GC_CCAP + j];
-          if (q >= k) continue;
-          const unsigned idq = (unsigned)(keys[q] & 0xffffffffull);
-          const int qy = (int)(idq / (unsigned)W), qx = (int)(idq - (unsigned)qy * (unsigned)W);
-          const double dx = x - qx, dy = y - qy;
-          if (dx * dx + dy * dy < md2) visit(q);
-        }
-      }
-  };
-  int nnb = 0;
-  if (valid) walk([&](unsigned q) {
-    if (nnb < GC_NB) nb[(size_t)k * GC_NB + nnb] = q;
-    ++nnb;
-  });
-  unsigned st = valid ? (unsigned)GF_UNDECIDED : (unsigned)GF_REJECTED;
-  for (unsigned round = 0;; ++round) {
-    if (t == 0) s_open = 0;
-    __syncthreads();
-    if (st == GF_UNDECIDED) {
-      bool any_acc = false, any_und = false;
-      auto look = [&](unsigned q) {
-        const unsigned sq = __hip_atomic_load(&state[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        any_acc |= sq == GF_ACCEPTED;
-        any_und |= sq == GF_UNDECIDED;
-      };
-      if (nnb <= GC_NB) {
-        for (int j = 0; j < nnb; ++j) look(nb[(size_t)k * GC_NB + j]);
-      } else {
-        walk(look);
-      }
-      if (any_acc) st = GF_REJECTED;
-      else if (!any_und) st = GF_ACCEPTED;
-      if (st != GF_UNDECIDED) __hip_atomic_store(&state[k], st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else s_open = 1;
-    }
-    __syncthreads();
-    unsigned* open = ctl + GC_OPEN + (round & 3u);
-    if (t == 0) {
-      if (s_open) __hip_atomic_store(open, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (blockIdx.x == 0)       // the word of two rounds on: its readers all passed the previous barrier
-        __hip_atomic_store(ctl + GC_OPEN + ((round + 2u) & 3u), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    grid_barrier(ctl + GC_BAR, target, n_wg, ctl + 3);
-    if (__hip_atomic_load(&ctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;   // (a barrier gave up)
-    if (__hip_atomic_load(open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) break;   // (uniform over the launch)
-    if (round > nc) {            // (every round decides the first undecided candidate: never reached)
-      if (t == 0) atomicOr(&ctl[3], 4u);
-      return;
-    }
-  }
-  // ranks: accepted candidates before this one = those of the earlier workgroups + those before it here
-  const unsigned acc = st == GF_ACCEPTED ? 1u : 0u;
-  const unsigned long long bal = __ballot(acc != 0u);
-  const int lane = t & 63, wv = t >> 6;
-  if (lane == 0) s_red[wv] = (unsigned)__popcll(bal);
-  __syncthreads();
-  unsigned before = (unsigned)__popcll(bal & ((1ull << lane) - 1ull)), mine = 0;
-  for (int w = 0; w < GC_T / 64; ++w) {
-    if (w < wv) before += s_red[w];
-    mine += s_red[w];
-  }
-  if (t == 0) __hip_atomic_store(ctl + GC_WGCNT + blockIdx.x, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  grid_barrier(ctl + GC_BAR, target, n_wg, ctl + 3);
-  unsigned part = 0;
-  for (unsigned w = t; w < blockIdx.x; w += GC_T) part += __hip_atomic_load(ctl + GC_WGCNT + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
-  __syncthreads();
-  if (lane == 0) s_red[wv] = part;
-  __syncthreads();
-  if (t == 0) {
-    unsigned b = 0;
-    for (int w = 0; w < GC_T / 64; ++w) b += s_red[w];
-    s_base = b;
-  }
-  __syncthreads();
-  const unsigned limit = max_corners > 0 ? (unsigned)max_corners : 0xffffffffu;
-  const unsigned rank = s_base + before;
-  if (acc && rank < limit) {
-    xy[2 * rank] = (float)x;
-    xy[2 * rank + 1] = (float)y;
-  }
-  if (blockIdx.x == n_wg - 1 && t == 0) ctl[2] = min(s_base + mine, limit);
-}
-
-// minDistance < 1: the first max_corners of the sorted list
-__global__ __launch_bounds__(256) void take_sorted_kernel(const unsigned long long* __restrict__ keys, unsigned n, int W,
-                                                          float* __restrict__ xy) {
-  const unsigned k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= n) return;
-  const unsigned id = (unsigned)(keys[k] & 0xffffffffull);
-  xy[2 * k] = (float)(id % (unsigned)W);
-  xy[2 * k + 1] = (float)(id / (unsigned)W);
-}
-
-
-// ---- S images per set of launches (vo_good_features_batch_dev) ----------------------------------------------------------
-// The same stages with the image as a grid dimension and every count left on the device; the rounds of the
-// minimum-distance rule are launches, not spins behind a launch-wide barrier, so nothing here depends on which
-// workgroups are resident.  Per image a control block of GB_CTL words (256 bytes: the images' counters never share a
-// cache line):
+// ---- S images per set of launches -----------------------------------------------------------------------------------------
+// Every stage has the image as a grid dimension and leaves its counts on the device; the rounds of the minimum-distance
+// rule are launches, so no workgroup ever waits for another and nothing depends on which workgroups are resident.  Per
+// image a control block of GB_CTL words (256 bytes: the images' counters never share a cache line):
 //   [GB_MAX] masked maximum (key)   [GB_NC] candidates sorted   [GB_N] corners   [GB_FAULT] bit 0: GRID_SLOTS overflowed
 //   in the walk, bit 8: more local maxima than the candidate capacity   [GB_PATH] 0 rounds, 1 walk, 2 take-sorted
 //   [GB_ROUNDS] round launches that still found the image open   [GB_WALK] the rounds path hands the image to the walk
@@ -765,317 +585,193 @@ __global__ __launch_bounds__(GC_T) void gfb_emit_kernel(const unsigned long long
 // no partitioning of the segments by length: that step reads its counts back on the host
 typedef rocprim::segmented_radix_sort_config<8, rocprim::kernel_config<256, 16>> gfb_sort_config;
 
-}  // namespace
-
-extern "C" {
-
-int vo_min_eigen_map(vo_ctx* ctx, const uint8_t* img, int H, int W, int block, float* eig) {
-  if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, img && eig && H > 0 && W > 0, "min_eigen_map: bad arguments");
-  VO_REQUIRE(ctx, block >= 1 && block <= 31, "min_eigen_map: blockSize must be in 1..31");
-  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t px = (size_t)H * W;
-  hipStream_t st = ctx->stream;
-  vo_buf* s = ctx->scratch;
-  VO_TRY(vo_ensure(ctx, ctx->img, px));
-  VO_TRY(vo_ensure(ctx, s[0], px * 4));
-  VO_TRY(vo_ensure(ctx, s[1], 16));
-  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, img, px, hipMemcpyHostToDevice, st));
-  VO_HIP_TRY(ctx, hipMemsetAsync(s[1].p, 0, 16, st));
-  const double scale = 1.0 / (4.0 * block * 255.0);
-  const int RW = GX + block - 1, RH = GY + block - 1;
-  const size_t lds = ((size_t)RW * RH + (size_t)3 * RH * GX) * 4;
-  hipLaunchKernelGGL(min_eig_kernel, dim3(vo_cdiv(W, GX), vo_cdiv(H, GY)), dim3(GT), lds, st, (const uint8_t*)ctx->img.p,
-                     H, W, block, (float)(scale * scale), (const uint8_t*)nullptr, (float*)s[0].p, (unsigned*)s[1].p);
-  VO_TRY(vo_check_launch(ctx, "min_eig_kernel"));
-  VO_HIP_TRY(ctx, hipMemcpyAsync(eig, s[0].p, px * 4, hipMemcpyDeviceToHost, st));
-  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
-  return VO_OK;
-}
-
-}  // extern "C"
-
-// The device-resident form (vo_internal.h): image and mask are in HBM already, the corners stay there (*d_xy_out points
-// into the context's workspace and holds until the context's next call).  Only the counts the launches are sized by come
-// back to the host (vo_ctx::bytes_d2h).
-int vo_good_features_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const uint8_t* d_mask, int max_corners,
-                         double quality, double min_dist, int block, const float** d_xy_out, int32_t* n_out) {
-  if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, d_img && d_xy_out && n_out && H > 0 && W > 0, "good_features: bad arguments");
-  VO_REQUIRE(ctx, block >= 1 && block <= 31, "good_features: blockSize must be in 1..31");
-  VO_REQUIRE(ctx, quality > 0 && min_dist >= 0, "good_features: bad quality / minDistance");
-  *n_out = 0;
-  *d_xy_out = nullptr;
-  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t px = (size_t)H * W;
-  hipStream_t st = ctx->stream;
-  vo_buf* s = ctx->scratch;
-  const unsigned cap = (unsigned)((px + 3) / 4 + 64);             // 3x3 maxima: at most one per 2x2 block
-  VO_REQUIRE(ctx, W < 65536 && H < 65536, "good_features: image side must be below 65536");
-  const int cell = std::max(1, (int)std::lround(min_dist));
-  const int gw = (W + cell - 1) / cell, gh = (H + cell - 1) / cell;
-  const size_t cells = (size_t)gw * gh;
-  const size_t out_cap = max_corners > 0 ? (size_t)max_corners : (size_t)cap;
-  size_t sort_tmp = 0;
-  VO_HIP_TRY(ctx, rocprim::radix_sort_keys_desc(nullptr, sort_tmp, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                (size_t)cap, 0, 64, st));
-  VO_TRY(vo_ensure(ctx, s[0], px * 4));
-  VO_TRY(vo_ensure(ctx, s[1], (size_t)GC_WORDS * 4));
-  VO_TRY(vo_ensure(ctx, s[2], (size_t)cap * 8));
-  VO_TRY(vo_ensure(ctx, s[3], (size_t)cap * 8));
-  VO_TRY(vo_ensure(ctx, s[4], sort_tmp + 256));
-  VO_TRY(vo_ensure(ctx, s[5], cells * 4));
-  VO_TRY(vo_ensure(ctx, s[6], cells * GRID_SLOTS * 4));
-  VO_TRY(vo_ensure(ctx, s[7], out_cap * 8));
-  VO_HIP_TRY(ctx, hipMemsetAsync(s[1].p, 0, (size_t)GC_WORDS * 4, st));
-  VO_HIP_TRY(ctx, hipMemsetAsync(s[5].p, 0, cells * 4, st));
-  unsigned* d_ctl = (unsigned*)s[1].p;                            // [0] max key, [1] candidate count, [2] corners, [3] fault
-  const double scale = 1.0 / (4.0 * block * 255.0);
-  const int RW = GX + block - 1, RH = GY + block - 1;
-  const size_t lds = ((size_t)RW * RH + (size_t)3 * RH * GX) * 4;
-  hipLaunchKernelGGL(min_eig_kernel, dim3(vo_cdiv(W, GX), vo_cdiv(H, GY)), dim3(GT), lds, st, d_img,
-                     H, W, block, (float)(scale * scale), d_mask, (float*)s[0].p, d_ctl);
-  VO_TRY(vo_check_launch(ctx, "min_eig_kernel"));
-  hipLaunchKernelGGL(corner_candidates_kernel, dim3(vo_cdiv(W, GX), vo_cdiv(H, GY)), dim3(GT), 0, st,
-                     (const float*)s[0].p, H, W, d_mask, d_ctl, quality, (unsigned long long*)s[2].p, d_ctl + 1, cap);
-  VO_TRY(vo_check_launch(ctx, "corner_candidates_kernel"));
-  unsigned ctl[4] = {0, 0, 0, 0};
-  VO_HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 8, hipMemcpyDeviceToHost, st));
-  VO_HIP_TRY(ctx, hipStreamSynchronize(st));                      // (the sort is sized by the candidate count)
-  ctx->bytes_d2h += 8;
-  if (ctl[1] > cap)      // (ties count as maxima: plateaus can exceed one maximum per 2x2 block)
-    return vo_set_error(ctx, VO_ECAPACITY, "good_features: %u local maxima exceed the candidate capacity %u", ctl[1], cap);
-  const unsigned nc = ctl[1];
-  if (nc == 0) return VO_OK;
-  unsigned long long* d_sorted = (unsigned long long*)s[3].p;
-  VO_HIP_TRY(ctx, rocprim::radix_sort_keys_desc(s[4].p, sort_tmp, (unsigned long long*)s[2].p, d_sorted, (size_t)nc, 0, 64, st));
-  float* d_xy = (float*)s[7].p;
-  int n = 0;
-  if (min_dist >= 1) {
-    const unsigned n_wg = (nc + GC_T - 1) / GC_T;
-    bool done = false;
-    if (n_wg <= (unsigned)GC_WG) {
-      VO_TRY(vo_ensure(ctx, s[8], cells * GC_CCAP * 4));
-      VO_TRY(vo_ensure(ctx, s[9], (size_t)nc * 4));
-      VO_TRY(vo_ensure(ctx, s[10], (size_t)nc * GC_NB * 4));
-      hipLaunchKernelGGL(greedy_distance_rounds_kernel, dim3(n_wg), dim3(GC_T), 0, st, d_sorted, nc, W, cell, gw, gh,
-                         min_dist * min_dist, max_corners, (unsigned*)s[5].p, (unsigned*)s[8].p, (unsigned*)s[9].p,
-                         (unsigned*)s[10].p, d_xy, d_ctl);
-      VO_TRY(vo_check_launch(ctx, "greedy_distance_rounds_kernel"));
-      VO_HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, st));
-      VO_HIP_TRY(ctx, hipStreamSynchronize(st));
-      ctx->bytes_d2h += 16;
-      done = ctl[3] == 0;
-      if (!done) {                     // a crowded cell: the walk decides (its grid holds accepted corners only)
-        VO_HIP_TRY(ctx, hipMemsetAsync(s[5].p, 0, cells * 4, st));
-        VO_HIP_TRY(ctx, hipMemsetAsync(d_ctl + 2, 0, 8, st));
-      }
-    }
-    if (!done) {
-      hipLaunchKernelGGL(greedy_distance_kernel, dim3(1), dim3(GF_T), 0, st, d_sorted, nc, W, cell, gw, gh,
-                         min_dist * min_dist, max_corners, (unsigned*)s[5].p, (unsigned*)s[6].p, d_xy, d_ctl);
-      VO_TRY(vo_check_launch(ctx, "greedy_distance_kernel"));
-      VO_HIP_TRY(ctx, hipMemcpyAsync(ctl, d_ctl, 16, hipMemcpyDeviceToHost, st));
-      VO_HIP_TRY(ctx, hipStreamSynchronize(st));
-      ctx->bytes_d2h += 16;
-      if (ctl[3]) return vo_set_error(ctx, VO_ECAPACITY, "good_features: more than %d corners in one grid cell", GRID_SLOTS);
-    }
-    n = (int)ctl[2];
-  } else {
-    n = (int)(max_corners > 0 ? std::min<unsigned>(nc, (unsigned)max_corners) : nc);
-    hipLaunchKernelGGL(take_sorted_kernel, dim3(vo_cdiv(n, 256)), dim3(256), 0, st, d_sorted, (unsigned)n, W, d_xy);
-    VO_TRY(vo_check_launch(ctx, "take_sorted_kernel"));
-  }
-  *d_xy_out = d_xy;
-  *n_out = n;
-  return VO_OK;
-}
-
-extern "C" {
-
-int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_t* mask, int max_corners,
-                     double quality, double min_dist, int block, float* xy, int32_t* n_out) {
-  if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, img && xy && n_out && H > 0 && W > 0, "good_features: bad arguments");
-  *n_out = 0;
-  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t px = (size_t)H * W;
-  hipStream_t st = ctx->stream;
-  VO_TRY(vo_ensure(ctx, ctx->img, px));
-  if (mask) VO_TRY(vo_ensure(ctx, ctx->img2, px));
-  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, img, px, hipMemcpyHostToDevice, st));
-  if (mask) VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img2.p, mask, px, hipMemcpyHostToDevice, st));
-  const float* d_xy = nullptr;
-  int32_t n = 0;
-  VO_TRY(vo_good_features_dev(ctx, (const uint8_t*)ctx->img.p, H, W, mask ? (const uint8_t*)ctx->img2.p : nullptr, max_corners,
-                              quality, min_dist, block, &d_xy, &n));
-  if (n > 0) {
-    VO_HIP_TRY(ctx, hipMemcpyAsync(xy, d_xy, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    VO_HIP_TRY(ctx, hipStreamSynchronize(st));
-  }
-  *n_out = n;
-  return VO_OK;
-}
-
-}  // extern "C"
-
-// ---- the batched form ----------------------------------------------------------------------------------------------------
-// A fixed launch sequence for S images of one size on ctx->stream: map + maximum, candidates, segment bounds, segmented
-// sort, prep, lists, GB_R rounds, walk (flagged images), emit.  Nothing is read back and nothing waits (growing the
-// context's workspace, on the first call of a size, does).  Workspace per image, linear in S; at 1376 x 1241 with
-// minDistance 8 (26 832 cells), max_corners 2000:
+// ---- one call, in stages -------------------------------------------------------------------------------------------------
+// plan (checks, sizes, workspace, memsets), front (map + maximum, candidates, segment bounds and paths), the sort, back
+// (prep, lists, the rounds, the walk of flagged images, emit), all on ctx->stream.  Only growing the context's workspace,
+// on the first call of a size, waits.  Workspace per image, linear in S; at 1376 x 1241 with minDistance 8 (26 832 cells),
+// max_corners 2000:
 //   eigenvalue map 6 830 464 B, candidate keys and their sorted copy 2 x 3 415 744 B, the sort's own copy 3 415 744 B,
 //   neighbour lists 131 072 x 24 x 4 = 12 582 912 B, state words 524 288 B, cell candidates 26 832 x 32 x 4 = 3 434 496 B,
 //   cell counts (rounds + walk) 214 656 B, the walk's cells 858 624 B and staging rows 16 000 B, control block 256 B
 //   = 34 708 928 B, about 33.1 MiB per image.
-extern "C" {
+struct gfb_call {
+  // the arguments of vo_good_features_batch_gated_dev, in its order
+  const uint8_t* d_imgs;
+  size_t img_stride;
+  int S, H, W;
+  const uint8_t* d_masks;
+  size_t mask_stride;
+  int max_corners;
+  double quality, min_dist;
+  int block;
+  float* d_xy;
+  size_t xy_stride;
+  int32_t *d_n, *d_over, *d_info;
+  int n_rounds, cand_limit;
+  const int* d_go;
+  // what plan makes of them
+  gfb_dims g;
+  bool rounds;                      // min_dist >= 1: the rule runs; below, the corners are the sorted list's head
+  size_t out_cap, sort_tmp;
+};
 
-int vo_good_features_capacity(int H, int W, int max_corners) {
-  if (H <= 0 || W <= 0) return 0;
-  if (max_corners > 0) return max_corners;
-  const size_t cap = ((size_t)H * W + 3) / 4 + 64;
-  return cap > 0x7fffffffull ? 0 : (int)cap;
+size_t min_eig_lds(int block) {
+  const int RW = GX + block - 1, RH = GY + block - 1;
+  return ((size_t)RW * RH + (size_t)3 * RH * GX) * 4;
 }
 
-int vo_good_features_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
-                               const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality, double min_dist,
-                               int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over, int32_t* d_info) {
-  return vo_good_features_batch_rounds_dev(ctx, d_imgs, img_stride, S, H, W, d_masks, mask_stride, max_corners, quality, min_dist,
-                                           block, d_xy, xy_stride, d_n, d_over, d_info, GB_R, GC_WG * GC_T);
-}
-
-// (vo_internal.h) the same with the number of round launches and the rounds path's candidate limit given: what the tests
-// use to send images through the hand-over from unfinished rounds to the walk and through the walk of a long list
-int vo_good_features_batch_rounds_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
-                                      const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
-                                      double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over,
-                                      int32_t* d_info, int n_rounds, int cand_limit) {
-  return vo_good_features_batch_gated_dev(ctx, d_imgs, img_stride, S, H, W, d_masks, mask_stride, max_corners, quality, min_dist,
-                                          block, d_xy, xy_stride, d_n, d_over, d_info, n_rounds, cand_limit, nullptr);
-}
-
-}  // extern "C"
-
-// (vo_internal.h) the argument checks of the batched forms alone
-int vo_good_features_batch_check(vo_ctx* ctx, int S, int H, int W, double quality, double min_dist, int block) {
+int gfb_check(vo_ctx* ctx, const char* who, int S, int H, int W, double quality, double min_dist, int block) {
   if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, H > 0 && W > 0, "good_features_batch: bad arguments");
-  VO_REQUIRE(ctx, S >= 1 && S <= 65535, "good_features_batch: S must be in 1..65535");
-  VO_REQUIRE(ctx, block >= 1 && block <= 31, "good_features_batch: blockSize must be in 1..31");
-  VO_REQUIRE(ctx, quality > 0 && min_dist >= 0, "good_features_batch: bad quality / minDistance");
-  VO_REQUIRE(ctx, W < 65536 && H < 65536, "good_features_batch: image side must be below 65536");
+  VO_REQUIRE(ctx, H > 0 && W > 0, "%s: bad arguments", who);
+  VO_REQUIRE(ctx, S >= 1 && S <= 65535, "%s: S must be in 1..65535", who);
+  VO_REQUIRE(ctx, block >= 1 && block <= 31, "%s: blockSize must be in 1..31", who);
+  VO_REQUIRE(ctx, quality > 0 && min_dist >= 0, "%s: bad quality / minDistance", who);
+  VO_REQUIRE(ctx, W < 65536 && H < 65536, "%s: image side must be below 65536", who);
   const size_t cap = ((size_t)H * W + 3) / 4 + 64;                // 3x3 maxima: at most one per 2x2 block
-  VO_REQUIRE(ctx, (size_t)S * cap < 0xffffffffull, "good_features_batch: %d images of %d x %d exceed the sort's 32-bit offsets", S, H, W);
+  VO_REQUIRE(ctx, (size_t)S * cap < 0xffffffffull, "%s: %d images of %d x %d exceed the sort's 32-bit offsets", who, S, H, W);
   return VO_OK;
 }
 
-// (vo_internal.h) ... and with a gate per image
-int vo_good_features_batch_gated_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
-                                     const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
-                                     double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over,
-                                     int32_t* d_info, int n_rounds, int cand_limit, const int* d_go) {
-  if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, n_rounds >= 0 && n_rounds <= GB_R && cand_limit >= 1 && cand_limit <= GC_WG * GC_T,
-             "good_features_batch: rounds must be in 0..%d, the candidate limit in 1..%d", GB_R, GC_WG * GC_T);
-  VO_REQUIRE(ctx, d_imgs && d_xy && d_n && H > 0 && W > 0, "good_features_batch: bad arguments");
-  VO_TRY(vo_good_features_batch_check(ctx, S, H, W, quality, min_dist, block));
-  const size_t px = (size_t)H * W, Sz = (size_t)S;
-  VO_REQUIRE(ctx, img_stride >= px && (!d_masks || mask_stride >= px), "good_features_batch: image / mask stride below H*W");
+// host_sort: the workspace of a device-wide sort of one image's keys (gfb_sort_counted) in place of the segmented one's
+int gfb_plan(vo_ctx* ctx, const char* who, gfb_call& c, bool host_sort) {
+  VO_REQUIRE(ctx, c.n_rounds >= 0 && c.n_rounds <= GB_R && c.cand_limit >= 1 && c.cand_limit <= GC_WG * GC_T,
+             "%s: rounds must be in 0..%d, the candidate limit in 1..%d", who, GB_R, GC_WG * GC_T);
+  VO_REQUIRE(ctx, c.d_imgs && c.d_xy && c.d_n && c.H > 0 && c.W > 0, "%s: bad arguments", who);
+  VO_TRY(gfb_check(ctx, who, c.S, c.H, c.W, c.quality, c.min_dist, c.block));
+  const size_t px = (size_t)c.H * c.W, Sz = (size_t)c.S;
+  VO_REQUIRE(ctx, c.img_stride >= px && (!c.d_masks || c.mask_stride >= px), "%s: image / mask stride below H*W", who);
   const size_t cap = (px + 3) / 4 + 64;                          // 3x3 maxima: at most one per 2x2 block
-  const size_t out_cap = max_corners > 0 ? (size_t)max_corners : cap;
-  VO_REQUIRE(ctx, xy_stride >= out_cap, "good_features_batch: xy_stride %zu is below the capacity %zu", xy_stride, out_cap);
+  c.out_cap = c.max_corners > 0 ? (size_t)c.max_corners : cap;
+  VO_REQUIRE(ctx, c.xy_stride >= c.out_cap, "%s: xy_stride %zu is below the capacity %zu", who, c.xy_stride, c.out_cap);
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   vo_buf* s = ctx->scratch;
-  gfb_dims g;
-  g.H = H;
-  g.W = W;
-  g.cell = std::max(1, (int)std::lround(min_dist));
-  g.gw = (W + g.cell - 1) / g.cell;
-  g.gh = (H + g.cell - 1) / g.cell;
+  gfb_dims& g = c.g;
+  g.H = c.H;
+  g.W = c.W;
+  g.cell = std::max(1, (int)std::lround(c.min_dist));
+  g.gw = (c.W + g.cell - 1) / g.cell;
+  g.gh = (c.H + g.cell - 1) / g.cell;
   g.ccap = (int)std::min<long long>(GC_CCAP, (long long)g.cell * g.cell);
   g.cap = (unsigned)cap;
-  g.lim = (unsigned)std::min<size_t>((size_t)cand_limit, cap);
-  g.rounds = n_rounds;
+  g.lim = (unsigned)std::min<size_t>((size_t)c.cand_limit, cap);
+  g.rounds = c.n_rounds;
   g.px = px;
   g.cells = (size_t)g.gw * g.gh;
-  const bool rounds = min_dist >= 1;
-  size_t sort_tmp = 0;
-  VO_HIP_TRY(ctx, rocprim::segmented_radix_sort_keys_desc<gfb_sort_config>(
-                      nullptr, sort_tmp, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned)(Sz * cap),
-                      (unsigned)S, (unsigned*)nullptr, (unsigned*)nullptr, 0, 64, st));
+  c.rounds = c.min_dist >= 1;
+  c.sort_tmp = 0;
+  if (host_sort)
+    VO_HIP_TRY(ctx, rocprim::radix_sort_keys_desc(nullptr, c.sort_tmp, (unsigned long long*)nullptr,
+                                                  (unsigned long long*)nullptr, cap, 0, 64, st));
+  else
+    VO_HIP_TRY(ctx, rocprim::segmented_radix_sort_keys_desc<gfb_sort_config>(
+                        nullptr, c.sort_tmp, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned)(Sz * cap),
+                        (unsigned)c.S, (unsigned*)nullptr, (unsigned*)nullptr, 0, 64, st));
   VO_TRY(vo_ensure(ctx, s[0], Sz * px * 4));
   VO_TRY(vo_ensure(ctx, s[1], Sz * GB_CTL * 4));
   VO_TRY(vo_ensure(ctx, s[2], Sz * cap * 8));
   VO_TRY(vo_ensure(ctx, s[3], Sz * cap * 8));
-  VO_TRY(vo_ensure(ctx, s[4], sort_tmp + 256));
+  VO_TRY(vo_ensure(ctx, s[4], c.sort_tmp + 256));
   VO_TRY(vo_ensure(ctx, s[11], Sz * 2 * 4));
-  if (rounds) {
+  if (c.rounds) {
     VO_TRY(vo_ensure(ctx, s[5], Sz * g.cells * 4 * 2));
     VO_TRY(vo_ensure(ctx, s[6], Sz * g.cells * GRID_SLOTS * 4));
-    VO_TRY(vo_ensure(ctx, s[7], Sz * out_cap * 8));
+    VO_TRY(vo_ensure(ctx, s[7], Sz * c.out_cap * 8));
     VO_TRY(vo_ensure(ctx, s[8], Sz * g.cells * g.ccap * 4));
     VO_TRY(vo_ensure(ctx, s[9], Sz * g.lim * 4));
     VO_TRY(vo_ensure(ctx, s[10], Sz * g.lim * GC_NB * 4));
     VO_HIP_TRY(ctx, hipMemsetAsync(s[5].p, 0, Sz * g.cells * 4 * 2, st));
   }
   VO_HIP_TRY(ctx, hipMemsetAsync(s[1].p, 0, Sz * GB_CTL * 4, st));
+  return VO_OK;
+}
+
+int gfb_front(vo_ctx* ctx, const gfb_call& c) {
+  hipStream_t st = ctx->stream;
+  vo_buf* s = ctx->scratch;
   unsigned* d_ctl = (unsigned*)s[1].p;
-  unsigned* d_seg = (unsigned*)s[11].p;
-  unsigned long long* d_keys = (unsigned long long*)s[2].p;
-  unsigned long long* d_sorted = (unsigned long long*)s[3].p;
-  const double scale = 1.0 / (4.0 * block * 255.0);
-  const int RW = GX + block - 1, RH = GY + block - 1;
-  const size_t lds = ((size_t)RW * RH + (size_t)3 * RH * GX) * 4;
-  const dim3 tiles(vo_cdiv(W, GX), vo_cdiv(H, GY), S);
-  hipLaunchKernelGGL(min_eig_batch_kernel, tiles, dim3(GT), lds, st, d_imgs, img_stride, g, block, (float)(scale * scale),
-                     d_masks, mask_stride, (float*)s[0].p, d_ctl, d_go);
+  const double scale = 1.0 / (4.0 * c.block * 255.0);
+  const dim3 tiles(vo_cdiv(c.W, GX), vo_cdiv(c.H, GY), c.S);
+  hipLaunchKernelGGL(min_eig_batch_kernel, tiles, dim3(GT), min_eig_lds(c.block), st, c.d_imgs, c.img_stride, c.g, c.block,
+                     (float)(scale * scale), c.d_masks, c.mask_stride, (float*)s[0].p, d_ctl, c.d_go);
   VO_TRY(vo_check_launch(ctx, "min_eig_batch_kernel"));
-  hipLaunchKernelGGL(corner_candidates_batch_kernel, tiles, dim3(GT), 0, st, (const float*)s[0].p, g, d_masks, mask_stride,
-                     quality, d_keys, d_ctl, d_go);
+  hipLaunchKernelGGL(corner_candidates_batch_kernel, tiles, dim3(GT), 0, st, (const float*)s[0].p, c.g, c.d_masks,
+                     c.mask_stride, c.quality, (unsigned long long*)s[2].p, d_ctl, c.d_go);
   VO_TRY(vo_check_launch(ctx, "corner_candidates_batch_kernel"));
-  hipLaunchKernelGGL(gfb_segments_kernel, dim3(1), dim3(256), 0, st, S, g, rounds ? 0 : 1, d_ctl, d_seg);
+  hipLaunchKernelGGL(gfb_segments_kernel, dim3(1), dim3(256), 0, st, c.S, c.g, c.rounds ? 0 : 1, d_ctl, (unsigned*)s[11].p);
   VO_TRY(vo_check_launch(ctx, "gfb_segments_kernel"));
-  VO_HIP_TRY(ctx, rocprim::segmented_radix_sort_keys_desc<gfb_sort_config>(s[4].p, sort_tmp, d_keys, d_sorted,
-                                                                           (unsigned)(Sz * cap), (unsigned)S, d_seg,
-                                                                           d_seg + S, 0, 64, st));
-  if (rounds) {
-    const double md2 = min_dist * min_dist;
+  return VO_OK;
+}
+
+// capacity-sized segments, one per image, bounded on the device: no host turn
+int gfb_sort_segments(vo_ctx* ctx, const gfb_call& c) {
+  vo_buf* s = ctx->scratch;
+  size_t sort_tmp = c.sort_tmp;
+  unsigned* d_seg = (unsigned*)s[11].p;
+  VO_HIP_TRY(ctx, rocprim::segmented_radix_sort_keys_desc<gfb_sort_config>(
+                      s[4].p, sort_tmp, (unsigned long long*)s[2].p, (unsigned long long*)s[3].p,
+                      (unsigned)((size_t)c.S * c.g.cap), (unsigned)c.S, d_seg, d_seg + c.S, 0, 64, ctx->stream));
+  return VO_OK;
+}
+
+// one image (plan's host_sort): its candidate count comes back -- the segments kernel has turned an overflow of the
+// capacity into no candidates and the fault bit -- and exactly that many keys are sorted device-wide; at 1376 x 1241
+// that sort takes 36 us where the one-segment sort above takes 426 us, which the host turn buys
+int gfb_sort_counted(vo_ctx* ctx, const gfb_call& c) {
+  vo_buf* s = ctx->scratch;
+  hipStream_t st = ctx->stream;
+  size_t sort_tmp = c.sort_tmp;
+  unsigned nc = 0;
+  VO_HIP_TRY(ctx, hipMemcpyAsync(&nc, (const unsigned*)s[1].p + GB_NC, 4, hipMemcpyDeviceToHost, st));
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  ctx->bytes_d2h += 4;
+  if (nc > 0)
+    VO_HIP_TRY(ctx, rocprim::radix_sort_keys_desc(s[4].p, sort_tmp, (unsigned long long*)s[2].p, (unsigned long long*)s[3].p,
+                                                  (size_t)nc, 0, 64, st));
+  return VO_OK;
+}
+
+int gfb_back(vo_ctx* ctx, const gfb_call& c) {
+  hipStream_t st = ctx->stream;
+  vo_buf* s = ctx->scratch;
+  const gfb_dims& g = c.g;
+  const size_t Sz = (size_t)c.S;
+  unsigned* d_ctl = (unsigned*)s[1].p;
+  const unsigned long long* d_sorted = (const unsigned long long*)s[3].p;
+  if (c.rounds) {
+    const double md2 = c.min_dist * c.min_dist;
     unsigned* cell_cnt = (unsigned*)s[5].p;
     unsigned* walk_cnt = cell_cnt + Sz * g.cells;
-    const dim3 grid(vo_cdiv((int)g.lim, GC_T), S);
-    hipLaunchKernelGGL(gfb_prep_kernel, grid, dim3(GC_T), 0, st, (const unsigned long long*)d_sorted, g, cell_cnt,
-                       (unsigned*)s[8].p, (unsigned*)s[9].p, d_ctl);
+    const dim3 grid(vo_cdiv((int)g.lim, GC_T), c.S);
+    hipLaunchKernelGGL(gfb_prep_kernel, grid, dim3(GC_T), 0, st, d_sorted, g, cell_cnt, (unsigned*)s[8].p, (unsigned*)s[9].p,
+                       d_ctl);
     VO_TRY(vo_check_launch(ctx, "gfb_prep_kernel"));
-    hipLaunchKernelGGL(gfb_lists_kernel, grid, dim3(GC_T), 0, st, (const unsigned long long*)d_sorted, g, md2,
-                       (const unsigned*)cell_cnt, (const unsigned*)s[8].p, (unsigned*)s[9].p, (unsigned*)s[10].p,
-                       (const unsigned*)d_ctl);
+    hipLaunchKernelGGL(gfb_lists_kernel, grid, dim3(GC_T), 0, st, d_sorted, g, md2, (const unsigned*)cell_cnt,
+                       (const unsigned*)s[8].p, (unsigned*)s[9].p, (unsigned*)s[10].p, (const unsigned*)d_ctl);
     VO_TRY(vo_check_launch(ctx, "gfb_lists_kernel"));
-    for (int r = 0; r < n_rounds; ++r)
-      hipLaunchKernelGGL(gfb_round_kernel, grid, dim3(GC_T), 0, st, (const unsigned long long*)d_sorted, g, md2, r,
-                         (const unsigned*)cell_cnt, (const unsigned*)s[8].p, (unsigned*)s[9].p, (const unsigned*)s[10].p,
-                         d_ctl);
+    for (int r = 0; r < c.n_rounds; ++r)
+      hipLaunchKernelGGL(gfb_round_kernel, grid, dim3(GC_T), 0, st, d_sorted, g, md2, r, (const unsigned*)cell_cnt,
+                         (const unsigned*)s[8].p, (unsigned*)s[9].p, (const unsigned*)s[10].p, d_ctl);
     VO_TRY(vo_check_launch(ctx, "gfb_round_kernel"));
-    hipLaunchKernelGGL(greedy_distance_batch_kernel, dim3(S), dim3(GF_T), 0, st, (const unsigned long long*)d_sorted, g, md2,
-                       max_corners, walk_cnt, (unsigned*)s[6].p, (float*)s[7].p, out_cap, d_ctl);
+    hipLaunchKernelGGL(greedy_distance_batch_kernel, dim3(c.S), dim3(GF_T), 0, st, d_sorted, g, md2, c.max_corners, walk_cnt,
+                       (unsigned*)s[6].p, (float*)s[7].p, c.out_cap, d_ctl);
     VO_TRY(vo_check_launch(ctx, "greedy_distance_batch_kernel"));
   }
-  hipLaunchKernelGGL(gfb_emit_kernel, dim3(S), dim3(GC_T), 0, st, (const unsigned long long*)d_sorted, g, max_corners,
-                     (const unsigned*)s[9].p, (const float*)s[7].p, out_cap, (const unsigned*)d_ctl, d_xy, xy_stride, d_n,
-                     d_over, d_info);
+  hipLaunchKernelGGL(gfb_emit_kernel, dim3(c.S), dim3(GC_T), 0, st, d_sorted, g, c.max_corners, (const unsigned*)s[9].p,
+                     (const float*)s[7].p, c.out_cap, (const unsigned*)d_ctl, c.d_xy, c.xy_stride, c.d_n, c.d_over, c.d_info);
   VO_TRY(vo_check_launch(ctx, "gfb_emit_kernel"));
   return VO_OK;
 }
 
-extern "C" {
-
-int vo_good_features_batch(vo_ctx* ctx, const uint8_t* imgs, const uint8_t* masks, int S, int H, int W, int max_corners,
-                           double quality, double min_dist, int block, float* xy, int32_t* n_out) {
+// Both host forms: the S images (and masks) up, the stages on the context's own buffers, counts and corners down.
+// host_sort (S = 1, vo_good_features): gfb_sort_counted for the sort, and the one-image call's error texts.
+int gfb_host(vo_ctx* ctx, const char* who, bool host_sort, const uint8_t* imgs, const uint8_t* masks, int S, int H, int W,
+             int max_corners, double quality, double min_dist, int block, float* xy, int32_t* n_out) {
   if (!ctx) return VO_EINVAL;
-  VO_REQUIRE(ctx, imgs && xy && n_out && H > 0 && W > 0 && S >= 1, "good_features_batch: bad arguments");
+  VO_REQUIRE(ctx, imgs && xy && n_out && H > 0 && W > 0 && S >= 1, "%s: bad arguments", who);
   for (int q = 0; q < S; ++q) n_out[q] = 0;
   const size_t rows = (size_t)vo_good_features_capacity(H, W, max_corners);
-  VO_REQUIRE(ctx, rows > 0, "good_features_batch: image too large");
+  VO_REQUIRE(ctx, rows > 0, "%s: image too large", who);
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t px = (size_t)H * W, Sz = (size_t)S;
   hipStream_t st = ctx->stream;
@@ -1088,17 +784,24 @@ int vo_good_features_batch(vo_ctx* ctx, const uint8_t* imgs, const uint8_t* mask
   if (masks) VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img2.p, masks, Sz * px, hipMemcpyHostToDevice, st));
   ctx->bytes_h2d += (int64_t)(Sz * px * (masks ? 2 : 1));
   int32_t* d_cnt = (int32_t*)s[13].p;
-  VO_TRY(vo_good_features_batch_dev(ctx, (const uint8_t*)ctx->img.p, px, S, H, W, masks ? (const uint8_t*)ctx->img2.p : nullptr,
-                                    px, max_corners, quality, min_dist, block, (float*)s[12].p, rows, d_cnt, d_cnt + S,
-                                    nullptr));
+  gfb_call c = {(const uint8_t*)ctx->img.p, px, S, H, W, masks ? (const uint8_t*)ctx->img2.p : nullptr, px, max_corners,
+                quality, min_dist, block, (float*)s[12].p, rows, d_cnt, d_cnt + S, nullptr, GB_R, GC_WG * GC_T, nullptr};
+  VO_TRY(gfb_plan(ctx, who, c, host_sort));
+  VO_TRY(gfb_front(ctx, c));
+  VO_TRY(host_sort ? gfb_sort_counted(ctx, c) : gfb_sort_segments(ctx, c));
+  VO_TRY(gfb_back(ctx, c));
   std::vector<int32_t> cnt(Sz * 2);
   VO_HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), d_cnt, Sz * 8, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   ctx->bytes_d2h += (int64_t)(Sz * 8);
   for (int q = 0; q < S; ++q) {
-    if (cnt[Sz + q] == 1)
+    const int over = cnt[Sz + q];
+    if (over && host_sort)
+      return over == 1 ? vo_set_error(ctx, VO_ECAPACITY, "good_features: the local maxima exceed the candidate capacity %u", c.g.cap)
+                       : vo_set_error(ctx, VO_ECAPACITY, "good_features: more than %d corners in one grid cell", GRID_SLOTS);
+    if (over == 1)
       return vo_set_error(ctx, VO_ECAPACITY, "good_features_batch: the local maxima of image %d exceed the candidate capacity", q);
-    if (cnt[Sz + q])
+    if (over)
       return vo_set_error(ctx, VO_ECAPACITY, "good_features_batch: image %d has more than %d corners in one grid cell", q, GRID_SLOTS);
   }
   // a corner limit: the S blocks in one download (rows behind an image's count are workspace); every corner: the blocks
@@ -1119,6 +822,91 @@ int vo_good_features_batch(vo_ctx* ctx, const uint8_t* imgs, const uint8_t* mask
                                        hipMemcpyDeviceToHost, st));
     ctx->bytes_d2h += (int64_t)(total * 8);
   }
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  return VO_OK;
+}
+
+}  // namespace
+
+// (vo_internal.h) the argument checks of the batched forms alone
+int vo_good_features_batch_check(vo_ctx* ctx, int S, int H, int W, double quality, double min_dist, int block) {
+  return gfb_check(ctx, "good_features_batch", S, H, W, quality, min_dist, block);
+}
+
+// (vo_internal.h) the device form every other one goes through: plan, front, the segmented sort, back -- nothing is read
+// back and nothing waits.  d_go gates images out; n_rounds and cand_limit are what the tests use to send images through
+// the hand-over from unfinished rounds to the walk and through the walk of a long list.
+int vo_good_features_batch_gated_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                                     const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
+                                     double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over,
+                                     int32_t* d_info, int n_rounds, int cand_limit, const int* d_go) {
+  if (!ctx) return VO_EINVAL;
+  gfb_call c = {d_imgs, img_stride, S, H, W, d_masks, mask_stride, max_corners, quality, min_dist, block, d_xy, xy_stride,
+                d_n, d_over, d_info, n_rounds, cand_limit, d_go};
+  VO_TRY(gfb_plan(ctx, "good_features_batch", c, false));
+  VO_TRY(gfb_front(ctx, c));
+  VO_TRY(gfb_sort_segments(ctx, c));
+  return gfb_back(ctx, c);
+}
+
+extern "C" {
+
+int vo_good_features_capacity(int H, int W, int max_corners) {
+  if (H <= 0 || W <= 0) return 0;
+  if (max_corners > 0) return max_corners;
+  const size_t cap = ((size_t)H * W + 3) / 4 + 64;
+  return cap > 0x7fffffffull ? 0 : (int)cap;
+}
+
+int vo_good_features_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                               const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality, double min_dist,
+                               int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over, int32_t* d_info) {
+  return vo_good_features_batch_rounds_dev(ctx, d_imgs, img_stride, S, H, W, d_masks, mask_stride, max_corners, quality, min_dist,
+                                           block, d_xy, xy_stride, d_n, d_over, d_info, GB_R, GC_WG * GC_T);
+}
+
+// (vo_internal.h) the same with the number of round launches and the rounds path's candidate limit given
+int vo_good_features_batch_rounds_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                                      const uint8_t* d_masks, size_t mask_stride, int max_corners, double quality,
+                                      double min_dist, int block, float* d_xy, size_t xy_stride, int32_t* d_n, int32_t* d_over,
+                                      int32_t* d_info, int n_rounds, int cand_limit) {
+  return vo_good_features_batch_gated_dev(ctx, d_imgs, img_stride, S, H, W, d_masks, mask_stride, max_corners, quality, min_dist,
+                                          block, d_xy, xy_stride, d_n, d_over, d_info, n_rounds, cand_limit, nullptr);
+}
+
+int vo_good_features_batch(vo_ctx* ctx, const uint8_t* imgs, const uint8_t* masks, int S, int H, int W, int max_corners,
+                           double quality, double min_dist, int block, float* xy, int32_t* n_out) {
+  return gfb_host(ctx, "good_features_batch", false, imgs, masks, S, H, W, max_corners, quality, min_dist, block, xy, n_out);
+}
+
+int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_t* mask, int max_corners,
+                     double quality, double min_dist, int block, float* xy, int32_t* n_out) {
+  return gfb_host(ctx, "good_features", true, img, mask, 1, H, W, max_corners, quality, min_dist, block, xy, n_out);
+}
+
+int vo_min_eigen_map(vo_ctx* ctx, const uint8_t* img, int H, int W, int block, float* eig) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, img && eig && H > 0 && W > 0, "min_eigen_map: bad arguments");
+  VO_REQUIRE(ctx, block >= 1 && block <= 31, "min_eigen_map: blockSize must be in 1..31");
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t px = (size_t)H * W;
+  hipStream_t st = ctx->stream;
+  vo_buf* s = ctx->scratch;
+  VO_TRY(vo_ensure(ctx, ctx->img, px));
+  VO_TRY(vo_ensure(ctx, s[0], px * 4));
+  VO_TRY(vo_ensure(ctx, s[1], GB_CTL * 4));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, img, px, hipMemcpyHostToDevice, st));
+  VO_HIP_TRY(ctx, hipMemsetAsync(s[1].p, 0, GB_CTL * 4, st));
+  gfb_dims g = {};                   // (the map kernel reads H, W and px alone)
+  g.H = H;
+  g.W = W;
+  g.px = px;
+  const double scale = 1.0 / (4.0 * block * 255.0);
+  hipLaunchKernelGGL(min_eig_batch_kernel, dim3(vo_cdiv(W, GX), vo_cdiv(H, GY), 1), dim3(GT), min_eig_lds(block), st,
+                     (const uint8_t*)ctx->img.p, px, g, block, (float)(scale * scale), (const uint8_t*)nullptr, (size_t)0,
+                     (float*)s[0].p, (unsigned*)s[1].p, (const int*)nullptr);
+  VO_TRY(vo_check_launch(ctx, "min_eig_batch_kernel"));
+  VO_HIP_TRY(ctx, hipMemcpyAsync(eig, s[0].p, px * 4, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   return VO_OK;
 }

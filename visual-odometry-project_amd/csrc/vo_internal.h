@@ -68,7 +68,7 @@ struct vo_ctx {
   // pinned host staging
   void* h_pin = nullptr;
   size_t h_pin_cap = 0;
-  // bytes the device-resident forms of the bootstrap stages (vo_good_features_dev, vo_fundamental_*_dev) copied between
+  // bytes the device-resident forms of the bootstrap stages (vo_good_features_batch_dev, vo_fundamental_*_dev) copied between
   // host and device: scalars and the RANSAC batch's samples / counts; vo_pipeline_bootstrap_seq reports the difference
   int64_t bytes_h2d = 0, bytes_d2h = 0;
   // the device 8-point RANSAC's workspace (bootstrap.hip: vo_fundamental_ransac_dev), grown to the largest lane count and
@@ -218,11 +218,9 @@ extern "C" int vo_patch_descriptors_u8_batch_dev(vo_ctx* ctx, const uint8_t* d_i
                                                  const double* d_kp_xy, size_t kp_stride, int N, int r, uint8_t* d_desc,
                                                  size_t desc_stride, int row_bytes);
 // Device-resident forms of the two-view bootstrap's stages (goodfeatures.hip, bootstrap.hip): inputs in HBM, results left
-// there.  vo_good_features / vo_fundamental_hypotheses / vo_fundamental_fit / vo_relative_pose upload, call these and
-// download.  All work on ctx->stream; the hypothesis form synchronises (the counts come back), the others do not.
-//   good_features: *d_xy_out (n float pairs) points into the context's workspace (scratch[7]) until its next call
-int vo_good_features_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const uint8_t* d_mask, int max_corners,
-                         double quality, double min_dist, int block, const float** d_xy_out, int32_t* n_out);
+// there.  vo_fundamental_hypotheses / vo_fundamental_fit / vo_relative_pose upload, call these and download (vo_good_features
+// runs the stages of vo_good_features_batch_dev at S = 1).  All work on ctx->stream; the hypothesis form synchronises (the
+// counts come back), the others do not.
 // vo_good_features_batch_dev (vo_hip.h) with the number of round launches (0 .. 24; the ABI call: 24) and the rounds path's
 // candidate limit (1 .. 131 072; the ABI call: 131 072) given.  Results never depend on either: an image the rounds do not
 // finish, or whose candidates exceed the limit, is finished by the one-workgroup walk.  Like the other extern "C" entry
