@@ -93,6 +93,8 @@ enum {
   VO_K_STATE_LANDMARKS = 25,
   VO_K_EXPORT = 26,
   VO_K_SHI_TOMASI_CHAIN = 27,   /* the frame loop's Shi-Tomasi re-detect, all of its launches (vo_pipeline_config.detector = 1) */
+  VO_K_WINDOW_BA = 28,          /* vo_window_ba_dev's solver kernel */
+  VO_K_WINDOW_BUILD = 29,       /* vo_window_from_tracks_dev, both of its launches */
   VO_K_COUNT = 32
 };
 int vo_prof_enable(vo_ctx* ctx, int kernel_id);
@@ -858,6 +860,88 @@ int vo_pipeline_bootstrap_lanes(vo_pipeline* p, int n_lanes, const int32_t* seqs
                                 const vo_bootstrap_params* prm, const vo_pcg64* rngs, vo_bootstrap_result* outs, int32_t* status);
 /* the generator the bootstrap's RANSAC starts from: np.random.default_rng(2023)'s PCG64 state */
 void vo_bootstrap_default_rng(vo_pcg64* rng);
+
+/* ---- Window bundle adjustment ------------------------------------------------------------------
+ * Nothing in the reference corresponds to it (its poses stay as the P3P refinement left them, its landmarks as their two-view
+ * triangulation made them): a local back end over the last W frames, fed from the observation records above.
+ *
+ * One window: W poses (world -> camera; R row-major then t, 12 doubles: vo_refine_pose_dev's Rt0), L landmarks (3 doubles),
+ * M observations (slot, u, v) grouped by landmark -- lm_start[L + 1] is the CSR, landmark i owns observations lm_start[i] ..
+ * lm_start[i + 1] - 1, at least one, their slots strictly ascending -- and one K (3x3 row-major; fx, fy, cx, cy are read).
+ * The leading n_fixed >= 1 slots are held (default 2: the six gauge freedoms and the scale).
+ *   cost    e = x - proj(K, R X + t);  rho = |e|^2 when huber_px == 0, else Huber's: |e|^2 for |e| <= d, 2 d |e| - d^2 above
+ *           (d = huber_px), with the IRLS weight w = min(1, d / |e|) (w = 1 for the squared loss);  cost = sum rho
+ *   step    Levenberg-Marquardt on the weighted normal equations at the current point.  Pose increment (v, w) on the left,
+ *           T <- [Exp(w) | v] T, Exp by Rodrigues' formula (vo_refine_pose's parametrisation); landmark increment additive.
+ *           Per observation with p = R X + t, a = fx / p_z, b = fy / p_z, c = -fx p_x / p_z^2, d = -fy p_y / p_z^2:
+ *             J_pose = [a 0 c  c p_y  a p_z - c p_x  -a p_y;  0 b d  d p_y - b p_z  -d p_x  b p_x],  J_lm = [a 0 c; 0 b d] R.
+ *           U_j = sum w J_pose^T J_pose and g_p,j = sum w J_pose^T e over the observations of free pose j;  V_i = sum w
+ *           J_lm^T J_lm and g_l,i = sum w J_lm^T e over those of landmark i (every slot);  W_ij = w J_pose^T J_lm for an
+ *           observation of a free pose.  Damping: the diagonals of U and V times (1 + lambda).  Reduced system over the
+ *           free poses: S = U* - sum_i W_i V_i*^-1 W_i^T, b = g_p - sum_i W_i V_i*^-1 g_l,i, dense, 6 (W - n_fixed) square,
+ *           solved by Cholesky without pivoting; landmarks by back-substitution, dX_i = V_i*^-1 (g_l,i - sum_j W_ij^T d_j).
+ *           A landmark seen from held slots only adds nothing to S and is still refined.  A pivot that is not positive, in
+ *           a 3x3 or in S, rejects the trial.
+ *   control lambda starts at lambda0.  Before every trial, in this order: `max_iter` accepted steps -> status 1;
+ *           `max_trials` trials -> status 2; lambda > 1e12 -> status 3.  The system is solved (a rejected solve counts as a
+ *           trial).  |delta| <= step_tol (1 + |x|) -- delta: every pose and landmark increment, x: the free poses'
+ *           translations and every landmark, 2-norms -- ends the solve with status 0: the step is not taken and not counted.
+ *           Otherwise the trial is counted and evaluated: accepted iff every observation has p_z > 0 at the trial point and
+ *           cost_new <= cost; then lambda <- max(lambda / 10, 1e-12), else lambda <- 10 lambda.
+ *   refused status 4, the window bit for bit as it was: L <= 0 or M <= 0 (empty) or beyond the capacities; no free pose
+ *           (n_fixed >= W); a CSR that is not one (see above) or a slot outside 0 .. W - 1; a non-finite observation, pose,
+ *           landmark or intrinsic; an observation with p_z <= 0 at the start.
+ * All of it fp64.  Every sum has one fixed order (per landmark in CSR order, landmarks ascending; workgroup sums by a
+ * butterfly and a fixed-order add; no floating-point atomics): the same call gives the same bits, and a window gives the same
+ * bits alone as inside a batch.
+ *
+ * vo_window_ba_dev: S windows per call, one workgroup each, no host read until the caller asks for the results.  Window q:
+ *   d_counts + 4 q     int32 {L, M, -, -} (the header vo_window_from_tracks_dev writes)
+ *   d_K + 9 q          d_poses + 12 W q (in place)      d_X + 3 L_cap q (in place)
+ *   d_lm_start + (L_cap + 1) q      d_obs_slot + M_cap q      d_obs_xy + 2 M_cap q      d_results + q
+ * W <= 16, 1 <= M_cap <= L_cap W.  The workspace (vo_window_ba_workspace_bytes) is the context's and grows on demand.
+ * Enqueued on the context's stream; does not synchronise.  vo_window_ba: the same from host arrays (uploads, runs, downloads
+ * poses, X and results, synchronises).  Bad arguments: VO_EINVAL with a message.                                       */
+typedef struct vo_ba_params {             /* 0 in a field = the default named here */
+  int32_t max_iter;                       /* accepted steps, <= 50; default 10 */
+  int32_t max_trials;                     /* trials, <= 1000; default 2 * max_iter */
+  int32_t n_fixed;                        /* leading slots held; default 2 */
+  int32_t reserved;
+  double huber_px;                        /* Huber threshold in pixels; 0 = squared loss */
+  double lambda0;                         /* default 1e-3 */
+  double step_tol;                        /* default 1e-10 */
+} vo_ba_params;
+typedef struct vo_ba_result {
+  int32_t status;                         /* 0 converged, 1 max_iter, 2 max_trials, 3 lambda beyond 1e12, 4 refused */
+  int32_t iterations, trials;             /* accepted steps; trials counted */
+  int32_t n_obs;                          /* M */
+  double cost0, cost;                     /* at the start, at the result */
+  double lambda;                          /* as the solve left it */
+} vo_ba_result;
+size_t vo_window_ba_workspace_bytes(int S, int W, int L_cap, int M_cap);
+int vo_window_ba_dev(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const int32_t* d_counts, const double* d_K, double* d_poses,
+                     double* d_X, const int32_t* d_lm_start, const int32_t* d_obs_slot, const double* d_obs_xy,
+                     const vo_ba_params* prm /* NULL: defaults */, vo_ba_result* d_results);
+int vo_window_ba(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const int32_t* counts, const double* K, double* poses, double* X,
+                 const int32_t* lm_start, const int32_t* obs_slot, const double* obs_xy, const vo_ba_params* prm,
+                 vo_ba_result* results);
+/* The window of W observation records exactly as vo_pipeline_export_tracks_post_seq wrote them (d_records: a HOST array of W
+ * device pointers, oldest first; rows beyond `cap` of a record are ignored), built on the device, no host turn:
+ *   landmarks     the rows of the newest record with state == 2 and finite X, Y, Z whose id occurs in at least one other
+ *                 record of the window, in row order; the first L_cap of them.  d_X: that row's X, Y, Z; d_lm_id: its id.
+ *   observations  per landmark, for each slot in ascending order in which its id occurs (any state: it is the same image
+ *                 track; the first row carrying the id), (slot, (double)x, (double)y).
+ *   d_head        int32 {L, M, flags, 0}; flags: 1 when the first landmark left out was left out for L_cap, 2 when for M_cap
+ *                 (the list ends at the last landmark whose observations fit wholly), 0 when none was.  d_lm_start[L] = M.
+ * The join compares ids and copies; nothing is rounded.  The poses of the window are the caller's (vo_step_result).  Enqueued
+ * on the context's stream (order it behind the records with vo_pipeline_export_state_join when that is another stream).  */
+int vo_window_from_tracks_dev(vo_ctx* ctx, int W, const void* const* d_records, int cap, int L_cap, int M_cap, int32_t* d_head,
+                              int32_t* d_lm_start, int32_t* d_obs_slot, double* d_obs_xy, double* d_X, int32_t* d_lm_id);
+/* The one write of a back end into a pipeline: the features of sequence seq whose track id is d_ids[k] (device, n of them; the
+ * first k for an id given twice) AND whose state is 2 take the landmark d_X[3 k ..] (device); every other byte of the state,
+ * the poses included, stays as it was.  Nothing may be in flight; needs vo_pipeline_config.track_ids (VO_EINVAL naming it).
+ * Enqueued on the pipeline's stream; synchronises.                                                                      */
+int vo_pipeline_update_landmarks_seq(vo_pipeline* p, int seq, int n, const int32_t* d_ids, const double* d_X);
 
 /* ---- shared map over RCCL ------------------------------------------------------------------
  * The reference is one process and one thread (README.md:49); frame streams shard at sequence granularity (one

@@ -46,6 +46,22 @@ __global__ __launch_bounds__(256) void export_tracks_kernel(vo_feat F, const vo_
   for (int k = 0; k < 3; ++k) row[3 + k] = (unsigned long long)__double_as_longlong(st == 2 ? X[k] : vo_state_dev::dnan());
 }
 
+// vo_pipeline_update_landmarks_seq: feature i of the sequence takes X[3 k ..] when its id is ids[k] (the first such k) and its
+// state is 2; nothing else is written
+__global__ __launch_bounds__(256) void update_landmarks_kernel(vo_feat F, const vo_seq_ctl* __restrict__ ctl, int cap, int n_list,
+                                                               const int32_t* __restrict__ ids, const double* __restrict__ X) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= min(ctl->n, cap) || F.state[i] != 2) return;
+  const int id = F.ids[i].x;
+  for (int k = 0; k < n_list; ++k) {
+    if (ids[k] != id) continue;
+    F.land[3 * i] = X[3 * k];
+    F.land[3 * i + 1] = X[3 * k + 1];
+    F.land[3 * i + 2] = X[3 * k + 2];
+    return;
+  }
+}
+
 // vo_pipeline_rewind: the control block as it was at the checkpoint, except what lives on the reference's estimator
 // object (RANSAC.n_iterations / outlier_ratio, ransac.py:47-56) and the generator position, which go on
 __global__ __launch_bounds__(64) void ctl_rewind_kernel(vo_seq_ctl* __restrict__ ctl, const vo_seq_ctl* __restrict__ saved, int S,
@@ -634,6 +650,24 @@ int vo_pipeline_export_tracks_post_seq(vo_pipeline* p, int seq, const vo_step_re
                        (int)((p->last_k + 1) & 1), n, cap, seq, (unsigned long long*)d_record);
   }
   return vo_check_launch(ctx, "export_tracks_kernel");
+}
+
+int vo_pipeline_update_landmarks_seq(vo_pipeline* p, int seq, int n, const int32_t* d_ids, const double* d_X) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_TRY(check_track_ids(p, "pipeline_update_landmarks", seq, true));
+  VO_REQUIRE(ctx, p->have_state, "pipeline_update_landmarks: no state was handed over");
+  VO_REQUIRE(ctx, n >= 0 && (n == 0 || (d_ids && d_X)), "pipeline_update_landmarks: bad arguments");
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (n > 0) {
+    vo_prof_scope ps(ctx, VO_K_EXPORT);
+    hipLaunchKernelGGL(update_landmarks_kernel, dim3(vo_cdiv(p->cap, 256)), dim3(256), 0, st, vo_feat_seq(p->F[p->cur], (size_t)seq),
+                       (const vo_seq_ctl*)(p->d_ctl + seq), p->cap, n, d_ids, d_X);
+    VO_TRY(vo_check_launch(ctx, "update_landmarks_kernel"));
+  }
+  VO_HIP_TRY(ctx, hipStreamSynchronize(st));
+  return VO_OK;
 }
 
 int vo_pipeline_export_state_post(vo_pipeline* p, const vo_step_result* r, int cap, double* d_record) {

@@ -118,7 +118,7 @@ void vo_destroy(vo_ctx* c) {
                    &c->nms_keys_a1, &c->nms_idx_a1, &c->nms_keys_c, &c->nms_idx_c, &c->nms_hist,
                    &c->nms_ctl, &c->nms_sel, &c->nms_cand, &c->nms_alive, &c->nms_segcnt, &c->nms_rank, &c->sift_arena,
                    &c->match_arrived, &c->f8_ctl, &c->f8_raws, &c->f8_F, &c->f8_counts, &c->f8_risky, &c->f8_masks,
-                   &c->f8_table, &c->f8_samples};
+                   &c->f8_table, &c->f8_samples, &c->ba_work, &c->ba_match};
   for (vo_buf* b : all) free_buf(*b);
   for (vo_buf& b : c->scratch) free_buf(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -183,7 +183,7 @@ static const char* const k_names[VO_K_COUNT] = {
     "harris_response", "nms_candidates", "nms_threshold", "nms_compact", "nms_select",
     "patch_descriptors", "pyr_down", "klt_track", "dlt_triangulate", "p3p_solve",
     "p3p_score", "reproj_inliers", "match_knn2", "track_gather", "nms_round", "nms_collect", "nms_rank", "nms_emit", "sift_scale_space", "sift_detect", "sift_describe", "refine_pose",
-    "state_candidates", "state_regroup", "ransac_replay", "state_landmarks", "export_state", "shi_tomasi_chain"};
+    "state_candidates", "state_regroup", "ransac_replay", "state_landmarks", "export_state", "shi_tomasi_chain", "window_ba", "window_build"};
 
 const char* vo_kernel_name(int k) {
   if (k < 0 || k >= VO_K_COUNT || !k_names[k]) return "";

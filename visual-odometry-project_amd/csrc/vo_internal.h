@@ -76,6 +76,8 @@ struct vo_ctx {
   vo_buf f8_ctl, f8_raws, f8_F, f8_counts, f8_risky, f8_masks, f8_table, f8_samples;
   std::vector<double> f8_table_host;
   double f8_table_conf = 0.0;
+  // window bundle adjustment (window_ba.hip): the solver's per-window workspace, the builder's row x slot match table
+  vo_buf ba_work, ba_match;
 };
 
 // a launch that takes vo_ctx::next_stop as its stop event when one is set (and clears it)

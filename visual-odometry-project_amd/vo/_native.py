@@ -122,6 +122,27 @@ class BootstrapResult(C.Structure):
         return np.array(self.M).reshape(3, 4)
 
 
+class BaParams(C.Structure):
+    """vo_ba_params: 0 in a field = its default (max_iter 10, max_trials 2 * max_iter, n_fixed 2, squared loss,
+    lambda0 1e-3, step_tol 1e-10)."""
+    _fields_ = [("max_iter", C.c_int32), ("max_trials", C.c_int32), ("n_fixed", C.c_int32), ("reserved", C.c_int32),
+                ("huber_px", C.c_double), ("lambda0", C.c_double), ("step_tol", C.c_double)]
+
+
+class BaResult(C.Structure):
+    """vo_ba_result.  status: 0 converged, 1 max_iter, 2 max_trials, 3 lambda beyond 1e12, 4 refused."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32), ("n_obs", C.c_int32),
+                ("cost0", C.c_double), ("cost", C.c_double), ("lam", C.c_double)]
+
+
+BA_RESULT = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("n_obs", "<i4"), ("cost0", "<f8"),
+                      ("cost", "<f8"), ("lam", "<f8")])       # the same 40 bytes as a NumPy row
+
+
+def ba_params(n_fixed=0, huber_px=0.0, max_iter=0, max_trials=0, lambda0=0.0, step_tol=0.0):
+    return BaParams(int(max_iter), int(max_trials), int(n_fixed), 0, float(huber_px), float(lambda0), float(step_tol))
+
+
 _vp, _i, _d, _sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
 _SIGS = {
     "vo_create": (_i, [_i, _vp, C.POINTER(_vp)]),
@@ -255,6 +276,11 @@ _SIGS = {
     "vo_pipeline_bootstrap": (_i, [_vp, _i, _i, _vp, _vp]),
     "vo_pipeline_bootstrap_lanes": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "vo_bootstrap_default_rng": (None, [_vp]),
+    "vo_window_ba_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "vo_window_ba_dev": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_window_ba": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_window_from_tracks_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_pipeline_update_landmarks_seq": (_i, [_vp, _i, _i, _vp, _vp]),
 }
 
 
@@ -488,6 +514,61 @@ class Context:
                                                   int(cap_q), C.c_void_p(d_t), int(t_stride), C.c_void_p(d_nt), int(nt_stride),
                                                   int(cap_t), int(S), float(ratio), C.c_void_p(d_pairs), C.c_void_p(d_npairs),
                                                   int(row_bytes)))
+
+    # ---- window bundle adjustment (csrc/window_ba.hip) ----
+    def window_ba(self, K, poses, X, lm_start, obs_slot, obs_xy, counts, n_fixed=0, huber_px=0.0, max_iter=0, max_trials=0,
+                  lambda0=0.0, step_tol=0.0):
+        """vo_window_ba on host arrays: S windows of W slots in strided arrays -- K (S, 3, 3) or (3, 3) for all, poses
+        (S, W, 12) world -> camera (R row-major, then t), X (S, L_cap, 3), lm_start (S, L_cap + 1), obs_slot (S, M_cap),
+        obs_xy (S, M_cap, 2), counts (S, 2) = each window's (L, M).  Returns (poses, X, results): the refined copies and a
+        (S,) record array (dtype BA_RESULT).  The parameters: 0 = the default of vo_ba_params."""
+        poses = np.array(poses, np.float64, order="C")
+        if poses.ndim != 3 or poses.shape[2] != 12:
+            raise ValueError("window_ba: poses must be (S, W, 12), got %s" % (poses.shape,))
+        S, W = poses.shape[:2]
+        X = np.array(X, np.float64, order="C")
+        lm_start, obs_slot = _c(lm_start, np.int32), _c(obs_slot, np.int32)
+        obs_xy = _c(obs_xy, np.float64)
+        if X.ndim != 3 or X.shape[0] != S or X.shape[2] != 3 or X.shape[1] < 1:
+            raise ValueError("window_ba: X must be (S, L_cap >= 1, 3), got %s" % (X.shape,))
+        L_cap = X.shape[1]
+        if lm_start.shape != (S, L_cap + 1):
+            raise ValueError("window_ba: lm_start must be (S, L_cap + 1) = %s, got %s" % ((S, L_cap + 1), lm_start.shape))
+        if obs_slot.ndim != 2 or obs_slot.shape[0] != S or obs_slot.shape[1] < 1 or obs_xy.shape != obs_slot.shape + (2,):
+            raise ValueError("window_ba: obs_slot must be (S, M_cap >= 1) and obs_xy (S, M_cap, 2), got %s and %s"
+                             % (obs_slot.shape, obs_xy.shape))
+        M_cap = obs_slot.shape[1]
+        K = np.asarray(K, np.float64)
+        K = _c(np.broadcast_to(K.reshape(-1, 3, 3), (S, 3, 3)) if K.size == 9 else K.reshape(S, 3, 3), np.float64)
+        cnt = np.zeros((S, 4), np.int32)
+        cnt[:, :2] = np.asarray(counts).reshape(S, -1)[:, :2]
+        prm = ba_params(n_fixed, huber_px, max_iter, max_trials, lambda0, step_tol)
+        res = np.zeros(S, BA_RESULT)
+        self._chk(self._lib.vo_window_ba(self._h, S, W, L_cap, M_cap, _ptr(cnt), _ptr(K), _ptr(poses), _ptr(X), _ptr(lm_start),
+                                         _ptr(obs_slot), _ptr(obs_xy), C.byref(prm), _ptr(res)))
+        return poses, X, res
+
+    def window_ba_dev(self, S, W, L_cap, M_cap, d_counts, d_K, d_poses, d_X, d_lm_start, d_obs_slot, d_obs_xy, d_results,
+                      **params):
+        """vo_window_ba_dev on device pointers (alloc / to_device), enqueued on the context's stream: S windows solved in
+        place, one BA_RESULT row each at d_results.  params: ba_params' keywords."""
+        prm = ba_params(**params)
+        self._chk(self._lib.vo_window_ba_dev(self._h, int(S), int(W), int(L_cap), int(M_cap), C.c_void_p(d_counts),
+                                             C.c_void_p(d_K), C.c_void_p(d_poses), C.c_void_p(d_X), C.c_void_p(d_lm_start),
+                                             C.c_void_p(d_obs_slot), C.c_void_p(d_obs_xy), C.byref(prm), C.c_void_p(d_results)))
+
+    def window_ba_workspace_bytes(self, S, W, L_cap, M_cap):
+        return int(self._lib.vo_window_ba_workspace_bytes(int(S), int(W), int(L_cap), int(M_cap)))
+
+    def window_from_tracks(self, d_records, cap, L_cap, M_cap, d_head, d_lm_start, d_obs_slot, d_obs_xy, d_X, d_lm_id):
+        """vo_window_from_tracks_dev: the window of the W = len(d_records) observation records (device pointers, oldest
+        first, as Pipeline.export_tracks_post wrote them with capacity `cap`) into device arrays -- d_head 4 int32
+        {L, M, flags, 0}, d_lm_start L_cap + 1 int32, d_obs_slot M_cap int32, d_obs_xy 2 M_cap float64, d_X 3 L_cap float64,
+        d_lm_id L_cap int32.  Enqueued on the context's stream."""
+        recs = (C.c_void_p * len(d_records))(*[int(d) for d in d_records])
+        self._chk(self._lib.vo_window_from_tracks_dev(self._h, len(d_records), recs, int(cap), int(L_cap), int(M_cap),
+                                                      C.c_void_p(d_head), C.c_void_p(d_lm_start), C.c_void_p(d_obs_slot),
+                                                      C.c_void_p(d_obs_xy), C.c_void_p(d_X), C.c_void_p(d_lm_id)))
 
     # ---- frame ingest (csrc/ingest.hip) ----
     def gray_from_bgr(self, bgr):

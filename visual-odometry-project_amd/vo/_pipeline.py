@@ -364,6 +364,26 @@ class Pipeline:
         writes it) and returns it as a TrackRecord: a structured array of its min(n, cap) rows, the header as attributes."""
         return TrackRecord.from_bytes(self.ctx.download(d_record, (self.tracks_record_bytes(cap),), np.uint8), cap)
 
+    def update_landmarks(self, ids, X, seq=0, n=None):
+        """The features of sequence `seq` whose track id is in `ids` and whose state is 2 take the landmark of the same row
+        of X; everything else stays (vo_pipeline_update_landmarks_seq; track_ids=True, nothing in flight).  ids / X: host
+        arrays ((n,) and (n, 3)), or two device pointers with n given."""
+        if n is not None:
+            self.ctx._chk(self.ctx._lib.vo_pipeline_update_landmarks_seq(self._h, int(seq), int(n), C.c_void_p(ids),
+                                                                         C.c_void_p(X)))
+            return
+        ids = _c(np.asarray(ids).reshape(-1), np.int32)
+        X = _c(np.asarray(X, np.float64).reshape(-1, 3), np.float64)
+        if len(X) != ids.size:
+            raise ValueError("update_landmarks: %d landmarks for %d ids" % (len(X), ids.size))
+        d_ids, d_X = self.ctx.to_device(ids), self.ctx.to_device(X)
+        try:
+            self.ctx._chk(self.ctx._lib.vo_pipeline_update_landmarks_seq(self._h, int(seq), ids.size, C.c_void_p(d_ids),
+                                                                         C.c_void_p(d_X)))
+        finally:
+            self.ctx.free(d_ids)
+            self.ctx.free(d_X)
+
     def get_detection(self, seq=0):
         """The detector's keypoints of the frame submitted last, sequence `seq`: (n, 2) float64 -- n_keypoints rows with
         the Harris detector, the frame's corner count with Shi-Tomasi (nothing in flight)."""

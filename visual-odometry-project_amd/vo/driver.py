@@ -144,6 +144,52 @@ class _TrackTap:
         self.side.close()
 
 
+class _BaTap:
+    """The window bundle adjustment behind the collected steps: every lane keeps its last `window` observation records in
+    device buffers of its own (posted like the tap's, behind the step in flight) and the refined poses of their frames; once
+    a lane holds a full window, the windows of all such lanes go through one solver call per step
+    (vo.landmarks.solve_windows)."""
+
+    def __init__(self, ctx, pipe, lanes, window, params):
+        self.ctx, self.pipe, self.window, self.params = ctx, pipe, int(window), params
+        nbytes = pipe.tracks_record_bytes(pipe.cap)
+        self.ring = [[ctx.alloc(nbytes) for _ in range(self.window)] for _ in range(lanes)]
+        self.turn = [0] * lanes
+        self.adj = [None] * lanes
+
+    def start(self, lane, K):
+        from vo.landmarks import WindowBundleAdjuster
+        if self.adj[lane]:
+            self.adj[lane].close()
+        self.adj[lane] = WindowBundleAdjuster(K, window=self.window, cap=self.pipe.cap, context=self.ctx, **self.params)
+
+    def step(self, items, feedback):
+        """items: (lane, the step's StepResult, the list its `ba` entries go to) of the step collected just now."""
+        from vo.landmarks import solve_windows
+        for lane, r, _ in items:
+            d_rec = self.ring[lane][self.turn[lane]]
+            self.turn[lane] = (self.turn[lane] + 1) % self.window
+            self.pipe.export_tracks_post(r, self.pipe.cap, d_rec, seq=lane)
+            self.adj[lane].push(d_rec, np.concatenate((np.array(r.R_refined), np.array(r.t_refined))))
+        solved = solve_windows([self.adj[lane] for lane, _, _ in items])
+        for (lane, _, sink), s in zip(items, solved):
+            if s is None:
+                continue
+            sink.append(dict(frames=s.steps, poses=s.poses, ids=s.ids, landmarks=s.landmarks, status=int(s.result["status"]),
+                             cost0=float(s.result["cost0"]), cost=float(s.result["cost"]),
+                             iterations=int(s.result["iterations"])))
+            if feedback and s.n and int(s.result["status"]) != 4:
+                self.pipe.update_landmarks(s.d_ids, s.d_X, seq=lane, n=s.n)
+
+    def close(self):
+        for a in self.adj:
+            if a:
+                a.close()
+        for row in self.ring:
+            for d in row:
+                self.ctx.free(d)
+
+
 def track_table(observations):
     """What a back end ingests from the per-step observation records (run_on_device(..., tracks=True)["observations"]):
     {id: dict(steps=(m,) int indices into `observations`, keypoints=(m, 2) float32, born=int, landmark=(3,) float64 -- the
@@ -167,7 +213,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
                   klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                   redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                   bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
-                  tracks: bool = False):
+                  tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None):
     """Same loop, same bootstrap, but the steady state runs as the device-resident pipeline (vo_pipeline_*):
     after the host bootstrap the Features / State arrays are handed to the GPU once, every later frame costs one
     image upload and one call, and nothing but the pose record comes back.  KLT tracker mode with the Harris
@@ -190,6 +236,15 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     tracks: the pipeline keeps persistent track ids (Pipeline(track_ids=True)) and the result gains `observations`, one
     TrackRecord per step (id, born, keypoint, state, candidate, landmark of every feature; track_table() turns them into
     per-track observations) -- each posted behind its step and read back one collect later, so the look-ahead stays.
+    ba_window: W (2 .. 16; needs tracks=True) -- a sliding-window bundle adjustment (vo.landmarks.WindowBundleAdjuster,
+    vo_window_ba_dev) runs behind every collected step once W consecutive records exist, over the last W refined poses and
+    the landmarks their records share; the result gains `ba`, one dict per solved window: frames (the records' step
+    counters), poses (W, 12) world -> camera, ids, landmarks, status, cost0, cost, iterations.  The pipeline's own poses are
+    never moved.  The solve is queued on the pipeline's stream and read back at once, so a collect then waits for the step
+    in flight.  ba_params: WindowBundleAdjuster's n_fixed / huber_px / max_iter.  ba_feedback: the refined landmarks go
+    back into the pipeline (Pipeline.update_landmarks) between steps; that needs nothing in flight, so every step is
+    collected before the next is submitted: the look-ahead of one step is given up.  ba_window=None (the default): nothing
+    of this exists and the loop is the one it was.
 
     This is run_batch_on_device([sequence], lanes=1, ...)[0], the same loop (_DeviceRun) with one lane, and what comes
     with that: the lane's camera is set once more at the start (Pipeline.set_camera with the constructor's K, so the
@@ -200,11 +255,14 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     (reading / decoding / rendering inside next() is the sequence's time, not the loop's)."""
     run = _DeviceRun([sequence], 1, max_frames, context, bootstrap, tracks,
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
-                     (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector))
+                     (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
+                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params)
     out = run.run()[0]
     out["frame_seconds"] = out["frame_seconds"] - np.array(run.read_seconds)
     if tracks:
         out.setdefault("observations", [])
+    if ba_window is not None:
+        out.setdefault("ba", [])
     if verbose:
         for r in out["results"]:
             print("%4d in, %4d tracked, %4d landmarks, %4d inliers, %3d candidates%s" % (
@@ -365,8 +423,13 @@ class _DeviceRun:
     boot_args: _device_bootstrap's / _bootstrap_kwargs' arguments, pipe_args: _pipeline_kwargs' after the state."""
     SLOTS = 4
 
-    def __init__(self, sequences, lanes, max_frames, context, bootstrap, tracks, boot_args, pipe_args):
+    def __init__(self, sequences, lanes, max_frames, context, bootstrap, tracks, boot_args, pipe_args, ba_window=None,
+                 ba_feedback=False, ba_params=None):
         _check_bootstrap_route(bootstrap)
+        if ba_window is not None and not tracks:
+            raise ValueError("ba_window needs tracks=True: the window is built from the observation records")
+        self.ba_window, self.ba_feedback, self.ba_params = ba_window, bool(ba_feedback), dict(ba_params or {})
+        self.ba = None                                   # lane -> its WindowBundleAdjuster (open_pipeline)
         self.sequences = sequences = list(sequences)
         self.on_device, self.context, self.tracks = bootstrap == "device", context, tracks
         self.boot_args, self.pipe_args = boot_args, pipe_args
@@ -417,6 +480,8 @@ class _DeviceRun:
         self.pipe = _native.Pipeline(self.ctx, H, W, self.SLOTS, self.camera_of(self.first), sequences=self.lanes,
                                      track_ids=self.tracks, **_pipeline_kwargs(state0, *self.pipe_args))
         self.tap = _TrackTap(self.ctx, self.pipe, self.lanes) if self.tracks else None
+        if self.ba_window is not None:
+            self.ba = _BaTap(self.ctx, self.pipe, self.lanes, self.ba_window, self.ba_params)
         self.ring = [[None] * self.SLOTS for _ in range(self.lanes)]
 
     def set_camera(self, lane, r):
@@ -478,6 +543,9 @@ class _DeviceRun:
             o["results"].append(r)                       # (run() reads the poses and counts out of them after the loop)
         if self.tap:
             self.tap.post([(lane, r, o.setdefault("observations", [])) for lane, r, o in taken])
+        if self.ba:
+            self.ba.step([(lane, r, o.setdefault("ba", [])) for lane, r, o in taken],
+                         feedback=self.ba_feedback and not self.pending)
 
     def change(self, t):
         """Step t's events -- lanes going idle, lanes starting a recording (the host route one by one, the device route
@@ -494,6 +562,9 @@ class _DeviceRun:
                 if prev is not None:
                     self.finish(lane, prev[0])
         starts = [(lane, r) for lane, r in events if r is not None]
+        if self.ba:
+            for lane, r in starts:
+                self.ba.start(lane, self.camera_of(r))    # (a hand-over: ids start again, a window must not span it)
         for lane, r in events:
             if r is None:
                 self.pipe.set_active(lane, False)
@@ -513,8 +584,8 @@ class _DeviceRun:
         t0 = time.perf_counter()
         self.reading = 0.0
         nxt, after = (self.slot + 1) % self.SLOTS, (self.slot + 2) % self.SLOTS
-        if len(self.pending) == 2:
-            self.collect_one()
+        while self.pending and (len(self.pending) == 2 or self.ba_feedback):
+            self.collect_one()                           # (ba_feedback: nothing may be in flight when landmarks go back)
         ahead = []                                       # (lane, recording) of the lanes that keep theirs at step t + 1
         if t + 1 < len(self.steps):
             ahead = [(lane, e[0]) for lane, e in enumerate(self.steps[t + 1]) if e is not None and e[1] > 0]
@@ -546,6 +617,8 @@ class _DeviceRun:
                     self.finish(lane, e[0])
             if self.tap:
                 self.tap.close()
+            if self.ba:
+                self.ba.close()
             self.pipe.close()
         for o in self.out:
             o["trajectory"] = np.array(o["trajectory"] + [r.pose_world_cam() for r in o["results"]])
@@ -558,7 +631,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                         klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                         bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
-                        tracks: bool = False):
+                        tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
     (_device_bootstrap); when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
@@ -572,13 +645,19 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     recording without a steady-state step never holds a lane: host route.)  detector: as in run_on_device, for every lane.
     tracks: as in run_on_device -- every recording's dict gains `observations`, one record per step it took (a lane's ids
     start over with every recording: each start is a hand-over).
+    ba_window / ba_feedback / ba_params: as in run_on_device; the windows of all lanes that hold a full one go through one
+    solver call per step, and a lane's window starts again with every recording.
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
     each step the recording took part in, the delivery of the next step's frames included).  run_on_device is this
     function with one recording and one lane; each lane computes what it computes for the lane's recording alone."""
     out = _DeviceRun(sequences, lanes, max_frames, context, bootstrap, tracks,
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
-                     (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector)).run()
+                     (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
+                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params).run()
+    if ba_window is not None:
+        for o in out:
+            o.setdefault("ba", [])
     if verbose:
         for o in out:
             print("%d steps, %d landmarks at the end" % (len(o["results"]), o["n_landmarks"][-1]))

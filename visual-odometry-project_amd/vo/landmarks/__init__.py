@@ -1,1 +1,2 @@
 from .triangulation import LandmarksTriangulator  # noqa: F401
+from .window_ba import WindowBundleAdjuster, pack_windows, solve_windows  # noqa: F401
