@@ -95,6 +95,8 @@ enum {
   VO_K_SHI_TOMASI_CHAIN = 27,   /* the frame loop's Shi-Tomasi re-detect, all of its launches (vo_pipeline_config.detector = 1) */
   VO_K_WINDOW_BA = 28,          /* vo_window_ba_dev's solver kernel */
   VO_K_WINDOW_BUILD = 29,       /* vo_window_from_tracks_dev, both of its launches */
+  VO_K_TWOVIEW_HYP = 30,        /* the two-view hypothesis kernel of a call: f8_hyp_kernel or e5_hyp_kernel */
+  VO_K_TWOVIEW_SCORE = 31,      /* ... and its scorer: f_score_kernel or e5_score_kernel */
   VO_K_COUNT = 32
 };
 int vo_prof_enable(vo_ctx* ctx, int kernel_id);
@@ -427,6 +429,49 @@ int vo_fundamental_ransac(vo_ctx* ctx, const double* p1, const double* p2, int N
                           vo_pcg64* rng, double* F, uint8_t* inlier_mask, int64_t* iterations, int32_t* best_count,
                           int32_t* finished_by_host);
 int vo_rng_raw32_device(vo_ctx* ctx, vo_pcg64* rng, int count, uint32_t* out);
+/* ---- calibrated two-view bootstrap (essential5.hip) ----
+ * [ref: src/vo/landmarks/triangulation.py:224-243, _find_essential_matrix]  The reference reaches E through the 8-point F,
+ * E = K2^T F K1.  These two reach it from the calibration directly: the five-point minimal solver (Nister 2004) inside the
+ * reference's RANSAC loop (src/vo/algorithms/ransac.py:69-129, s = 5).  K1, K2: 3x3 row-major pinhole matrices (HOST
+ * pointers); their inverses are formed in closed form from fx, fy, cx, cy, a skew entry is not read.
+ * vo_essential_hypotheses: for each of Hyp samples (samples: Hyp*5 indices into the N correspondences x1, x2, N*2 pixels
+ *   each) every real essential matrix consistent with its five correspondences:
+ *     1. x^ = K^-1 (x, y, 1) in both images
+ *     2. the rows kron(x^1, x^2) (the reference's row convention, :203-205) of the 5x9 system; Householder QR of its
+ *        transpose; the last four columns of the orthogonal factor span the null space: E = x X + y Y + z Z + W with
+ *        E[b][a] = e[3a + b].  A column norm below 1e-10 of the largest: the null space is not four-dimensional (a repeated
+ *        correspondence), n_sol = 0
+ *     3. det E = 0 and 2 E E^T E - tr(E E^T) E = 0: a 10x20 matrix over the monomials of (x, y, z)
+ *     4. Gauss-Jordan elimination with partial pivoting; a pivot below 1e-12 of the matrix's largest entry: n_sol = 0
+ *     5. the degree-10 polynomial in z (the determinant of Nister's 3x3 polynomial matrix); a leading coefficient below
+ *        1e-13 of the largest coefficient: n_sol = 0
+ *     6. every real root: isolated between the real roots of the derivative (from the ninth derivative down, inside the
+ *        Cauchy bound), 40 bisection steps on a derivative, 64 bisection and 4 safeguarded Newton steps on the polynomial
+ *     7. x, y from the two rows of the polynomial matrix at z whose cross product has the largest third component
+ *     8. unit Frobenius norm, the entry of largest magnitude positive (the first in row-major order on ties)
+ *   E: Hyp*10*9, the n_sol[h] matrices of sample h in ascending z, the rows behind them zero; never a NaN or Inf.
+ *   Every solution is scored as the fundamental matrix F = K2^-T E K1^-1 over all N correspondences in pixels with the
+ *   arithmetic of vo_fundamental_hypotheses (error_kind 0: (p2^T F p1)^2; 1: the larger squared distance to the two
+ *   epipolar lines; inlier = error < threshold): counts Hyp*10 (an absent solution: 0), masks Hyp*10*ceil(N/64) words
+ *   (nullable; an absent solution's row is empty), best_sol Hyp: the lowest index among the sample's solutions with the
+ *   largest count, -1 when it has none.
+ * vo_essential_ransac: the loop of ransac.py:69-129 with s = 5, composed on the host: samples are drawn ahead from a copy of
+ *   *rng by vo_rng_choice(rng, N, 5, 2048) in batches of 2048; hypotheses and scores are made on the device; per batch only
+ *   valid = (n_sol > 0), the best count and the best solution index of every sample come back (9 bytes per sample);
+ *   vo_ransac_replay with s = 5 walks the accept / adapt rule over them (a sample without a solution is the reference's
+ *   "model is None"); *rng is advanced by the samples the loop consumed; only the accepted model's E (9) and its mask row
+ *   (inlier_mask, N bytes) are downloaded at the end.  There is NO closing fit: the result is the accepted minimal-sample
+ *   model (as cv2.findEssentialMat returns one).  iterations, best_count nullable.
+ *   VO_ETRACKING: as many samples as the loop's first bound (min(max_iterations, the bound of outlier_ratio)) were drawn
+ *   and none had a real solution; *rng stands behind them.
+ * Both: N < 5, a null pointer, a non-finite K (or fx, fy = 0), error_kind outside {0, 1}, a sample index outside [0, N),
+ *   an outlier ratio or confidence outside (0, 1), max_iterations = 0: VO_EINVAL, nothing written.                        */
+int vo_essential_hypotheses(vo_ctx* ctx, const double* x1, const double* x2, int N, const double* K1, const double* K2,
+                            const int32_t* samples, int Hyp, int error_kind, double threshold, double* E, int32_t* n_sol,
+                            int32_t* counts, int32_t* best_sol, uint64_t* masks);
+int vo_essential_ransac(vo_ctx* ctx, const double* x1, const double* x2, int N, const double* K1, const double* K2,
+                        int error_kind, double threshold, double outlier_ratio, double confidence, int64_t max_iterations,
+                        vo_pcg64* rng, double* E, uint8_t* inlier_mask, int64_t* iterations, int32_t* best_count);
 int64_t vo_ransac_num_iterations(double confidence, double outlier_ratio, int s);
 int vo_ransac_replay(vo_ransac_state* st, const uint8_t* valid, const int32_t* counts, int B,
                      int N, int64_t* n_done, int32_t* best_count, int32_t* best_idx,

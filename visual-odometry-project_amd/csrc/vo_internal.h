@@ -297,6 +297,27 @@ int vo_fundamental_ransac_dev(vo_ctx* ctx, const double* d_p1, const double* d_p
 int vo_relative_pose_lanes_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, const vo_f8_lanes& lanes, const uint8_t* d_inl,
                                const double* d_F, const double* d_cam, size_t cam_stride, const int32_t* d_seq, double* d_M,
                                double* d_X, size_t X_stride, uint8_t* d_mask_out);
+// Device-resident forms of the calibrated two-view bootstrap (essential5.hip): points in HBM, K1 / K2 host pointers (their
+// closed-form inverses travel as launch arguments).  The caller's device blocks of one batch of Hyp samples:
+struct vo_e5_work {
+  int32_t* samples = nullptr;   // Hyp x 5
+  double* E = nullptr;          // Hyp x 10 x 9
+  double* F = nullptr;          // Hyp x 10 x 9: K2^-T E K1^-1, what the scorer reads
+  int32_t* n_sol = nullptr;     // Hyp
+  int32_t* counts = nullptr;    // Hyp x 10
+  uint64_t* masks = nullptr;    // Hyp x 10 x cdiv(N, 64) words (nullable)
+  int32_t* best = nullptr;      // 3 Hyp words: best counts (Hyp), best solution indices (Hyp), valid bytes (Hyp)
+};
+//   hypotheses: samples (host, Hyp x 5, checked against N) are the only array uploaded; best_count, best_sol (host, Hyp
+//   each) and valid (host, Hyp bytes), each nullable, the only ones downloaded: 9 bytes per sample.  Synchronises.
+int vo_essential_hypotheses_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, int N, const double* K1, const double* K2,
+                                const int32_t* samples, int Hyp, int error_kind, double threshold, const vo_e5_work& w,
+                                int32_t* best_count, int32_t* best_sol, uint8_t* valid);
+//   the loop: d_E 9 doubles, d_inl N bytes (the accepted model and its mask row); *rng advanced by what the loop consumed.
+//   Uses the context's scratch blocks 2 .. 8.  Synchronises.
+int vo_essential_ransac_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, int N, const double* K1, const double* K2,
+                            int error_kind, double threshold, double outlier_ratio, double confidence, int64_t max_iterations,
+                            vo_pcg64* rng, double* d_E, uint8_t* d_inl, int64_t* iterations, int32_t* best_count);
 // DLT with a device-resident point count (dlt.hip)
 int vo_triangulate_dlt_ndev(vo_ctx* ctx, const double* d_x1, const double* d_x2, const int32_t* d_n, int n_cap,
                             const double* d_C1, const double* d_C2, double* d_X);

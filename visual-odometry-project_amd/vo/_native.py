@@ -21,6 +21,7 @@ _CODES = {VO_EINVAL: "VO_EINVAL", VO_ENOMEM: "VO_ENOMEM", VO_EHIP: "VO_EHIP", VO
 K_HARRIS_RESPONSE, K_NMS_CANDIDATES, K_NMS_THRESHOLD, K_NMS_COMPACT, K_NMS_SELECT = 0, 1, 2, 3, 4
 K_PATCH_DESC, K_PYR_DOWN, K_KLT_TRACK, K_DLT, K_P3P_SOLVE, K_P3P_SCORE, K_REPROJ, K_MATCH = 5, 6, 7, 8, 9, 10, 11, 12
 K_SHI_TOMASI_CHAIN = 27
+K_TWOVIEW_HYP, K_TWOVIEW_SCORE = 30, 31      # f8_hyp_kernel / e5_hyp_kernel and f_score_kernel / e5_score_kernel
 K_COUNT = 32
 
 
@@ -206,6 +207,8 @@ _SIGS = {
     "vo_fundamental_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _d, _vp, _vp, _vp]),
     "vo_fundamental_fit": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "vo_fundamental_ransac": (_i, [_vp, _vp, _vp, _i, _i, _i, _d, _d, _d, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_essential_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "vo_essential_ransac": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _d, _d, _d, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "vo_rng_raw32_device": (_i, [_vp, _vp, _i, _vp]),
     "vo_rng_choice8_from_raw": (_i, [_vp, _i, _vp, _vp]),
     "vo_essential_decompose": (_i, [_vp, _vp, _vp]),
@@ -874,6 +877,58 @@ class Context:
             pcg.to_generator(rng)
         return F, mask.astype(bool), {"iterations": int(it.value), "best_count": int(best.value),
                                       "finished_by_host": int(host.value)}
+
+    # ---- calibrated two-view bootstrap ----
+    def essential_hypotheses(self, x1, x2, K1, K2, samples, threshold, error_kind=1, want_masks=False):
+        """Every real five-point E of every sample (samples (Hyp, 5)) and its inlier count over all correspondences, scored
+        as F = K2^-T E K1^-1 in pixels (vo_essential_hypotheses): (E (Hyp, 10, 3, 3), n_sol (Hyp,), counts (Hyp, 10),
+        best_sol (Hyp,)[, masks (Hyp, 10, N) bool]).  error_kind 0: (p2^T F p1)^2; 1: squared epipolar distance.
+        want_masks="packed": rows of 64-bit words (Context.unpack_mask(row, n) opens one)."""
+        x1 = _c(np.asarray(x1).reshape(-1, 2), np.float64)
+        x2 = _c(np.asarray(x2).reshape(-1, 2), np.float64)
+        K1 = _c(np.asarray(K1).reshape(3, 3), np.float64)
+        K2 = _c(np.asarray(K2).reshape(3, 3), np.float64)
+        samples = _c(np.asarray(samples).reshape(-1, 5), np.int32)
+        n, h = x1.shape[0], samples.shape[0]
+        E = np.empty((h, 10, 3, 3), np.float64)
+        n_sol = np.empty(h, np.int32)
+        counts = np.empty((h, 10), np.int32)
+        best_sol = np.empty(h, np.int32)
+        words = (n + 63) // 64
+        masks = np.empty((h, 10, words), np.uint64) if want_masks else None
+        self._chk(self._lib.vo_essential_hypotheses(self._h, _ptr(x1), _ptr(x2), n, _ptr(K1), _ptr(K2), _ptr(samples), h,
+                                                    int(error_kind), float(threshold), _ptr(E), _ptr(n_sol), _ptr(counts),
+                                                    _ptr(best_sol), _ptr(masks)))
+        if want_masks == "packed":
+            return E, n_sol, counts, best_sol, masks
+        if want_masks:
+            bits = np.unpackbits(masks.view(np.uint8).reshape(h, 10, words * 8), axis=2, bitorder="little")[:, :, :n]
+            return E, n_sol, counts, best_sol, bits.astype(bool)
+        return E, n_sol, counts, best_sol
+
+    def essential_ransac(self, x1, x2, K1, K2, threshold, rng, error_kind=1, outlier_ratio=0.9, confidence=0.999,
+                         max_iterations=2000):
+        """The five-point RANSAC loop in one call (vo_essential_ransac): (E (3, 3), inlier mask (N,) bool, info) with
+        info = {"iterations", "best_count"}; E is the accepted minimal-sample model, there is no closing fit.  rng: a Pcg64
+        (advanced in place by what the loop consumed) or a NumPy Generator (likewise).  max_iterations: None / np.inf =
+        unbounded."""
+        x1 = _c(np.asarray(x1).reshape(-1, 2), np.float64)
+        x2 = _c(np.asarray(x2).reshape(-1, 2), np.float64)
+        K1 = _c(np.asarray(K1).reshape(3, 3), np.float64)
+        K2 = _c(np.asarray(K2).reshape(3, 3), np.float64)
+        n = x1.shape[0]
+        pcg = rng if isinstance(rng, Pcg64) else Pcg64.from_generator(rng)
+        budget = -1 if max_iterations is None or max_iterations == np.inf else int(max_iterations)
+        E = np.empty((3, 3), np.float64)
+        mask = np.zeros(n, np.uint8)
+        it, best = C.c_int64(0), C.c_int32(0)
+        rc = self._lib.vo_essential_ransac(self._h, _ptr(x1), _ptr(x2), n, _ptr(K1), _ptr(K2), int(error_kind), float(threshold),
+                                           float(outlier_ratio), float(confidence), budget, C.byref(pcg), _ptr(E), _ptr(mask),
+                                           C.byref(it), C.byref(best))
+        if not isinstance(rng, Pcg64) and rc != VO_EINVAL:
+            pcg.to_generator(rng)
+        self._chk(rc)
+        return E, mask.astype(bool), {"iterations": int(it.value), "best_count": int(best.value)}
 
     def rng_raw32_device(self, pcg, count):
         """The next `count` 32-bit outputs of `pcg` (a Pcg64, advanced in place) made by the device's fill kernel."""

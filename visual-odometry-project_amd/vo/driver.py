@@ -23,22 +23,26 @@ from vo.pose_estimation import P3PPoseEstimator
 from vo.primitives import Features, Sequence, State
 
 
-def make_estimators(camera, ransac_threshold=0.25):
-    """The triangulator and pose estimator as src/main.py:185-201 configures them (ransac_threshold: 0.25 px there)."""
+def make_estimators(camera, ransac_threshold=0.25, bootstrap_method="8point"):
+    """The triangulator and pose estimator as src/main.py:185-201 configures them (ransac_threshold: 0.25 px there).
+    bootstrap_method: LandmarksTriangulator's `method` ("8point": the reference's route; "5point": the calibrated one)."""
     triangulator = LandmarksTriangulator(camera1=camera, camera2=camera, use_ransac=True, use_opencv=True,
-                                         outlier_ratio=0.9, ransac_threshold=ransac_threshold, ransac_confidence=0.999)
+                                         outlier_ratio=0.9, ransac_threshold=ransac_threshold, ransac_confidence=0.999,
+                                         method=bootstrap_method)
     pose_estimator = P3PPoseEstimator(use_opencv=True, intrinsic_matrix=camera.intrinsic_matrix,
                                       inlier_threshold=1.25, outlier_ratio=0.9, confidence=0.9999,
                                       nonlinear_refinement=True)
     return triangulator, pose_estimator
 
 
-def bootstrap(sequence: Sequence, tracker_mode: str = "klt", tracker_setup=None, ransac_threshold=0.25):
+def bootstrap(sequence: Sequence, tracker_mode: str = "klt", tracker_setup=None, ransac_threshold=0.25,
+              bootstrap_method: str = "8point"):
     """main.py:204-230: frames 0 and 2 -> (state, tracker, triangulator, pose_estimator).  The 8-point RANSAC's
     hypotheses, counts and closing fit, the essential-matrix decomposition and the cheirality votes run on the GPU
-    (csrc/bootstrap.hip); the host keeps the sequential accept rule and the bookkeeping classes."""
+    (csrc/bootstrap.hip); the host keeps the sequential accept rule and the bookkeeping classes.  bootstrap_method="5point":
+    the relative pose starts from the five-point essential-matrix RANSAC instead (csrc/essential5.hip)."""
     camera = sequence.get_camera()
-    triangulator, pose_estimator = make_estimators(camera, ransac_threshold)
+    triangulator, pose_estimator = make_estimators(camera, ransac_threshold, bootstrap_method)
     init_frame = next(sequence)
     state = State(init_frame)
     next(sequence)                                                       # frame 1 is skipped
@@ -63,10 +67,11 @@ def bootstrap(sequence: Sequence, tracker_mode: str = "klt", tracker_setup=None,
     return state, tracker, triangulator, pose_estimator
 
 
-def run(sequence: Sequence, tracker_mode: str = "klt", max_frames: int = None, verbose: bool = False):
+def run(sequence: Sequence, tracker_mode: str = "klt", max_frames: int = None, verbose: bool = False,
+        bootstrap_method: str = "8point"):
     """The reference's loop through the drop-in classes, one call per stage (host bookkeeping, host <-> device
     copies around every kernel).  Returns dict(trajectory (n, 4, 4) camera-to-world, n_landmarks, frame_seconds)."""
-    state, tracker, triangulator, pose_estimator = bootstrap(sequence, tracker_mode)
+    state, tracker, triangulator, pose_estimator = bootstrap(sequence, tracker_mode, bootstrap_method=bootstrap_method)
     trajectory = [np.eye(4), state.get_pose()]
     n_landmarks = [len(state.curr_frame.features.triangulated_inliers_landmarks)]
     seconds = []
@@ -213,7 +218,8 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
                   klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                   redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                   bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
-                  tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None):
+                  tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None,
+                  bootstrap_method: str = "8point"):
     """Same loop, same bootstrap, but the steady state runs as the device-resident pipeline (vo_pipeline_*):
     after the host bootstrap the Features / State arrays are handed to the GPU once, every later frame costs one
     image upload and one call, and nothing but the pose record comes back.  KLT tracker mode with the Harris
@@ -233,6 +239,9 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     Frames are uploaded as the sequence delivers them, grey or B, G, R; the pipeline's ingest makes them grey on the device.
     A camera with distortion_coeffs sets the lane's distortion (Pipeline.set_distortion: every frame is undistorted into
     the pinhole camera K behind its upload); one that really distorts needs bootstrap="device".
+    bootstrap_method: the host route's two-view solver, LandmarksTriangulator's `method` -- "8point" (the reference's) or
+    "5point" (the calibrated five-point RANSAC); the pipeline's own bootstrap is the 8-point one, so "5point" together with
+    bootstrap="device" is refused.
     tracks: the pipeline keeps persistent track ids (Pipeline(track_ids=True)) and the result gains `observations`, one
     TrackRecord per step (id, born, keypoint, state, candidate, landmark of every feature; track_table() turns them into
     per-track observations) -- each posted behind its step and read back one collect later, so the look-ahead stays.
@@ -256,7 +265,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     run = _DeviceRun([sequence], 1, max_frames, context, bootstrap, tracks,
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
                      (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
-                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params)
+                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method)
     out = run.run()[0]
     out["frame_seconds"] = out["frame_seconds"] - np.array(run.read_seconds)
     if tracks:
@@ -271,7 +280,8 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     return out
 
 
-def _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold):
+def _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold,
+                      bootstrap_method="8point"):
     """The host bootstrap (main.py:204-230) of a recording the device-resident pipeline goes on with: (state, tracker)."""
     from vo.features.klt import KLTTracker
     saved = (dict(KLTTracker._feature_params), dict(KLTTracker._lk_params))
@@ -287,15 +297,21 @@ def _device_bootstrap(sequence, n_keypoints, klt_win, klt_max_level, bootstrap_w
                                      maxLevel=klt_max_level if bootstrap_max_level is None else bootstrap_max_level)
 
     try:
-        state, tracker, _, _ = bootstrap(sequence, "klt", tracker_setup=setup, ransac_threshold=bootstrap_threshold)
+        state, tracker, _, _ = bootstrap(sequence, "klt", tracker_setup=setup, ransac_threshold=bootstrap_threshold,
+                                         bootstrap_method=bootstrap_method)
     finally:
         KLTTracker._feature_params, KLTTracker._lk_params = saved
     return state, tracker
 
 
-def _check_bootstrap_route(bootstrap):
+def _check_bootstrap_route(bootstrap, bootstrap_method="8point"):
     if bootstrap not in ("host", "device"):
         raise ValueError("bootstrap must be 'host' or 'device', not %r" % (bootstrap,))
+    if bootstrap_method not in ("8point", "5point"):
+        raise ValueError("bootstrap_method must be '8point' or '5point', not %r" % (bootstrap_method,))
+    if bootstrap == "device" and bootstrap_method != "8point":
+        raise ValueError("bootstrap_method=%r needs bootstrap='host': the pipeline's device bootstrap is the 8-point one"
+                         % (bootstrap_method,))
 
 
 def _bootstrap_frames(sequence):
@@ -424,8 +440,9 @@ class _DeviceRun:
     SLOTS = 4
 
     def __init__(self, sequences, lanes, max_frames, context, bootstrap, tracks, boot_args, pipe_args, ba_window=None,
-                 ba_feedback=False, ba_params=None):
-        _check_bootstrap_route(bootstrap)
+                 ba_feedback=False, ba_params=None, bootstrap_method="8point"):
+        _check_bootstrap_route(bootstrap, bootstrap_method)
+        self.bootstrap_method = bootstrap_method
         if ba_window is not None and not tracks:
             raise ValueError("ba_window needs tracks=True: the window is built from the observation records")
         self.ba_window, self.ba_feedback, self.ba_params = ba_window, bool(ba_feedback), dict(ba_params or {})
@@ -460,7 +477,9 @@ class _DeviceRun:
 
     def boot_of(self, r):
         if r not in self.boot:
-            self.boot[r] = _device_bootstrap(self.sequences[r], *self.boot_args)
+            # (the default route keeps the call it always made)
+            extra = {} if self.bootstrap_method == "8point" else {"bootstrap_method": self.bootstrap_method}
+            self.boot[r] = _device_bootstrap(self.sequences[r], *self.boot_args, **extra)
         return self.boot[r]
 
     def open_result(self, r):
@@ -631,7 +650,8 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                         klt_max_level: int = 2, hyp: int = 4000, context=None, verbose: bool = False,
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                         bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
-                        tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None):
+                        tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None,
+                        bootstrap_method: str = "8point"):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
     (_device_bootstrap); when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
@@ -647,6 +667,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     start over with every recording: each start is a hand-over).
     ba_window / ba_feedback / ba_params: as in run_on_device; the windows of all lanes that hold a full one go through one
     solver call per step, and a lane's window starts again with every recording.
+    bootstrap_method: as in run_on_device, for every recording's host bootstrap.
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
     each step the recording took part in, the delivery of the next step's frames included).  run_on_device is this
@@ -654,7 +675,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     out = _DeviceRun(sequences, lanes, max_frames, context, bootstrap, tracks,
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
                      (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
-                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params).run()
+                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method).run()
     if ba_window is not None:
         for o in out:
             o.setdefault("ba", [])

@@ -7,7 +7,9 @@ inliers, and E decomposition + the four cheirality votes + the final triangulati
 kernel; the host keeps the reference's sequential accept / adapt rule over the counts and
 its generator.  `use_opencv` is accepted for signature compatibility; both values run
 these routines (the reference's cv2.findFundamentalMat / cv2.triangulatePoints have no
-counterpart here)."""
+counterpart here).  `method="5point"` (not in the reference) starts the bootstrap from the
+five-point essential-matrix RANSAC instead (csrc/essential5.hip); the default is the
+reference's 8-point route, unchanged."""
 import numpy as np
 
 from vo import _native
@@ -20,7 +22,10 @@ from vo.sensors import Camera
 class LandmarksTriangulator:
     def __init__(self, camera1: Camera, camera2: Camera, use_ransac: bool = True, outlier_ratio: float = 0.9,
                  ransac_threshold: float = 3.0, ransac_confidence=0.99, use_opencv: bool = True,
-                 context=None) -> None:
+                 context=None, method: str = "8point") -> None:
+        if method not in ("8point", "5point"):
+            raise ValueError("method must be '8point' or '5point', not %r" % (method,))
+        self._method = method
         self.camera1 = camera1
         self.camera2 = camera2
         self._use_ransac = use_ransac
@@ -111,12 +116,28 @@ class LandmarksTriangulator:
         return T2.T @ F @ T1, inliers
 
     def _find_essential_matrix(self, points1: np.ndarray, points2: np.ndarray):
-        """E = K2^T F K1 (triangulation.py:224-243)."""
+        """E = K2^T F K1 (triangulation.py:224-243); method="5point": E from the five-point RANSAC (vo_essential_ransac),
+        with its inlier mask."""
         K1, K2 = self.camera1.intrinsic_matrix, self.camera2.intrinsic_matrix
+        if self._method == "5point":
+            return self._find_essential_matrix_5point(points1, points2)
         if self._use_ransac:
             F, inliers = self._find_fundamental_matrix_ransac(points1, points2)
             return K2.T @ F @ K1, inliers
         return K2.T @ self._find_fundamental_matrix(points1, points2) @ K1
+
+    def _find_essential_matrix_5point(self, points1: np.ndarray, points2: np.ndarray):
+        """The calibrated route: five-point hypotheses inside the reference's RANSAC loop (s = 5), the larger squared
+        distance to the two epipolar lines in pixels against ransac_threshold squared (the error of the 8-point route
+        above), at most 2000 iterations, no closing fit: (E, inlier mask).  The generator is the reference's
+        (np.random.default_rng(2023), ransac.py:52), new with every call like the RANSAC object of the 8-point route."""
+        K1 = np.asarray(self.camera1.intrinsic_matrix, np.float64)
+        K2 = np.asarray(self.camera2.intrinsic_matrix, np.float64)
+        E, inliers, _ = self._context().essential_ransac(points1, points2, K1, K2, self._ransac_reproj_threshold ** 2,
+                                                         np.random.default_rng(2023), error_kind=1,
+                                                         outlier_ratio=self._outlier_ratio,
+                                                         confidence=self._ransac_confidence, max_iterations=2000)
+        return E, inliers
 
     def _decompose_essential_matrix(self, E: np.ndarray) -> np.ndarray:
         """The four [R | +-T] candidates (triangulation.py:245-277); the same set as the reference's, in the order this
@@ -129,6 +150,12 @@ class LandmarksTriangulator:
         (vo_relative_pose) behind the fundamental matrix."""
         K1 = np.asarray(self.camera1.intrinsic_matrix, np.float64)
         K2 = np.asarray(self.camera2.intrinsic_matrix, np.float64)
+        if self._method == "5point":
+            # relative_pose forms E = K2^T F K1 itself: it is fed F = K2^-T E K1^-1
+            E, inliers = self._find_essential_matrix(points1, points2)
+            F = np.linalg.inv(K2).T @ E @ np.linalg.inv(K1)
+            M, X, mask, _ = self._context().relative_pose(points1, points2, K1, K2, F, inliers)
+            return M, X.reshape(-1, 3, 1), mask
         if self._use_ransac:
             F, inliers = self._find_fundamental_matrix_ransac(points1, points2)
         else:
