@@ -243,7 +243,31 @@ double vo_inlier_sum_sq_limit(double thr_sq);
  * minimiser itself (SciPy's default tolerances stop within ~1e-4 of it).  Outputs R (9,
  * row-major), t (3), the number of accepted steps and the final cost (sum of squared pixel
  * errors).  The _dev form takes Rt0 = R0 then t0 (12 doubles) and writes 14 doubles:
- * R, t, iterations, cost.                                                              */
+ * R, t, iterations, cost.
+ *
+ * The rule (tests/refine_reference.py states it in NumPy; the stand-alone kernel and the frame loop's pose kernel
+ * share one routine):
+ *   cost    e_i = x_i - proj(K, R X_i + t) over the active points (mask byte != 0; every non-zero byte means the
+ *           same; the coordinates of the others are never used);  cost = sum_i |e_i|^2.  No cheirality test: a point
+ *           behind the camera counts with its (finite) residual.
+ *   rows    with p = R X + t, a = fx / p_z, b = fy / p_z, c = -fx p_x / p_z^2, d = -fy p_y / p_z^2 the rows of
+ *           J = d proj / d (v, w) are  [a 0 c  c p_y  a p_z - c p_x  -a p_y]  and  [0 b d  d p_y - b p_z  -d p_x  b p_x].
+ *   sums    28 of them over the active points: the 21 entries of the upper triangle of A = sum J^T J (the entry (0,1) is
+ *           zero), the 6 of g = sum J^T e, and the cost.  Their order of summation is not part of the rule.
+ *   solve   A d = g by Gauss-Jordan elimination without pivoting, in the order of the rows; a pivot that is not
+ *           positive (NaN included) refuses the solve and ends the refinement with the pose it has.
+ *   step    d = (v, w):  T <- [Exp(w) | v] T,  i.e.  R <- E R,  t <- E t + v  with  E = I + A [w]x + B [w]x^2,
+ *           A = sin(th) / th, B = (1 - cos th) / th^2, th = |w|;  for th^2 < 1/16 both by their series in th^2 through
+ *           th^16 (nested, 1 - th^2/6 (1 - th^2/20 (...)) and 1/2 (1 - th^2/12 (1 - th^2/30 (...)))), sin and cos otherwise.
+ *   order   the start pose is evaluated.  Then, repeatedly: `max_iter` accepted steps -> stop;  solve (refused -> stop);
+ *           the trial pose is formed and the step tested, |d| <= 1e-9 (1 + |t_trial|) -> stop, the step is neither taken
+ *           nor evaluated;  the trial is evaluated;  unless cost_new <= cost -> stop, the previous pose and its cost stay
+ *           (a NaN cost rejects);  the trial is accepted and counted;  cost - cost_new <= 1e-16 cost -> stop.
+ *   result  the pose of the last accepted step (the start if none), the number of accepted steps, and the cost of
+ *           exactly that pose.
+ *   fewer than three active points (N = 0 and an all-zero mask included), or a start cost that is not finite: the pose
+ *           is returned unchanged bit for bit, iterations = 0, and the cost is the cost of the active points at the start
+ *           (0 for none, the non-finite value otherwise).                                                            */
 int vo_refine_pose(vo_ctx* ctx, const double* X, const double* x, int N, const double* K,
                    const uint8_t* inlier_mask, const double* R0, const double* t0, int max_iter,
                    double* R, double* t, int32_t* iterations, double* cost);

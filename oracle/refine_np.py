@@ -52,9 +52,11 @@ def refine_pose(X, x, K, R0, t0, max_iter=20, tol=1e-9):
     x = np.asarray(x, np.float64).reshape(-1, 2)
     R = np.array(R0, np.float64).reshape(3, 3)
     t = np.array(t0, np.float64).reshape(3)
-    if len(X) < 3:
+    if len(X) == 0:
         return R, t, 0, 0.0
     A, b, cost = normal_equations(X, x, K, R, t)
+    if len(X) < 3 or not np.isfinite(cost):     # the rule of include/vo_hip.h: the pose stays, the cost is the start's
+        return R, t, 0, cost
     it = 0
     while it < max_iter:
         try:

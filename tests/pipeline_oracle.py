@@ -125,6 +125,7 @@ class OracleLoop:
         f2 = matches.frame2.features
         X = np.ascontiguousarray(f2.triangulated_inliers_landmarks[:, :, 0], np.float64)
         x = np.ascontiguousarray(f2.triangulated_inliers_keypoints[:, :, 0], np.float64)
+        p3p_index = np.arange(f2.length)[f2.triangulate_inliers]     # (where the population sits among the new frame's features)
         rs = self.rs
         rs.model_fn = lambda idx: native.p3p_solve(X[np.asarray(idx).reshape(-1)], x[np.asarray(idx).reshape(-1)], K)
         rs.error_fn = lambda m, pop: native.reproj_errors(X, x, K, m[0], m[1])
@@ -149,7 +150,10 @@ class OracleLoop:
             st.update_with_world_landmarks(Xw.reshape(-1, 3, 1), cand)
         return dict(n_before=n_before,
                     n_tracked=f2.length, n_tri=len(X), R=R, t=np.asarray(t).reshape(3), R_ref=Rr,
-                    t_ref=np.asarray(tr).reshape(3), refine_iters=it, inliers=inl, n_inliers=int(inl.sum()),
+                    t_ref=np.asarray(tr).reshape(3), refine_iters=it, refine_cost=float(cost),
+                    refine_input=(X[inl], x[inl], K, R, np.asarray(t).reshape(3), self.cfg["refine"]),
+                    p3p_index=p3p_index,
+                    inliers=inl, n_inliers=int(inl.sum()),
                     draws=len(rs.trace) - n0, iters=rs.iterations_done, n_cand=n_cand, candidate_mask=cand,
                     n_landmarks=int((feats.state == 2).sum()), n_state2_before=n_state2_before,
                     features=feats, pose=st.get_pose().copy(), n_iterations=rs.n_iterations,

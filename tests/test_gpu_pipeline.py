@@ -2,15 +2,21 @@
 (tests/pipeline_oracle.py: the reference's call sequence src/main.py:248-286 composed from the pinned
 bookkeeping classes and the CPU oracles), frame by frame, and against the reference's own bookkeeping
 golden (tests/golden/bookkeeping.npz)."""
+import math
 import os
 
 import numpy as np
 import pytest
 
 from pipeline_oracle import OracleLoop, initial_features
+import refine_reference
+from refine_cases import DECISION_MARGIN
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
+# how check_step's refinement checks fell out over the session (printed when the module is done)
+ITERATION_CHECKS = {"wide": 0, "narrow": 0}
+COST_CHECKS = {"recomputed": 0, "with_removed_inliers": 0}
 
 
 @pytest.fixture(scope="module")
@@ -19,6 +25,10 @@ def ctx():
     c = _native.Context(0)
     yield c
     c.close()
+    print("\ncheck_step: iteration count held exactly in %d steps, to +-1 in %d (decision below DECISION_MARGIN); cost "
+          "recomputed from the device's landmarks in %d steps, %d of them with removed inliers" % (
+              ITERATION_CHECKS["wide"], ITERATION_CHECKS["narrow"], COST_CHECKS["recomputed"],
+              COST_CHECKS["with_removed_inliers"]))
 
 
 def subsample(features, keep):
@@ -72,8 +82,41 @@ def check_step(r, ref, pipe, gen_ref, tol_refined=1e-7, land_tol=1e-6):
     assert np.allclose(R, ref["R"], atol=1e-9) and np.allclose(t, ref["t"], atol=1e-9)
     Rr, tr = np.array(r.R_refined).reshape(3, 3), np.array(r.t_refined)
     assert np.allclose(Rr, ref["R_ref"], atol=tol_refined) and np.allclose(tr, ref["t_ref"], atol=tol_refined)
-    assert r.n_candidates == ref["n_cand"] and r.n_landmarks == ref["n_landmarks"]
+    Xi, xi, Ki, Ri, ti, max_iter = ref["refine_input"]
+    if max_iter <= 0:                    # not refined: the record says so, the refined pose is the accepted one
+        assert r.refine_iterations == ref["refine_iters"] == -1
+    else:
+        # the iteration count is the rule's (tests/refine_reference.py) wherever the rule takes every decision by more than
+        # rounding can move it; the last accepted step of a converged run often changes the cost by 1e-14 of itself, and
+        # such a step may or may not count (tests/refine_cases.py, DECISION_MARGIN) -- the cost does not depend on it
+        rule = refine_reference.refine(Xi, xi, Ki, Ri, ti, max_iter=max_iter)
+        wide = rule.min_margin >= DECISION_MARGIN
+        ITERATION_CHECKS["wide" if wide else "narrow"] += 1
+        if wide:
+            assert r.refine_iterations == rule.iterations == ref["refine_iters"]
+        else:
+            assert abs(r.refine_iterations - rule.iterations) <= 1 and abs(r.refine_iterations - ref["refine_iters"]) <= 1
+        if land_tol <= 1e-6:
+            assert abs(r.refine_cost - ref["refine_cost"]) <= 1e-9 * ref["refine_cost"]
     st = pipe.get_state()
+    if max_iter > 0 and land_tol > 1e-6:
+        # (SIFT and Harris modes: the landmarks the device refined over are the oracle's to land_tol only, so the minimum
+        #  it finds is another one's.)  The returned cost is the cost of the returned pose over the device's own landmarks
+        #  and keypoints, to 1e-9.  An inlier whose landmark this very step's cheirality check removed is gone from the
+        #  state: the oracle's value stands in for it, known to d = 2 f land_tol pixels in projection, which for m such
+        #  points moves the cost by 2 sqrt(m cost) d + m d^2 at most.
+        idx = ref["p3p_index"][ref["inliers"]]
+        L, kp = st["landmarks"][idx].reshape(-1, 3).copy(), st["keypoints"][idx].reshape(-1, 2)
+        gone = np.isnan(L).any(axis=1)
+        L[gone] = Xi[gone]
+        p = L @ Rr.T + tr
+        e = kp - np.stack([Ki[0, 0] * p[:, 0] / p[:, 2] + Ki[0, 2], Ki[1, 1] * p[:, 1] / p[:, 2] + Ki[1, 2]], axis=1)
+        cost = math.fsum((e * e).reshape(-1).tolist())
+        d, m = 2.0 * max(Ki[0, 0], Ki[1, 1]) * land_tol, int(gone.sum())
+        COST_CHECKS["recomputed"] += 1
+        COST_CHECKS["with_removed_inliers"] += m > 0
+        assert abs(r.refine_cost - cost) <= 1e-9 * cost + 2.0 * np.sqrt(m * cost) * d + m * d * d, (r.refine_cost, cost, m)
+    assert r.n_candidates == ref["n_cand"] and r.n_landmarks == ref["n_landmarks"]
     check_state(st, ref["features"], ref["pose"], land_tol=land_tol)
     assert st["n_iterations"] == ref["n_iterations"] and st["outlier_ratio"] == ref["outlier_ratio"]
     g = np.random.default_rng(0)
@@ -124,6 +167,31 @@ def test_pipeline_matches_oracle_loop(ctx, H, W, N, hyp, frac, redetect, pose_fa
     if frac < 1.0:
         assert redetects >= 1, "the re-detect branch was meant to run"
     assert host_path == (len(order) - 1 if pose_fault else 0)
+    pipe.close()
+
+
+def test_refinement_over_a_population_beyond_the_register_cache(ctx):
+    """One step whose P3P population exceeds the 2048 points the pose kernel's threads keep in registers: the rest is
+    re-read from memory every iteration, its inlier bits from the mask row in memory where the cached points took theirs
+    from LDS.  The accepted mask has inliers and outliers past index 2048, so a point of that loop that is dropped,
+    doubled or read with the wrong bit moves the refined pose and its cost.  480 x 640 is the smallest of the suite's
+    stream sizes whose detector fills 3300 keypoints at NMS radius 5; two thirds of them start triangulated."""
+    from vo import synthetic
+    H, W, N, hyp = 480, 640, 3300, 256
+    stream = synthetic.Stream(2, H, W)
+    feats, T = start_state(stream, N)
+    orc = OracleLoop(stream, N, 15, 2, refine_iters=20)
+    orc.set_state(0, feats, T, T)
+    ref = orc.step(1)
+    inl = ref["inliers"]
+    assert feats.length == N and ref["n_tri"] > 2048 and len(inl) == ref["n_tri"]
+    assert inl[2048:].any() and (~inl[2048:]).any(), "inliers and outliers past the cache"
+    assert ref["refine_iters"] >= 1
+    pipe = make_pipe(ctx, stream, N, hyp)
+    pipe.set_state(0, feats, T, T)
+    r = pipe.step(0, 1)
+    assert r.recovered == 0, "the device path"
+    check_step(r, ref, pipe, orc.rs.rng)
     pipe.close()
 
 

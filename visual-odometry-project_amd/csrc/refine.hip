@@ -7,6 +7,7 @@
 // this kernel runs Gauss-Newton with the analytic Jacobian on the left-multiplied increment
 // T <- [Exp(w) | v] T  (restated in oracle/refine_np.py) until the next step would be below 1e-9
 // relative, 2-3 iterations; SciPy stops within ~1e-4 of the minimiser (tests/test_oracle_refine.py).
+// The rule in full is in include/vo_hip.h ("pose refinement"); tests/refine_reference.py states it in NumPy.
 //
 // One workgroup of 512 threads: every thread keeps its (up to four) points in registers and
 // accumulates their 21 + 6 + 1 terms once per iteration; a wave adds its lanes' terms with a
@@ -22,6 +23,7 @@ namespace {
 
 constexpr int RF_T = 512;
 constexpr int RF_S = 28;   // 21 (upper triangle of J^T J) + 6 (J^T e) + 1 (cost)
+constexpr int RF_W = 29;   // values a wave hands over: the RF_S sums and the number of active points
 constexpr int RF_PT = 4;   // points per thread kept in registers (N <= 2048; beyond that they are re-read)
 
 struct rf_point {
@@ -47,7 +49,7 @@ __device__ __forceinline__ rf_point load_point(const double* __restrict__ X, con
   return p;
 }
 
-// adds one point's terms for the pose (R, t) to s[]
+// adds one point's terms for the pose (R, t) to s[0..27] and counts it in s[28]
 __device__ __forceinline__ void add_point(const rf_point& p, const double* R, const double* t, double fx, double fy,
                                           double cx, double cy, double* s) {
   if (!p.on) return;
@@ -92,6 +94,7 @@ __device__ __forceinline__ void add_point(const rf_point& p, const double* R, co
   s[25] += j04 * eu + j14 * ev;
   s[26] += j05 * eu + j15 * ev;
   s[27] += eu * eu + ev * ev;
+  s[RF_S] += 1.0;
 }
 
 // sums for the pose (R, t): the thread's cached points, plus (N > RF_PT * RF_T) the rest re-read
@@ -100,7 +103,7 @@ __device__ __forceinline__ void accumulate(const rf_point* cache, const double* 
                                            const unsigned long long* __restrict__ mask_bits, const double* R,
                                            const double* t, double fx, double fy, double cx, double cy, double* s) {
 #pragma unroll
-  for (int k = 0; k < RF_S; ++k) s[k] = 0.0;
+  for (int k = 0; k < RF_W; ++k) s[k] = 0.0;
 #pragma unroll
   for (int k = 0; k < RF_PT; ++k) add_point(cache[k], R, t, fx, fy, cx, cy, s);
   for (int i = RF_PT * RF_T + threadIdx.x; i < N; i += RF_T)
@@ -149,11 +152,12 @@ __device__ __forceinline__ void fold_step(double* v, int lane) {
   }
 }
 
-// wave-wide sums of s[0..27]: afterwards lanes 2j and 2j+1 hold the total of s[j] (32 shuffles, not 28 * 6)
+// wave-wide sums of s[0..28]: afterwards lanes 2j and 2j+1 hold the total of s[j] (32 shuffles, not 28 * 6; the count
+// rides in one of the fold's four spare slots, the 28 sums are formed exactly as without it)
 __device__ __forceinline__ double wave_sums(const double* s, int lane) {
   double v[32];
 #pragma unroll
-  for (int k = 0; k < 32; ++k) v[k] = k < RF_S ? s[k] : 0.0;
+  for (int k = 0; k < 32; ++k) v[k] = k < RF_W ? s[k] : 0.0;
   fold_step<32, 32>(v, lane);
   fold_step<16, 16>(v, lane);
   fold_step<8, 8>(v, lane);
@@ -249,7 +253,7 @@ __device__ __forceinline__ void rodrigues_coefficients(double th2, double* a, do
 __device__ __forceinline__ void gauss_newton(const rf_point* cache, const double* __restrict__ X,
                                              const double* __restrict__ x, int N, const uint8_t* __restrict__ mask8,
                                              const unsigned long long* __restrict__ mask_bits, double fx, double fy,
-                                             double cx, double cy, int max_iter, double tol, double (*s_w)[RF_S],
+                                             double cx, double cy, int max_iter, double tol, double (*s_w)[RF_W],
                                              double* s_pose, double* s_try, int* s_state, int* it_out,
                                              double* cost_out) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -258,14 +262,14 @@ __device__ __forceinline__ void gauss_newton(const rf_point* cache, const double
   for (;;) {
     __syncthreads();
     if (*s_state != 0) break;
-    double s[RF_S];
+    double s[RF_W];
     accumulate(cache, X, x, N, mask8, mask_bits, s_try, s_try + 9, fx, fy, cx, cy, s);
     const double wsum = wave_sums(s, lane);
-    if ((lane & 1) == 0 && (lane >> 1) < RF_S) s_w[wv][lane >> 1] = wsum;
+    if ((lane & 1) == 0 && (lane >> 1) < RF_W) s_w[wv][lane >> 1] = wsum;
     __syncthreads();
     if (wv != 0) continue;
     double tot = 0.0;
-    if (lane < RF_S) {
+    if (lane < RF_W) {
 #pragma unroll
       for (int w = 0; w < RF_T / 64; ++w) tot += s_w[w][lane];
     }
@@ -274,6 +278,9 @@ __device__ __forceinline__ void gauss_newton(const rf_point* cache, const double
     if (it < 0) {
       it = 0;
       cost = cost_new;
+      // fewer than three active points or a start cost that is not finite: the pose stays as it came, bit for bit
+      // (a rank-deficient matrix can pass the pivot test by rounding alone)
+      stop = !(lane_value<RF_S>(tot) >= 3.0) || !(fabs(cost_new) <= 1.7976931348623157e308);
     } else if (!(cost_new <= cost)) {
       stop = true;           // no decrease: keep the previous pose
     } else {
@@ -338,7 +345,7 @@ __global__ __launch_bounds__(RF_T) void refine_pose_kernel(const double* __restr
                                                            const double* __restrict__ Rt0, double fx, double fy, double cx,
                                                            double cy, int max_iter, double tol, double* __restrict__ out,
                                                            unsigned tag) {
-  __shared__ double s_w[RF_T / 64][RF_S];
+  __shared__ double s_w[RF_T / 64][RF_W];
   __shared__ double s_pose[12], s_try[12];
   __shared__ int s_state;   // 0 run the next trial, 1 finished (s_pose holds the result)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -386,7 +393,7 @@ constexpr int TAIL_LIST = 4096;   // candidates the LDS list holds (more: every 
 __global__ __launch_bounds__(RF_T) void frame_pose_kernel(vo_pose_job job) {
   using namespace vo_state_dev;
   __shared__ double s_table[RP_TABLE_LDS];
-  __shared__ double s_w[RF_T / 64][RF_S];
+  __shared__ double s_w[RF_T / 64][RF_W];
   __shared__ double s_pose[12], s_try[12];
   __shared__ int s_state, s_cand[RF_T / 64];
   __shared__ int s_list[TAIL_LIST];

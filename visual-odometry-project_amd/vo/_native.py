@@ -1032,6 +1032,13 @@ class Context:
         self._chk(self._lib.vo_reproj_inliers_dev(self._h, C.c_void_p(d_X), C.c_void_p(d_x), int(N), _ptr(K),
                                                   C.c_void_p(d_Rt), float(thr_sq), C.c_void_p(d_mask), C.c_void_p(d_err)))
 
+    def refine_pose_dev(self, d_X, d_x, N, K, d_mask, d_Rt0, max_iter, d_out14):
+        """vo_refine_pose_dev: d_mask (N bytes) may be None; d_Rt0 = R0 then t0 (12 doubles); d_out14 receives R, t,
+        iterations, cost."""
+        K = _c(K, np.float64).reshape(3, 3)
+        self._chk(self._lib.vo_refine_pose_dev(self._h, C.c_void_p(d_X), C.c_void_p(d_x), int(N), _ptr(K),
+                                               C.c_void_p(d_mask), C.c_void_p(d_Rt0), int(max_iter), C.c_void_p(d_out14)))
+
     def harris_response_dev(self, d_img, H, W, patch, kappa, d_scores):
         self._chk(self._lib.vo_harris_response_dev(self._h, C.c_void_p(d_img), H, W, int(patch), float(kappa),
                                                    C.c_void_p(d_scores)))
