@@ -97,7 +97,8 @@ enum {
   VO_K_WINDOW_BUILD = 29,       /* vo_window_from_tracks_dev, both of its launches */
   VO_K_TWOVIEW_HYP = 30,        /* the two-view hypothesis kernel of a call: f8_hyp_kernel or e5_hyp_kernel */
   VO_K_TWOVIEW_SCORE = 31,      /* ... and its scorer: f_score_kernel or e5_score_kernel */
-  VO_K_COUNT = 32
+  VO_K_WINDOW_STRUCTURE = 32,   /* vo_window_structure_dev, both of its launches */
+  VO_K_COUNT = 33
 };
 int vo_prof_enable(vo_ctx* ctx, int kernel_id);
 /* bracket only every n-th launch of a profiled kernel (default 1): the event pair itself costs
@@ -1011,6 +1012,78 @@ int vo_window_from_tracks_dev(vo_ctx* ctx, int W, const void* const* d_records, 
  * the poses included, stays as it was.  Nothing may be in flight; needs vo_pipeline_config.track_ids (VO_EINVAL naming it).
  * Enqueued on the pipeline's stream; synchronises.                                                                      */
 int vo_pipeline_update_landmarks_seq(vo_pipeline* p, int seq, int n, const int32_t* d_ids, const double* d_X);
+
+/* ---- Window structure refinement ------------------------------------------------------------------
+ * The window bundle adjustment with every pose held -- the configuration it refuses (n_fixed >= W) and the cheap one: the
+ * poses stay as the per-frame P3P refinement left them, and each landmark is a least-squares problem of its own in three
+ * unknowns over the observations of its track.  No Schur complement, no reduced system; landmarks never meet.
+ *
+ * The window is vo_window_ba_dev's, array for array and stride for stride (d_counts {L, M, -, -}, d_K, d_poses W x 12 -- read
+ * only here --, d_X in place, d_lm_start, d_obs_slot, d_obs_xy); W <= 16, S windows per call.  Per landmark i, over its
+ * observations k = lm_start[i] .. lm_start[i + 1] - 1, with e, rho, the IRLS weight w, p, a b c d and J_lm = [a 0 c; 0 b d] R
+ * exactly as above:
+ *   sums    V = sum w J_lm^T J_lm;  g = sum w J_lm^T e;  cost = sum rho.  Every sum runs over the landmark's observations in
+ *           one fixed order.
+ *   step    the diagonal of V times (1 + lambda); the 3x3 system solved by Cholesky without pivoting, dX = V*^-1 g.  A pivot
+ *           that is not positive rejects the trial: it is counted and lambda <- 10 lambda.
+ *   control lambda starts at lambda0.  Before every trial, in this order: `max_iter` accepted steps -> status 1;
+ *           `max_trials` trials -> status 2; lambda > 1e12 -> status 3.  Then the system is solved.
+ *   stop    the step is not taken and not counted, status 0, when |dX| <= step_tol (1 + |X|) or g . dX <= f_tol cost (g . dX:
+ *           the decrease the linearisation predicts).  The second test is what makes the counts a property of the window and
+ *           not of the summation order: these problems converge quadratically to rounding level, where a trial changes the
+ *           cost by 1e-15 of itself and cost_new <= cost is a coin toss; a trial that is evaluated is predicted to lower the
+ *           cost by more than f_tol of it.
+ *   accept  otherwise the trial is counted; accepted iff every observation has p_z > 0 at X + dX and cost_new <= cost: then
+ *           lambda <- max(lambda / 10, 1e-12), else lambda <- 10 lambda.
+ *   refused status 4, X bit for bit as it was, iterations = trials = 0, costs and min_cos 0: a landmark with fewer than 2
+ *           observations or more than W (n_obs: the CSR's count when it lies in 0 .. W, else 0); slots not strictly ascending
+ *           in 0 .. W - 1; a non-finite observation or X; an observation with p_z <= 0, or a cost that is not finite, at the
+ *           start.  A window with L > L_cap, M outside 0 .. M_cap, lm_start[L] != M or a non-finite pose or intrinsic
+ *           refuses every one of its landmarks (n_obs 0); L <= 0 has none.  One bad landmark never touches its neighbours.
+ *   min_cos the smallest cosine between any two of the landmark's world-frame observation rays, R^T ((u - cx) / fx,
+ *           (v - cy) / fy, 1) normalised.
+ *   gate    a refined landmark is kept iff status is 0 or 1, and gate_px == 0 or sqrt(sum |e|^2 / n_obs) <= gate_px (the
+ *           squared residuals at the result, also under Huber), and min_parallax == 0 or min_cos <= cos(min_parallax).  A
+ *           landmark that is not kept has X bit for bit as it was; cost is still the one the refinement reached.
+ * All of it fp64, no floating-point atomics: the same call gives the same bits, and a window gives the same bits alone as
+ * inside a batch.
+ *
+ * vo_window_structure_dev: window q's rows at d_results + L_cap q (rows i < min(L, L_cap) are written, the others left) and
+ * its summary at d_summary + q; two launches (the landmarks; one workgroup per window for the summary), enqueued on the
+ * context's stream, no synchronisation.  vo_window_structure: the same from host arrays (uploads, runs, downloads X, the
+ * results -- rows that are not written read 0 -- and the summaries, synchronises).  Bad arguments: VO_EINVAL with a message. */
+typedef struct vo_structure_params {      /* 0 in a field = the default named here */
+  int32_t max_iter;                       /* accepted steps, <= 50; default 10 */
+  int32_t max_trials;                     /* trials, <= 1000; default 2 * max_iter */
+  double huber_px;                        /* Huber threshold in pixels; 0 = squared loss */
+  double lambda0;                         /* default 1e-3 */
+  double step_tol;                        /* default 1e-10 */
+  double f_tol;                           /* default 1e-9 */
+  double gate_px;                         /* RMS reprojection gate in pixels; 0 = no gate */
+  double min_parallax;                    /* radians, < pi; 0 = no gate */
+} vo_structure_params;
+typedef struct vo_structure_result {      /* per landmark */
+  int32_t status;                         /* 0 converged, 1 max_iter, 2 max_trials, 3 lambda beyond 1e12, 4 refused */
+  int32_t iterations, trials;             /* accepted steps; trials counted */
+  int32_t n_obs;
+  double cost0, cost;                     /* at the start, at the refined point */
+  double min_cos;
+  int32_t kept;                           /* 1: X is the refined point, 0: X is the input */
+  int32_t reserved;
+} vo_structure_result;
+typedef struct vo_structure_summary {     /* per window */
+  int32_t L;                              /* as d_counts gave it */
+  int32_t n_refused, n_kept;
+  int32_t max_iterations;
+  double cost0, cost;                     /* sums over the landmarks not refused, in one fixed order */
+} vo_structure_summary;
+int vo_window_structure_dev(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const int32_t* d_counts, const double* d_K,
+                            const double* d_poses, double* d_X, const int32_t* d_lm_start, const int32_t* d_obs_slot,
+                            const double* d_obs_xy, const vo_structure_params* prm /* NULL: defaults */,
+                            vo_structure_result* d_results /* S * L_cap */, vo_structure_summary* d_summary /* S */);
+int vo_window_structure(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const int32_t* counts, const double* K,
+                        const double* poses, double* X, const int32_t* lm_start, const int32_t* obs_slot, const double* obs_xy,
+                        const vo_structure_params* prm, vo_structure_result* results, vo_structure_summary* summary);
 
 /* ---- shared map over RCCL ------------------------------------------------------------------
  * The reference is one process and one thread (README.md:49); frame streams shard at sequence granularity (one

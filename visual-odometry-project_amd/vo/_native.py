@@ -21,8 +21,10 @@ _CODES = {VO_EINVAL: "VO_EINVAL", VO_ENOMEM: "VO_ENOMEM", VO_EHIP: "VO_EHIP", VO
 K_HARRIS_RESPONSE, K_NMS_CANDIDATES, K_NMS_THRESHOLD, K_NMS_COMPACT, K_NMS_SELECT = 0, 1, 2, 3, 4
 K_PATCH_DESC, K_PYR_DOWN, K_KLT_TRACK, K_DLT, K_P3P_SOLVE, K_P3P_SCORE, K_REPROJ, K_MATCH = 5, 6, 7, 8, 9, 10, 11, 12
 K_SHI_TOMASI_CHAIN = 27
+K_WINDOW_BA, K_WINDOW_BUILD = 28, 29          # vo_window_ba_dev's solver; vo_window_from_tracks_dev, both launches
 K_TWOVIEW_HYP, K_TWOVIEW_SCORE = 30, 31      # f8_hyp_kernel / e5_hyp_kernel and f_score_kernel / e5_score_kernel
-K_COUNT = 32
+K_WINDOW_STRUCTURE = 32                       # vo_window_structure_dev, both launches
+K_COUNT = 33
 
 
 class VoError(RuntimeError):
@@ -142,6 +144,27 @@ BA_RESULT = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"
 
 def ba_params(n_fixed=0, huber_px=0.0, max_iter=0, max_trials=0, lambda0=0.0, step_tol=0.0):
     return BaParams(int(max_iter), int(max_trials), int(n_fixed), 0, float(huber_px), float(lambda0), float(step_tol))
+
+
+class StructureParams(C.Structure):
+    """vo_structure_params: 0 in a field = its default (max_iter 10, max_trials 2 * max_iter, squared loss, lambda0 1e-3,
+    step_tol 1e-10, f_tol 1e-9, no residual gate, no parallax gate)."""
+    _fields_ = [("max_iter", C.c_int32), ("max_trials", C.c_int32), ("huber_px", C.c_double), ("lambda0", C.c_double),
+                ("step_tol", C.c_double), ("f_tol", C.c_double), ("gate_px", C.c_double), ("min_parallax", C.c_double)]
+
+
+# vo_structure_result (per landmark; status as BA_RESULT's, kept: X is the refined point) and vo_structure_summary (per
+# window) as NumPy rows: the same 48 and 32 bytes
+STRUCTURE_RESULT = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("n_obs", "<i4"), ("cost0", "<f8"),
+                             ("cost", "<f8"), ("min_cos", "<f8"), ("kept", "<i4"), ("reserved", "<i4")])
+STRUCTURE_SUMMARY = np.dtype([("L", "<i4"), ("n_refused", "<i4"), ("n_kept", "<i4"), ("max_iterations", "<i4"),
+                              ("cost0", "<f8"), ("cost", "<f8")])
+
+
+def structure_params(huber_px=0.0, max_iter=0, max_trials=0, lambda0=0.0, step_tol=0.0, f_tol=0.0, gate_px=0.0,
+                     min_parallax=0.0):
+    return StructureParams(int(max_iter), int(max_trials), float(huber_px), float(lambda0), float(step_tol), float(f_tol),
+                           float(gate_px), float(min_parallax))
 
 
 _vp, _i, _d, _sz = C.c_void_p, C.c_int, C.c_double, C.c_size_t
@@ -283,6 +306,8 @@ _SIGS = {
     "vo_window_ba_dev": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_window_ba": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_window_from_tracks_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_window_structure_dev": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_window_structure": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_pipeline_update_landmarks_seq": (_i, [_vp, _i, _i, _vp, _vp]),
 }
 
@@ -572,6 +597,48 @@ class Context:
         self._chk(self._lib.vo_window_from_tracks_dev(self._h, len(d_records), recs, int(cap), int(L_cap), int(M_cap),
                                                       C.c_void_p(d_head), C.c_void_p(d_lm_start), C.c_void_p(d_obs_slot),
                                                       C.c_void_p(d_obs_xy), C.c_void_p(d_X), C.c_void_p(d_lm_id)))
+
+    # ---- window structure refinement (csrc/window_structure.hip) ----
+    def window_structure(self, K, poses, X, lm_start, obs_slot, obs_xy, counts, **params):
+        """vo_window_structure on host arrays, laid out as window_ba's: every pose held, each landmark refined on its own.
+        Returns (X, results, summary): the refined copy (a landmark that is refused or not kept keeps its bits), an
+        (S, L_cap) record array (dtype STRUCTURE_RESULT; rows beyond a window's L are zero) and an (S,) one (dtype
+        STRUCTURE_SUMMARY).  params: structure_params' keywords, 0 = the default of vo_structure_params."""
+        poses = _c(poses, np.float64)
+        if poses.ndim != 3 or poses.shape[2] != 12:
+            raise ValueError("window_structure: poses must be (S, W, 12), got %s" % (poses.shape,))
+        S, W = poses.shape[:2]
+        X = np.array(X, np.float64, order="C")
+        lm_start, obs_slot = _c(lm_start, np.int32), _c(obs_slot, np.int32)
+        obs_xy = _c(obs_xy, np.float64)
+        if X.ndim != 3 or X.shape[0] != S or X.shape[2] != 3 or X.shape[1] < 1:
+            raise ValueError("window_structure: X must be (S, L_cap >= 1, 3), got %s" % (X.shape,))
+        L_cap = X.shape[1]
+        if lm_start.shape != (S, L_cap + 1):
+            raise ValueError("window_structure: lm_start must be (S, L_cap + 1) = %s, got %s" % ((S, L_cap + 1), lm_start.shape))
+        if obs_slot.ndim != 2 or obs_slot.shape[0] != S or obs_slot.shape[1] < 1 or obs_xy.shape != obs_slot.shape + (2,):
+            raise ValueError("window_structure: obs_slot must be (S, M_cap >= 1) and obs_xy (S, M_cap, 2), got %s and %s"
+                             % (obs_slot.shape, obs_xy.shape))
+        M_cap = obs_slot.shape[1]
+        K = np.asarray(K, np.float64)
+        K = _c(np.broadcast_to(K.reshape(-1, 3, 3), (S, 3, 3)) if K.size == 9 else K.reshape(S, 3, 3), np.float64)
+        cnt = np.zeros((S, 4), np.int32)
+        cnt[:, :2] = np.asarray(counts).reshape(S, -1)[:, :2]
+        prm = structure_params(**params)
+        res, summ = np.zeros((S, L_cap), STRUCTURE_RESULT), np.zeros(S, STRUCTURE_SUMMARY)
+        self._chk(self._lib.vo_window_structure(self._h, S, W, L_cap, M_cap, _ptr(cnt), _ptr(K), _ptr(poses), _ptr(X),
+                                                _ptr(lm_start), _ptr(obs_slot), _ptr(obs_xy), C.byref(prm), _ptr(res), _ptr(summ)))
+        return X, res, summ
+
+    def window_structure_dev(self, S, W, L_cap, M_cap, d_counts, d_K, d_poses, d_X, d_lm_start, d_obs_slot, d_obs_xy,
+                             d_results, d_summary, **params):
+        """vo_window_structure_dev on device pointers, enqueued on the context's stream: the landmarks of S windows refined
+        in place, STRUCTURE_RESULT rows at d_results + L_cap q, one STRUCTURE_SUMMARY row per window at d_summary."""
+        prm = structure_params(**params)
+        self._chk(self._lib.vo_window_structure_dev(self._h, int(S), int(W), int(L_cap), int(M_cap), C.c_void_p(d_counts),
+                                                    C.c_void_p(d_K), C.c_void_p(d_poses), C.c_void_p(d_X), C.c_void_p(d_lm_start),
+                                                    C.c_void_p(d_obs_slot), C.c_void_p(d_obs_xy), C.byref(prm),
+                                                    C.c_void_p(d_results), C.c_void_p(d_summary)))
 
     # ---- frame ingest (csrc/ingest.hip) ----
     def gray_from_bgr(self, bgr):

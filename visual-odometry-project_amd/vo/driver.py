@@ -153,29 +153,43 @@ class _BaTap:
     """The window bundle adjustment behind the collected steps: every lane keeps its last `window` observation records in
     device buffers of its own (posted like the tap's, behind the step in flight) and the refined poses of their frames; once
     a lane holds a full window, the windows of all such lanes go through one solver call per step
-    (vo.landmarks.solve_windows)."""
+    (vo.landmarks.solve_windows).  mode "structure": the poses are held and the landmarks alone are refined
+    (vo.landmarks.WindowStructureRefiner / refine_windows) -- the same records, the same builder, the same write-back."""
 
-    def __init__(self, ctx, pipe, lanes, window, params):
-        self.ctx, self.pipe, self.window, self.params = ctx, pipe, int(window), params
+    def __init__(self, ctx, pipe, lanes, window, params, mode="full"):
+        self.ctx, self.pipe, self.window, self.params, self.mode = ctx, pipe, int(window), params, mode
         nbytes = pipe.tracks_record_bytes(pipe.cap)
         self.ring = [[ctx.alloc(nbytes) for _ in range(self.window)] for _ in range(lanes)]
         self.turn = [0] * lanes
         self.adj = [None] * lanes
 
     def start(self, lane, K):
-        from vo.landmarks import WindowBundleAdjuster
+        from vo.landmarks import WindowBundleAdjuster, WindowStructureRefiner
         if self.adj[lane]:
             self.adj[lane].close()
-        self.adj[lane] = WindowBundleAdjuster(K, window=self.window, cap=self.pipe.cap, context=self.ctx, **self.params)
+        make = WindowStructureRefiner if self.mode == "structure" else WindowBundleAdjuster
+        self.adj[lane] = make(K, window=self.window, cap=self.pipe.cap, context=self.ctx, **self.params)
 
     def step(self, items, feedback):
         """items: (lane, the step's StepResult, the list its `ba` entries go to) of the step collected just now."""
-        from vo.landmarks import solve_windows
+        from vo.landmarks import refine_windows, solve_windows
         for lane, r, _ in items:
             d_rec = self.ring[lane][self.turn[lane]]
             self.turn[lane] = (self.turn[lane] + 1) % self.window
             self.pipe.export_tracks_post(r, self.pipe.cap, d_rec, seq=lane)
             self.adj[lane].push(d_rec, np.concatenate((np.array(r.R_refined), np.array(r.t_refined))))
+        if self.mode == "structure":
+            for (lane, _, sink), s in zip(items, refine_windows([self.adj[lane] for lane, _, _ in items])):
+                if s is None:
+                    continue
+                m = s.summary
+                refused = int(m["n_refused"]) == s.n                       # (every landmark, or none to refuse: L = 0)
+                sink.append(dict(frames=s.steps, poses=s.poses, ids=s.ids, landmarks=s.landmarks, kept=s.results["kept"].astype(bool),
+                                 status=4 if refused else 0, cost0=float(m["cost0"]), cost=float(m["cost"]),
+                                 iterations=int(m["max_iterations"]), n_kept=int(m["n_kept"])))
+                if feedback and s.n and not refused:
+                    self.pipe.update_landmarks(s.d_ids, s.d_X, seq=lane, n=s.n)      # (a landmark not kept: the bits it had)
+            return
         solved = solve_windows([self.adj[lane] for lane, _, _ in items])
         for (lane, _, sink), s in zip(items, solved):
             if s is None:
@@ -219,7 +233,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
                   redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                   bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
                   tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None,
-                  bootstrap_method: str = "8point"):
+                  bootstrap_method: str = "8point", ba_mode: str = "full"):
     """Same loop, same bootstrap, but the steady state runs as the device-resident pipeline (vo_pipeline_*):
     after the host bootstrap the Features / State arrays are handed to the GPU once, every later frame costs one
     image upload and one call, and nothing but the pose record comes back.  KLT tracker mode with the Harris
@@ -254,6 +268,13 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     back into the pipeline (Pipeline.update_landmarks) between steps; that needs nothing in flight, so every step is
     collected before the next is submitted: the look-ahead of one step is given up.  ba_window=None (the default): nothing
     of this exists and the loop is the one it was.
+    ba_mode: "full" (the default) -- the adjustment above; "structure" -- every pose of the window is held and each landmark
+    is refined on its own over the observations of its track (vo.landmarks.WindowStructureRefiner, vo_window_structure_dev):
+    the cheap configuration the adjustment refuses.  ba_params then takes huber_px / max_iter / gate_px / min_parallax
+    (n_fixed: ValueError), and a `ba` entry is frames, poses (as given), ids, landmarks, kept (per landmark: refined and
+    through the gates; the others are the record's), status (0, or 4 when no landmark was refined: the whole window was
+    refused, or it is empty, L = 0 -- as the adjustment reports an empty window), cost0, cost (sums over the landmarks not
+    refused), iterations (the largest), n_kept.  ba_feedback writes back the same way.
 
     This is run_batch_on_device([sequence], lanes=1, ...)[0], the same loop (_DeviceRun) with one lane, and what comes
     with that: the lane's camera is set once more at the start (Pipeline.set_camera with the constructor's K, so the
@@ -265,7 +286,8 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     run = _DeviceRun([sequence], 1, max_frames, context, bootstrap, tracks,
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
                      (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
-                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method)
+                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method,
+                     ba_mode=ba_mode)
     out = run.run()[0]
     out["frame_seconds"] = out["frame_seconds"] - np.array(run.read_seconds)
     if tracks:
@@ -440,12 +462,20 @@ class _DeviceRun:
     SLOTS = 4
 
     def __init__(self, sequences, lanes, max_frames, context, bootstrap, tracks, boot_args, pipe_args, ba_window=None,
-                 ba_feedback=False, ba_params=None, bootstrap_method="8point"):
+                 ba_feedback=False, ba_params=None, bootstrap_method="8point", ba_mode="full"):
         _check_bootstrap_route(bootstrap, bootstrap_method)
         self.bootstrap_method = bootstrap_method
         if ba_window is not None and not tracks:
             raise ValueError("ba_window needs tracks=True: the window is built from the observation records")
+        if ba_mode not in ("full", "structure"):
+            raise ValueError("ba_mode must be 'full' or 'structure', got %r" % (ba_mode,))
         self.ba_window, self.ba_feedback, self.ba_params = ba_window, bool(ba_feedback), dict(ba_params or {})
+        self.ba_mode = ba_mode
+        if ba_window is not None and ba_mode == "structure":
+            allowed = ("huber_px", "max_iter", "gate_px", "min_parallax")
+            for k in self.ba_params:
+                if k not in allowed:
+                    raise ValueError("ba_mode='structure' holds every pose: ba_params takes %s, not %s" % (", ".join(allowed), k))
         self.ba = None                                   # lane -> its WindowBundleAdjuster (open_pipeline)
         self.sequences = sequences = list(sequences)
         self.on_device, self.context, self.tracks = bootstrap == "device", context, tracks
@@ -500,7 +530,7 @@ class _DeviceRun:
                                      track_ids=self.tracks, **_pipeline_kwargs(state0, *self.pipe_args))
         self.tap = _TrackTap(self.ctx, self.pipe, self.lanes) if self.tracks else None
         if self.ba_window is not None:
-            self.ba = _BaTap(self.ctx, self.pipe, self.lanes, self.ba_window, self.ba_params)
+            self.ba = _BaTap(self.ctx, self.pipe, self.lanes, self.ba_window, self.ba_params, self.ba_mode)
         self.ring = [[None] * self.SLOTS for _ in range(self.lanes)]
 
     def set_camera(self, lane, r):
@@ -651,7 +681,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                         bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
                         tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None,
-                        bootstrap_method: str = "8point"):
+                        bootstrap_method: str = "8point", ba_mode: str = "full"):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
     (_device_bootstrap); when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
@@ -665,7 +695,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     recording without a steady-state step never holds a lane: host route.)  detector: as in run_on_device, for every lane.
     tracks: as in run_on_device -- every recording's dict gains `observations`, one record per step it took (a lane's ids
     start over with every recording: each start is a hand-over).
-    ba_window / ba_feedback / ba_params: as in run_on_device; the windows of all lanes that hold a full one go through one
+    ba_window / ba_feedback / ba_params / ba_mode: as in run_on_device; the windows of all lanes that hold a full one go through one
     solver call per step, and a lane's window starts again with every recording.
     bootstrap_method: as in run_on_device, for every recording's host bootstrap.
 
@@ -675,7 +705,8 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     out = _DeviceRun(sequences, lanes, max_frames, context, bootstrap, tracks,
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
                      (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
-                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method).run()
+                     ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method,
+                     ba_mode=ba_mode).run()
     if ba_window is not None:
         for o in out:
             o.setdefault("ba", [])

@@ -1,2 +1,3 @@
 from .triangulation import LandmarksTriangulator  # noqa: F401
 from .window_ba import WindowBundleAdjuster, pack_windows, solve_windows  # noqa: F401
+from .window_structure import WindowStructureRefiner, refine_windows  # noqa: F401

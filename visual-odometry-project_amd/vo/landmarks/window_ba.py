@@ -44,10 +44,11 @@ def pose_cw12(pose):
 class _Arena:
     """Device arrays of S windows (W slots, L_cap landmarks, M_cap observations each)."""
 
-    def __init__(self, ctx, S, W, L_cap, M_cap):
+    def __init__(self, ctx, S, W, L_cap, M_cap, **more):
         self.ctx, self.shape = ctx, (S, W, L_cap, M_cap)
         sizes = dict(head=16, K=72, poses=96 * W, X=24 * L_cap, lm_start=4 * (L_cap + 1), obs_slot=4 * M_cap,
                      obs_xy=16 * M_cap, lm_id=4 * L_cap, res=40)
+        sizes.update(more)            # (bytes per window of a further array, or another size for one of these)
         self.stride = sizes
         self.d = {k: ctx.alloc(S * v) for k, v in sizes.items()}
 
@@ -115,6 +116,41 @@ def _headers(adj):
     return [int(h["step"]) for h in heads[keep:]]
 
 
+def _full_windows(holders):
+    """(index, holder, steps) of the holders that hold a full window of consecutive records."""
+    ready = []
+    for k, a in enumerate(holders):
+        if len(a.records) == a.window:
+            steps = _headers(a)
+            if len(a.records) == a.window:
+                ready.append((k, a, steps))
+    return ready
+
+
+def _join_windows(ready, who, **more):
+    """The windows of `ready` (_full_windows) joined on the device into the first holder's arena, K and the poses uploaded.
+    more: further arrays of the arena (name -> bytes per window, or a function of (W, L_cap, M_cap))."""
+    first = ready[0][1]
+    ctx, W = first.ctx, first.window
+    cap = first.cap
+    if cap is None:
+        raise ValueError("%s: cap (the records' capacity) was not given" % who)
+    L_cap = first.L_cap or cap
+    M_cap = L_cap * W
+    S = len(ready)
+    if first._arena is None or first._arena.shape != (S, W, L_cap, M_cap):
+        if first._arena:
+            first._arena.close()
+        first._arena = _Arena(ctx, S, W, L_cap, M_cap, **{k: v(W, L_cap, M_cap) if callable(v) else v for k, v in more.items()})
+    ar = first._arena
+    ctx.upload(ar.d["K"], np.stack([a.K for _, a, _ in ready]))
+    ctx.upload(ar.d["poses"], np.stack([np.stack(a.poses) for _, a, _ in ready]))
+    for q, (_, a, _) in enumerate(ready):
+        ctx.window_from_tracks(a.records, cap, L_cap, M_cap, ar.at("head", q), ar.at("lm_start", q), ar.at("obs_slot", q),
+                               ar.at("obs_xy", q), ar.at("X", q), ar.at("lm_id", q))
+    return ar, S, W, L_cap, M_cap
+
+
 def solve_windows(adjusters):
     """The windows of several adjusters (same context, window length, capacities and parameters: the lanes of one pipeline)
     through ONE solver call.  Returns a list with, per adjuster, None (no full window) or a namespace: poses (W, 12), ids
@@ -122,32 +158,12 @@ def solve_windows(adjusters):
     d_ids / d_X / n: the refined landmarks still on the device (valid until the first adjuster's next solve)."""
     from vo import _native
     out = [None] * len(adjusters)
-    ready = []
-    for k, a in enumerate(adjusters):
-        if len(a.records) == a.window:
-            steps = _headers(a)
-            if len(a.records) == a.window:
-                ready.append((k, a, steps))
+    ready = _full_windows(adjusters)
     if not ready:
         return out
     first = ready[0][1]
-    ctx, W = first.ctx, first.window
-    cap = first.cap
-    if cap is None:
-        raise ValueError("WindowBundleAdjuster: cap (the records' capacity) was not given")
-    L_cap = first.L_cap or cap
-    M_cap = L_cap * W
-    S = len(ready)
-    if first._arena is None or first._arena.shape != (S, W, L_cap, M_cap):
-        if first._arena:
-            first._arena.close()
-        first._arena = _Arena(ctx, S, W, L_cap, M_cap)
-    ar = first._arena
-    ctx.upload(ar.d["K"], np.stack([a.K for _, a, _ in ready]))
-    ctx.upload(ar.d["poses"], np.stack([np.stack(a.poses) for _, a, _ in ready]))
-    for q, (_, a, _) in enumerate(ready):
-        ctx.window_from_tracks(a.records, cap, L_cap, M_cap, ar.at("head", q), ar.at("lm_start", q), ar.at("obs_slot", q),
-                               ar.at("obs_xy", q), ar.at("X", q), ar.at("lm_id", q))
+    ctx = first.ctx
+    ar, S, W, L_cap, M_cap = _join_windows(ready, "WindowBundleAdjuster")
     ctx.window_ba_dev(S, W, L_cap, M_cap, ar.d["head"], ar.d["K"], ar.d["poses"], ar.d["X"], ar.d["lm_start"],
                       ar.d["obs_slot"], ar.d["obs_xy"], ar.d["res"], **first.params)
     head = ctx.download(ar.d["head"], (S, 4), np.int32)
