@@ -98,7 +98,10 @@ enum {
   VO_K_TWOVIEW_HYP = 30,        /* the two-view hypothesis kernel of a call: f8_hyp_kernel or e5_hyp_kernel */
   VO_K_TWOVIEW_SCORE = 31,      /* ... and its scorer: f_score_kernel or e5_score_kernel */
   VO_K_WINDOW_STRUCTURE = 32,   /* vo_window_structure_dev, both of its launches */
-  VO_K_COUNT = 33
+  VO_K_LOOP_RECORD = 33,        /* vo_structure_loop_post: the record into the ring and its ids into the table */
+  VO_K_LOOP_JOIN = 34,          /* ... the header check and the join, one workgroup per lane */
+  VO_K_LOOP_WRITE = 35,         /* ... the entry and the write-back (also when it is queued again behind a redone step) */
+  VO_K_COUNT = 36
 };
 int vo_prof_enable(vo_ctx* ctx, int kernel_id);
 /* bracket only every n-th launch of a profiled kernel (default 1): the event pair itself costs
@@ -1084,6 +1087,79 @@ int vo_window_structure_dev(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, con
 int vo_window_structure(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const int32_t* counts, const double* K,
                         const double* poses, double* X, const int32_t* lm_start, const int32_t* obs_slot, const double* obs_xy,
                         const vo_structure_params* prm, vo_structure_result* results, vo_structure_summary* summary);
+
+/* ---- Structure loop ------------------------------------------------------------------
+ * The structure refinement above, run behind every collected step of a KLT-mode pipeline (tracker_mode 0, track_ids) without
+ * giving up the look-ahead: the last W observation records of every lane stay in a ring on the device, and ONE call per
+ * collected step, vo_structure_loop_post, queues everything on the pipeline's main stream.  The host does not wait and reads
+ * nothing back; one further step may be in flight.
+ *
+ * Call order.  post(k) is called after step k has been collected, with at most one further step, k + 1, in flight
+ * (vo_pipeline_export_tracks_post_seq's condition).  It queues items 1 to 5, in this order, on the main stream: they run behind
+ * step k + 1 and in front of whatever is submitted next.
+ *   1. record   the observation record of step k -- byte for byte what vo_pipeline_export_tracks_post_seq writes, with cap = the
+ *               pipeline's feature capacity -- into the lane's ring slot, and the refined pose of step k (R_refined, t_refined
+ *               of its vo_step_result, 12 doubles) into the lane's pose ring.  An idle lane (its result's n_features_in == -1)
+ *               posts nothing and its window starts again.
+ *   2. window   the lane's last W records, oldest = slot 0.  The window is FULL iff W records have been posted since the last
+ *               reset, every step counter follows its predecessor by one, and no next_id decreases.  The host knows only how
+ *               many records were posted; the headers are checked on the device.  A window that is not full has L = 0, and
+ *               items 3 to 5 do nothing for that lane.
+ *   3. join     head, lm_start, obs_slot, obs_xy, X, lm_id: array for array and bit for bit what vo_window_from_tracks_dev gives
+ *               for the same W records with cap = the feature capacity and the loop's L_cap, M_cap -- the two cut flags and the
+ *               "first row carrying the id" rule included.  The poses of the window come from the pose ring in age order, K
+ *               from the lane's camera.
+ *   4. refine   vo_window_structure_dev's kernels on that window with the loop's vo_structure_params: results, summary and X per
+ *               lane are bit for bit what a stand-alone call gives.
+ *   5. write    (feedback = 1 only) into the features as step k + 1 left them, or as step k left them when nothing was in
+ *               flight.  A feature takes the refined landmark of window landmark i iff its track id is lm_id[i], AND its state
+ *               is 2, AND landmark i is kept and its X differs in at least one bit from the window's input, AND the feature's
+ *               landmark is still bit for bit the window's input X of i.  The last condition makes one step of lag safe: a
+ *               track whose landmark was reset and triangulated again during step k + 1 keeps its new landmark.  Nothing else
+ *               of the state is written.
+ * Faulted steps.  A lane whose sticky fault word is set when the write-back runs (step k + 1 left the device-only path; a
+ *   logical flag, what vo_pipeline_config.debug_fault_every forces) is left untouched, like every kernel behind such a step;
+ *   vo_pipeline_collect_all queues that lane's write-back again behind the redone step and in front of the chains it enqueues
+ *   again, so the redone step's features receive it exactly as they would have without the fault.
+ * Ordering.  All of it is main-stream work enqueued before the next submit, so nothing of step k + 2 that reads landmarks runs
+ *   before the write-back; the tracker, detection and upload streams read keypoints, images and pyramids only.
+ * Hand-over.  vo_structure_loop_reset_seq forgets a lane's window (call it wherever a lane is handed a new state: ids start
+ *   again).  A restart or bootstrap without it is still caught by the header check, as is a rewind.
+ * Results.  Every post leaves one vo_structure_loop_entry per lane (an idle lane: step = -1, all else 0), copied
+ *   asynchronously into a pinned ring of the last 64 posts.  vo_structure_loop_poll(post_index -- posts count from 0 --, wait,
+ *   entries[S]): VO_OK with the entries; 1 when wait = 0 and the copy has not landed yet (it has once a step submitted after the
+ *   post has been collected); wait != 0 blocks on the post's event.  post itself never synchronises with running work.
+ *
+ * vo_structure_loop_create: window 2 .. 16; L_cap 0 = the pipeline's feature capacity; M_cap 0 = L_cap * window; params: all 0 =
+ *   vo_structure_params' defaults (checked at the first post).  One loop per pipeline; VO_EINVAL with a message for a pipeline
+ *   without track_ids, tracker_mode != 0, a window out of range, a second loop, and at post for two steps in flight.
+ * vo_structure_loop_download_seq: lane seq's last window -- head (4), poses (W x 12), lm_start (L_cap + 1), obs_slot (M_cap),
+ *   obs_xy (M_cap x 2), X_in (L_cap x 3, the join's), lm_id (L_cap), X (L_cap x 3, refined), results (L_cap), summary, entry;
+ *   any pointer may be NULL; entries beyond L / M are not defined.  Synchronises: for tests and tools.
+ * vo_structure_loop_destroy waits for the stream and releases the loop; vo_pipeline_destroy does it for a loop still attached. */
+typedef struct vo_structure_loop vo_structure_loop;
+typedef struct vo_structure_loop_config {
+  int32_t window;                         /* W, 2 .. 16 */
+  int32_t L_cap, M_cap;                   /* 0 = the feature capacity, L_cap * window */
+  int32_t feedback;                       /* 1: item 5 */
+  vo_structure_params params;
+} vo_structure_loop_config;
+typedef struct vo_structure_loop_entry {  /* per lane and post */
+  int32_t step;                           /* the posted record's step counter; -1: the lane posted nothing */
+  int32_t full;
+  int32_t L, M, flags;                    /* the join's head */
+  int32_t n_written;                      /* features the write-back wrote */
+  vo_structure_summary summary;
+} vo_structure_loop_entry;
+int vo_structure_loop_create(vo_pipeline* p, const vo_structure_loop_config* cfg, vo_structure_loop** out);
+int vo_structure_loop_post(vo_structure_loop* loop, const vo_step_result* results /* S, as vo_pipeline_collect_all returned them */);
+int vo_structure_loop_posts(vo_structure_loop* loop);      /* posts made so far */
+int vo_structure_loop_reset_seq(vo_structure_loop* loop, int seq);
+int vo_structure_loop_poll(vo_structure_loop* loop, int post_index, int wait, vo_structure_loop_entry* entries);
+int vo_structure_loop_download_seq(vo_structure_loop* loop, int seq, int32_t* head, double* poses, int32_t* lm_start, int32_t* obs_slot,
+                                   double* obs_xy, double* X_in, int32_t* lm_id, double* X, vo_structure_result* results,
+                                   vo_structure_summary* summary, vo_structure_loop_entry* entry);
+int vo_structure_loop_destroy(vo_structure_loop* loop);
 
 /* ---- shared map over RCCL ------------------------------------------------------------------
  * The reference is one process and one thread (README.md:49); frame streams shard at sequence granularity (one

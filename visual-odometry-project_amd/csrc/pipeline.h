@@ -127,6 +127,7 @@ struct vo_pipeline {
   hipEvent_t evA = nullptr, evB = nullptr;
   double* d_newkp = nullptr;         // scratch of the bookkeeping entry point
   vo_pipeline_boot* boot = nullptr;  // vo_pipeline_bootstrap_seq's workspace (device memory in dev_mem; made at its first call)
+  vo_structure_loop* sloop = nullptr;   // structure_loop.hip: the loop attached by vo_structure_loop_create (null: none)
   // SIFT tracker mode (vo_pipeline_config.tracker_mode = 1; src/vo/features/tracker.py:60-61, sift.py:23-56): the frame's
   // keypoints and descriptors are made by the SIFT kernels on the tracker's stream, matched against the descriptors the
   // current Features carry (bytes, regrouped with them: matches.py:51-58, 134-141) on the matrix cores, and regrouped
@@ -293,4 +294,8 @@ VO_PIPE_INTERNAL int worker_idle(vo_pipeline* p);
 VO_PIPE_INTERNAL int prime(vo_pipeline* p, bool wait = true, int q0 = 0, int Sn = 0);
 // releases p->boot (its device memory is in dev_mem)
 VO_PIPE_INTERNAL void vo_pipeline_boot_free(vo_pipeline* p);
+// structure_loop.hip: releases an attached loop; the write-back of the last post once more for lane q, whose step of flight
+// k went through the host path or was continued (a no-op unless that post waited behind flight k)
+VO_PIPE_INTERNAL void vo_structure_loop_free(vo_pipeline* p);
+VO_PIPE_INTERNAL int vo_structure_loop_requeue(vo_pipeline* p, int q, long k);
 VO_PIPE_INTERNAL int enqueue_detection(vo_pipeline* p, int frame, int s, bool force, char* err_buf = nullptr, int q0 = 0, int Sn = 0);

@@ -168,6 +168,7 @@ void vo_pipeline_destroy(vo_pipeline* p) {
     if (q) (void)hipStreamSynchronize(q->stream);
   if (p->up_stream) (void)hipStreamSynchronize(p->up_stream);
   dbg_stage("destroy: streams idle");
+  vo_structure_loop_free(p);
   vo_pipeline_boot_free(p);
   for (void* q : p->dev_mem) (void)hipFree(q);
   for (void* q : p->host_mem) (void)hipHostFree(q);

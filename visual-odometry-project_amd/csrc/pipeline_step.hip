@@ -995,6 +995,8 @@ int vo_pipeline_collect_all(vo_pipeline* p, vo_step_result* outs) {
     }
     if (out->fault || was_open) {
       rc = out->fault ? recover_step(p, f, q, out) : VO_OK;
+      // (a structure loop's write-back that this lane's fault word kept out: once more, on the redone step's features)
+      if (rc == VO_OK && p->sloop) rc = vo_structure_loop_requeue(p, q, f.k);
       // steps submitted behind it saw the fault and did nothing for this sequence: their main-stream chains are
       // enqueued again for it alone (pyramids and detections are done and still in place)
       for (int k = 1; rc == VO_OK && k < p->n_flight; ++k) {

@@ -24,7 +24,8 @@ K_SHI_TOMASI_CHAIN = 27
 K_WINDOW_BA, K_WINDOW_BUILD = 28, 29          # vo_window_ba_dev's solver; vo_window_from_tracks_dev, both launches
 K_TWOVIEW_HYP, K_TWOVIEW_SCORE = 30, 31      # f8_hyp_kernel / e5_hyp_kernel and f_score_kernel / e5_score_kernel
 K_WINDOW_STRUCTURE = 32                       # vo_window_structure_dev, both launches
-K_COUNT = 33
+K_LOOP_RECORD, K_LOOP_JOIN, K_LOOP_WRITE = 33, 34, 35     # vo_structure_loop_post's three kernels
+K_COUNT = 36
 
 
 class VoError(RuntimeError):
@@ -159,6 +160,17 @@ STRUCTURE_RESULT = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials"
                              ("cost", "<f8"), ("min_cos", "<f8"), ("kept", "<i4"), ("reserved", "<i4")])
 STRUCTURE_SUMMARY = np.dtype([("L", "<i4"), ("n_refused", "<i4"), ("n_kept", "<i4"), ("max_iterations", "<i4"),
                               ("cost0", "<f8"), ("cost", "<f8")])
+
+
+# vo_structure_loop_entry (per lane and post of a vo.landmarks.StructureLoop): 24 bytes of int32, then the summary
+STRUCTURE_LOOP_ENTRY = np.dtype([("step", "<i4"), ("full", "<i4"), ("L", "<i4"), ("M", "<i4"), ("flags", "<i4"), ("n_written", "<i4"),
+                                 ("summary", STRUCTURE_SUMMARY)])
+
+
+class StructureLoopConfig(C.Structure):
+    """vo_structure_loop_config."""
+    _fields_ = [("window", C.c_int32), ("L_cap", C.c_int32), ("M_cap", C.c_int32), ("feedback", C.c_int32),
+                ("params", StructureParams)]
 
 
 def structure_params(huber_px=0.0, max_iter=0, max_trials=0, lambda0=0.0, step_tol=0.0, f_tol=0.0, gate_px=0.0,
@@ -309,6 +321,13 @@ _SIGS = {
     "vo_window_structure_dev": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_window_structure": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vo_pipeline_update_landmarks_seq": (_i, [_vp, _i, _i, _vp, _vp]),
+    "vo_structure_loop_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "vo_structure_loop_post": (_i, [_vp, _vp]),
+    "vo_structure_loop_posts": (_i, [_vp]),
+    "vo_structure_loop_reset_seq": (_i, [_vp, _i]),
+    "vo_structure_loop_poll": (_i, [_vp, _i, _i, _vp]),
+    "vo_structure_loop_download_seq": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vo_structure_loop_destroy": (_i, [_vp]),
 }
 
 

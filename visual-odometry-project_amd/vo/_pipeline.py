@@ -108,6 +108,8 @@ class Pipeline:
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_loop", None):
+                self._loop.close()
             self.ctx._lib.vo_pipeline_destroy(self._h)
             self._h = None
 
@@ -383,6 +385,14 @@ class Pipeline:
         finally:
             self.ctx.free(d_ids)
             self.ctx.free(d_X)
+
+    def structure_loop(self, window, L_cap=None, M_cap=None, feedback=True, **structure_params):
+        """The structure refinement behind every collected step, stream-ordered (vo_hip.h, "Structure loop"; KLT tracker
+        mode, track_ids=True, one loop per pipeline): returns a vo.landmarks.StructureLoop -- post(results) after every
+        collect, with one further step in flight; reset(seq) at a hand-over; poll / download for what it did."""
+        from vo.landmarks import StructureLoop
+        self._loop = StructureLoop(self, window, L_cap=L_cap, M_cap=M_cap, feedback=feedback, **structure_params)
+        return self._loop
 
     def get_detection(self, seq=0):
         """The detector's keypoints of the frame submitted last, sequence `seq`: (n, 2) float64 -- n_keypoints rows with

@@ -170,7 +170,7 @@ class _BaTap:
         make = WindowStructureRefiner if self.mode == "structure" else WindowBundleAdjuster
         self.adj[lane] = make(K, window=self.window, cap=self.pipe.cap, context=self.ctx, **self.params)
 
-    def step(self, items, feedback):
+    def step(self, items, feedback, results=None):
         """items: (lane, the step's StepResult, the list its `ba` entries go to) of the step collected just now."""
         from vo.landmarks import refine_windows, solve_windows
         for lane, r, _ in items:
@@ -207,6 +207,61 @@ class _BaTap:
         for row in self.ring:
             for d in row:
                 self.ctx.free(d)
+
+
+class _StreamTap:
+    """ba_feedback="stream": the structure refinement as stream-ordered work of the pipeline itself
+    (vo.landmarks.StructureLoop).  Every collected step is posted -- record, window, refinement and write-back queue up behind
+    the step in flight -- and nothing is waited for: the entries of a post are read from pinned memory at a later collect,
+    when they have long landed.  download: every post is followed by a download of each lane's window (a synchronisation per
+    step; for tests)."""
+
+    def __init__(self, ctx, pipe, lanes, window, params):
+        params = dict(params)
+        self.download = bool(params.pop("download", False))
+        self.window = int(window)
+        self.loop = pipe.structure_loop(self.window, feedback=True, **params)
+        self.waiting = []                                # (post index, [(lane, sink, the downloaded arrays)])
+
+    def start(self, lane, K):
+        self.loop.reset(lane)                            # (a hand-over: ids start again, a window must not span it)
+
+    def drain(self, wait=False):
+        """Appends the entries of the posts that have landed (wait: of every post) to their `ba` lists."""
+        while self.waiting:
+            j, items = self.waiting[0]
+            entries = self.loop.poll(j, wait=wait)
+            if entries is None:
+                return
+            self.waiting.pop(0)
+            for lane, sink, extra in items:
+                e = entries[lane]
+                if not e["full"]:
+                    continue
+                m, L, step = e["summary"], int(e["L"]), int(e["step"])
+                refused = int(m["n_refused"]) == L               # (every landmark, or none to refuse: L = 0)
+                d = dict(frames=list(range(step - self.window + 1, step + 1)), status=4 if refused else 0, cost0=float(m["cost0"]),
+                         cost=float(m["cost"]), iterations=int(m["max_iterations"]), n_kept=int(m["n_kept"]), n=L,
+                         flags=int(e["flags"]), n_written=int(e["n_written"]))
+                d.update(extra)
+                sink.append(d)
+
+    def step(self, items, feedback, results=None):
+        """items: as _BaTap.step's; results: the records of all lanes as collect_all returned them."""
+        self.drain()
+        j = self.loop.post(results)
+        waiting = []
+        for lane, _, sink in items:
+            extra = {}
+            if self.download:
+                w = self.loop.download(lane)
+                extra = dict(poses=w.poses, ids=w.lm_id, landmarks=w.X, kept=w.results["kept"].astype(bool))
+            waiting.append((lane, sink, extra))
+        self.waiting.append((j, waiting))
+
+    def close(self):
+        self.drain(wait=True)
+        self.loop.close()
 
 
 def track_table(observations):
@@ -275,6 +330,13 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     through the gates; the others are the record's), status (0, or 4 when no landmark was refined: the whole window was
     refused, or it is empty, L = 0 -- as the adjustment reports an empty window), cost0, cost (sums over the landmarks not
     refused), iterations (the largest), n_kept.  ba_feedback writes back the same way.
+    ba_feedback="stream" (ba_mode="structure" only; ValueError otherwise, and without ba_window): the refinement and its
+    write-back are stream-ordered work of the pipeline (Pipeline.structure_loop, vo_hip.h "Structure loop") -- steps are not
+    drained, two stay pending as without a back end, nothing is read back, and a refined landmark reaches the features one
+    step late at most, only where the feature still carries the landmark the window was built from.  A `ba` entry is then
+    frames, status, cost0, cost, iterations, n_kept, n (landmarks of the window), flags, n_written (features the write-back
+    wrote), taken from the entries the device leaves in pinned memory; ba_params["download"] = True adds poses, ids,
+    landmarks, kept at the cost of a synchronisation per step (for tests).
 
     This is run_batch_on_device([sequence], lanes=1, ...)[0], the same loop (_DeviceRun) with one lane, and what comes
     with that: the lane's camera is set once more at the start (Pipeline.set_camera with the constructor's K, so the
@@ -469,10 +531,18 @@ class _DeviceRun:
             raise ValueError("ba_window needs tracks=True: the window is built from the observation records")
         if ba_mode not in ("full", "structure"):
             raise ValueError("ba_mode must be 'full' or 'structure', got %r" % (ba_mode,))
-        self.ba_window, self.ba_feedback, self.ba_params = ba_window, bool(ba_feedback), dict(ba_params or {})
+        # ba_feedback="stream": the write-back is stream-ordered work of the pipeline (_StreamTap); steps are not drained
+        self.ba_stream = isinstance(ba_feedback, str) and ba_feedback == "stream"
+        if isinstance(ba_feedback, str) and not self.ba_stream:
+            raise ValueError("ba_feedback must be False, True or 'stream', got %r" % (ba_feedback,))
+        if self.ba_stream and ba_window is None:
+            raise ValueError("ba_feedback='stream' needs ba_window: there is no window to refine")
+        if self.ba_stream and ba_mode != "structure":
+            raise ValueError("ba_feedback='stream' needs ba_mode='structure', got ba_mode=%r" % (ba_mode,))
+        self.ba_window, self.ba_feedback, self.ba_params = ba_window, bool(ba_feedback) and not self.ba_stream, dict(ba_params or {})
         self.ba_mode = ba_mode
         if ba_window is not None and ba_mode == "structure":
-            allowed = ("huber_px", "max_iter", "gate_px", "min_parallax")
+            allowed = ("huber_px", "max_iter", "gate_px", "min_parallax") + (("download",) if self.ba_stream else ())
             for k in self.ba_params:
                 if k not in allowed:
                     raise ValueError("ba_mode='structure' holds every pose: ba_params takes %s, not %s" % (", ".join(allowed), k))
@@ -529,7 +599,9 @@ class _DeviceRun:
         self.pipe = _native.Pipeline(self.ctx, H, W, self.SLOTS, self.camera_of(self.first), sequences=self.lanes,
                                      track_ids=self.tracks, **_pipeline_kwargs(state0, *self.pipe_args))
         self.tap = _TrackTap(self.ctx, self.pipe, self.lanes) if self.tracks else None
-        if self.ba_window is not None:
+        if self.ba_window is not None and self.ba_stream:
+            self.ba = _StreamTap(self.ctx, self.pipe, self.lanes, self.ba_window, self.ba_params)
+        elif self.ba_window is not None:
             self.ba = _BaTap(self.ctx, self.pipe, self.lanes, self.ba_window, self.ba_params, self.ba_mode)
         self.ring = [[None] * self.SLOTS for _ in range(self.lanes)]
 
@@ -594,7 +666,7 @@ class _DeviceRun:
             self.tap.post([(lane, r, o.setdefault("observations", [])) for lane, r, o in taken])
         if self.ba:
             self.ba.step([(lane, r, o.setdefault("ba", [])) for lane, r, o in taken],
-                         feedback=self.ba_feedback and not self.pending)
+                         feedback=self.ba_feedback and not self.pending, results=rs)
 
     def change(self, t):
         """Step t's events -- lanes going idle, lanes starting a recording (the host route one by one, the device route
