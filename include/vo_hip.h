@@ -170,6 +170,36 @@ int vo_klt_track_dev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_p
                      double eps, double min_eig, float* d_next_xy, uint8_t* d_status,
                      float* d_err);
 
+/* Forward-backward consistency check (opt-in; the calls above are untouched by it).
+ * Inputs are those of vo_klt_track plus fb_max in pixels: fb_max > 0, +inf allowed;
+ * a NaN or a value <= 0 returns VO_EINVAL with a message and writes nothing.
+ *   1. Forward.   (next_xy, status_f, err) is exactly what vo_klt_track(prev, next,
+ *      prev_xy, ...) returns; next_xy and err are returned unchanged, bit for bit,
+ *      for every point.
+ *   2. Backward.  Only for points with status_f = 1: the same tracker, same win,
+ *      levels, criteria and min_eig, with the images exchanged, starting from the
+ *      float32 next_xy[i] as stored, gives (back_xy, status_b).  The backward err is
+ *      not used.
+ *   3. Distance.  fb[i] = dx*dx + dy*dy with dx = back_x - prev_x, dy = back_y -
+ *      prev_y: float32 arithmetic in that order, no contraction, in px^2.
+ *      fb[i] = +inf where status_f = 0 or status_b = 0.
+ *   4. Status.    status[i] = status_f & status_b & (fb[i] <= thr2), thr2 =
+ *      (float)(fb_max * fb_max), the product formed in double.  A tie is kept.
+ * By construction the result equals two vo_klt_track calls and a compare.  One
+ * launch does both passes: the lanes that tracked a point forward keep it in
+ * registers and run the level loop again with the pyramids exchanged.  fb: N float32.
+ * In the frame pipeline the check is vo_pipeline_set_klt_fb; the pipeline's two-view
+ * bootstrap (vo_pipeline_bootstrap_seq) keeps the plain tracker -- out of scope.   */
+int vo_klt_track_fb(vo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int H, int W,
+                    const float* prev_xy, int N, int win, int max_level, int max_iter,
+                    double eps, double min_eig, double fb_max, float* next_xy,
+                    uint8_t* status, float* err, float* fb);
+int vo_klt_track_fb_dev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_pyr,
+                        const uint8_t* d_next, const uint8_t* d_next_pyr, int H, int W,
+                        int n_levels, const float* d_prev_xy, int N, int win, int max_iter,
+                        double eps, double min_eig, double fb_max, float* d_next_xy,
+                        uint8_t* d_status, float* d_err, float* d_fb);
+
 /* ---- DLT triangulation --------------------------------------------------------
  * [ref: src/vo/landmarks/triangulation.py:352-389, 38-86; src/vo/helpers.py:57-83]
  * per point A = [[x1]_x C1 ; [x2]_x C2] (6x4), smallest right singular vector,
@@ -794,6 +824,15 @@ int vo_pipeline_frame_uploaded(vo_pipeline* p, int idx, int wait);
  * step's tracker does not start behind a pyramid that its own, later, submit enqueues.  Results do not depend on the hint;
  * a wrong one costs one wasted pyramid.  KLT tracker mode; a no-op otherwise and before the first step.                 */
 int vo_pipeline_prepare(vo_pipeline* p, int idx);
+/* The tracker's forward-backward check in the frame loop (the rule: "pyramidal KLT", vo_klt_track_fb).  fb_max > 0 pixels
+ * (+inf allowed): from the next submitted step on, the step's tracker launch is the forward-backward one and the KLT filter
+ * reads its status, status_f & status_b & (fb <= fb_max^2), next to err < klt_err_threshold.  0 switches the check off, which
+ * is the state at creation: the pipeline then makes the launches it always made.  Any number of sequences; steps that go
+ * through the host path (recovery) track the same way.  Requires nothing in flight and the KLT tracker mode: refused with a
+ * message in the descriptor modes, as is a negative or NaN value.  vo_pipeline_config is not involved.  The two-view
+ * bootstrap (vo_pipeline_bootstrap_seq) keeps its plain tracker.  _get_ reads the value back (0: off).                    */
+int vo_pipeline_set_klt_fb(vo_pipeline* p, double fb_max);
+int vo_pipeline_get_klt_fb(vo_pipeline* p, double* fb_max);
 int vo_host_alloc(vo_ctx* ctx, size_t bytes, void** out);
 int vo_host_free(vo_ctx* ctx, void* p);          /* ctx may be NULL */
 /* ---- frame ingest: three-channel frames and lens undistortion on the device ------------------------------------

@@ -492,12 +492,61 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// ---- forward-backward check (vo_hip.h, "pyramidal KLT": vo_klt_track_fb) ----
+// What a lane group keeps of a point between the two passes of an FB kernel.
+template <bool FB>
+struct klt_fb_keep {};
+template <>
+struct klt_fb_keep<true> {
+  float p0x, p0y;        // where the point started (prev_xy, or the detector's keypoint as float32)
+  float nx, ny, err;     // the forward pass's result
+  bool ok = false;       // ... and status; false until the forward pass has been closed by klt_fb_turn
+};
+__device__ __forceinline__ bool klt_fb_turn(klt_fb_keep<false>&, float&, float&, float&, float&, bool&, float&) { return false; }
+// closes the forward pass and sets the second one up: p0 <- the forward result; false: the point sits the pass out
+__device__ __forceinline__ bool klt_fb_turn(klt_fb_keep<true>& k, float& p0x, float& p0y, float& nx, float& ny, bool& ok,
+                                            float& e_out) {
+  k.p0x = p0x;
+  k.p0y = p0y;
+  k.nx = nx;
+  k.ny = ny;
+  k.err = e_out;
+  k.ok = ok;
+  if (!ok) return false;
+  p0x = nx;
+  p0y = ny;
+  nx = 0.f;
+  ny = 0.f;
+  e_out = 0.f;
+  return true;
+}
+__device__ __forceinline__ void klt_fb_write(const klt_fb_keep<false>&, float, float, bool, float, int, float*, uint8_t*, float*,
+                                             float*) {}
+// (bx, by, ok_b): the backward pass's result; a point whose forward pass failed never ran it (k.ok is false)
+__device__ __forceinline__ void klt_fb_write(const klt_fb_keep<true>& k, float bx, float by, bool ok_b, float thr2, int i,
+                                             float* __restrict__ next_xy, uint8_t* __restrict__ status,
+                                             float* __restrict__ err, float* __restrict__ fb) {
+  const bool both = k.ok && ok_b;
+  const float dx = bx - k.p0x, dy = by - k.p0y;
+  const float d2 = both ? dx * dx + dy * dy : __builtin_inff();     // (fp contract is off: two products, one sum)
+  next_xy[2 * i] = k.nx;
+  next_xy[2 * i + 1] = k.ny;
+  err[i] = k.err;
+  fb[i] = d2;
+  status[i] = (both && d2 <= thr2) ? 1 : 0;                          // a tie is kept
+}
+
 // WIN_T > 0: window side known at compile time (index arithmetic folds, loops unroll)
-template <int WIN_T>
+// FB: the forward-backward variant (vo_klt_track_fb).  The wave that tracked a point forward keeps p0 and its result in
+// registers, runs the level loop a second time with the two pyramids exchanged, starting from the forward result, and
+// writes the squared round-trip distance and the combined status.  With FB = false the second pass does not exist and
+// fb_thr2 and fb are not read: the plain instantiations are, instruction for instruction, the code they were.
+template <int WIN_T, bool FB = false>
 __global__ __launch_bounds__(64 * KLT_WAVES) void klt_track_kernel(pyr_t P, const float* __restrict__ prev_xy, int N, const int* __restrict__ d_n, vo_klt_source src, vo_klt_batch B, int win_arg,
                                                        int max_iter, double eps2, float min_eig_thr,
                                                        float* __restrict__ next_xy, uint8_t* __restrict__ status,
-                                                       float* __restrict__ err, int lds_per_wave) {
+                                                       float* __restrict__ err, int lds_per_wave, float fb_thr2,
+                                                       float* __restrict__ fb) {
   extern __shared__ __align__(16) unsigned char smem_all[];
   const int i = blockIdx.x * KLT_WAVES + (threadIdx.x >> 6);
   // (the kernel argument P is left untouched: written to, it would be copied to scratch -- one copy per lane -- for the
@@ -510,6 +559,7 @@ __global__ __launch_bounds__(64 * KLT_WAVES) void klt_track_kernel(pyr_t P, cons
     next_xy += q * B.xy;
     status += q * B.out;
     err += q * B.out;
+    if (FB) fb += q * B.out;
     if (src.n) {
       src.n = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(src.n) + q * B.ctl);
       src.num_features = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(src.num_features) + q * B.ctl);
@@ -541,15 +591,18 @@ __global__ __launch_bounds__(64 * KLT_WAVES) void klt_track_kernel(pyr_t P, cons
 
   const float half = (float)(win - 1) * 0.5f;
   const float FLT_SCALE = 1.f / (float)(1 << 20);
-  const float p0x = i < n_own ? prev_xy[2 * i] : (float)src.det_kp[2 * (i - n_own)];
-  const float p0y = i < n_own ? prev_xy[2 * i + 1] : (float)src.det_kp[2 * (i - n_own) + 1];
+  float p0x = i < n_own ? prev_xy[2 * i] : (float)src.det_kp[2 * (i - n_own)];
+  float p0y = i < n_own ? prev_xy[2 * i + 1] : (float)src.det_kp[2 * (i - n_own) + 1];
   bool ok = true;
   float e_out = 0.f;
   float nx = 0.f, ny = 0.f;
+  klt_fb_keep<FB> fwd;                                 // (empty without FB)
+  bool back = false;                                   // FB: the second pass (next -> prev) is running
 
+second_pass:
   for (int level = P.n_levels - 1; level >= 0; --level) {
-    const uint8_t* I = P.prev[level] + pyr_off;
-    const uint8_t* J = P.next[level] + pyr_off;
+    const uint8_t* I = (FB && back ? P.next[level] : P.prev[level]) + pyr_off;
+    const uint8_t* J = (FB && back ? P.prev[level] : P.next[level]) + pyr_off;
     const int H = P.H[level], W = P.W[level], pitch = P.pitch[level];
     const float sc = (float)(1. / (double)(1 << level));
     float px = p0x * sc, py = p0y * sc;
@@ -702,11 +755,21 @@ __global__ __launch_bounds__(64 * KLT_WAVES) void klt_track_kernel(pyr_t P, cons
       e_out = (float)wave_sum(sabs) / (float)(32 * ww);
     }
   }
+  if constexpr (FB) {                                  // once more, next -> prev, from the forward result as stored
+    if (!back && klt_fb_turn(fwd, p0x, p0y, nx, ny, ok, e_out)) {
+      back = true;
+      goto second_pass;
+    }
+  }
   if (lane == 0) {
-    next_xy[2 * i] = nx;
-    next_xy[2 * i + 1] = ny;
-    status[i] = ok ? 1 : 0;
-    err[i] = e_out;
+    if (FB) {
+      klt_fb_write(fwd, nx, ny, ok, fb_thr2, i, next_xy, status, err, fb);
+    } else {
+      next_xy[2 * i] = nx;
+      next_xy[2 * i + 1] = ny;
+      status[i] = ok ? 1 : 0;
+      err[i] = e_out;
+    }
   }
 }
 
@@ -836,10 +899,11 @@ __device__ __forceinline__ void stage16(const uint8_t* __restrict__ img, int pit
   stage_store<NC, NR, LPK, PITCH>(b, s, r);
 }
 
-template <int WIN, int LPK>
+template <int WIN, int LPK, bool FB = false>
 __global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* __restrict__ prev_xy, int N, const int* __restrict__ d_n, vo_klt_source src, vo_klt_batch B, int max_iter,
                                                          double eps2, float min_eig_thr, float* __restrict__ next_xy,
-                                                         uint8_t* __restrict__ status, float* __restrict__ err) {
+                                                         uint8_t* __restrict__ status, float* __restrict__ err,
+                                                         float fb_thr2, float* __restrict__ fb) {
   typedef klt_rows<WIN> G;
   constexpr int win = WIN, ww = WIN * WIN, RS = G::RS, n1 = G::n1, n3 = G::n3, K16_PITCH = G::PITCH;
   constexpr int KPW = 64 / LPK;                        // keypoints per wave
@@ -857,6 +921,7 @@ __global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* _
     next_xy += q * B.xy;
     status += q * B.out;
     err += q * B.out;
+    if (FB) fb += q * B.out;
     if (src.n) {
       src.n = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(src.n) + q * B.ctl);
       src.num_features = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(src.num_features) + q * B.ctl);
@@ -894,6 +959,8 @@ __global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* _
   bool ok = true;
   float e_out = 0.f;
   float nx = 0.f, ny = 0.f;
+  klt_fb_keep<FB> fwd;                                 // (empty without FB)
+  bool back = false;                                   // FB: the second pass (next -> prev) is running
 
   // Template blocks depend on the previous keypoint only, so the block of level l - 1 is requested
   // while level l is being worked on (tplI holds the block of the level about to start).
@@ -904,12 +971,13 @@ __global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* _
     int ipx = (int)floorf(px), ipy = (int)floorf(py);
     ipx = min(max(ipx, -win), P.W[level] - 1);       // (a level whose block would leave the border is skipped below)
     ipy = min(max(ipy, -win), P.H[level] - 1);
-    stage_load<n3, n3, LPK>(P.prev[level] + pyr_off, P.pitch[level], ipx - 1, ipy - 1, r, tplI);
+    stage_load<n3, n3, LPK>((FB && back ? P.next[level] : P.prev[level]) + pyr_off, P.pitch[level], ipx - 1, ipy - 1, r, tplI);
   };
+second_pass:
   request_template(P.n_levels - 1);
 
   for (int level = P.n_levels - 1; level >= 0; --level) {
-    const uint8_t* J = P.next[level] + pyr_off;
+    const uint8_t* J = (FB && back ? P.prev[level] : P.next[level]) + pyr_off;
     const int H = P.H[level], W = P.W[level], pitch = P.pitch[level];
     const float sc = (float)(1. / (double)(1 << level));
     const staged_block<n3, n3, LPK> curI = tplI;
@@ -1105,11 +1173,24 @@ __global__ __launch_bounds__(64) void klt_track16_kernel(pyr_t P, const float* _
       e_out = (float)kp_sum_i32<LPK>(live * sabs) / (float)(32 * ww);
     }
   }
+  // FB: once more, next -> prev, from the forward result as stored.  A lane group whose forward pass failed goes straight
+  // on to the kernel's end and waits there while its wave-mates run the pass: the LDS slices are per group, wave_sync()
+  // holds back the compiler only, and the window sums stay inside a group's lanes.
+  if constexpr (FB) {
+    if (!back && klt_fb_turn(fwd, p0x, p0y, nx, ny, ok, e_out)) {
+      back = true;
+      goto second_pass;
+    }
+  }
   if (r == 0) {
-    next_xy[2 * i] = nx;
-    next_xy[2 * i + 1] = ny;
-    status[i] = ok ? 1 : 0;
-    err[i] = e_out;
+    if (FB) {
+      klt_fb_write(fwd, nx, ny, ok, fb_thr2, i, next_xy, status, err, fb);
+    } else {
+      next_xy[2 * i] = nx;
+      next_xy[2 * i + 1] = ny;
+      status[i] = ok ? 1 : 0;
+      err[i] = e_out;
+    }
   }
 }
 
@@ -1235,14 +1316,33 @@ int vo_klt_track_dev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_p
                            max_iter, eps, min_eig, d_next_xy, d_status, d_err);
 }
 
+// fb_max > 0 (+inf allowed); anything else, NaN included, is refused before a byte is written
+static bool klt_fb_max_ok(double fb_max) { return fb_max > 0.0; }
+
+int vo_klt_track_fb_dev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_pyr, const uint8_t* d_next,
+                        const uint8_t* d_next_pyr, int H, int W, int n_levels, const float* d_prev_xy, int N, int win,
+                        int max_iter, double eps, double min_eig, double fb_max, float* d_next_xy, uint8_t* d_status,
+                        float* d_err, float* d_fb) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, klt_fb_max_ok(fb_max), "klt_track_fb: fb_max must be > 0 pixels (+inf allowed), got %g", fb_max);
+  VO_REQUIRE(ctx, N <= 0 || d_fb, "klt_track_fb: null pointer");
+  return vo_klt_track_ndev(ctx, d_prev, d_prev_pyr, d_next, d_next_pyr, H, W, n_levels, d_prev_xy, N, nullptr, win,
+                           max_iter, eps, min_eig, d_next_xy, d_status, d_err, nullptr, nullptr, fb_max, d_fb);
+}
+
 }  // extern "C"
 
 // Pipeline-internal form: at most N keypoints, the actual count is read from *d_n when the kernel runs.
 int vo_klt_track_ndev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_pyr, const uint8_t* d_next,
                       const uint8_t* d_next_pyr, int H, int W, int n_levels, const float* d_prev_xy, int N,
                       const int32_t* d_n, int win, int max_iter, double eps, double min_eig, float* d_next_xy,
-                      uint8_t* d_status, float* d_err, const vo_klt_source* src_in, const vo_klt_batch* batch) {
+                      uint8_t* d_status, float* d_err, const vo_klt_source* src_in, const vo_klt_batch* batch, double fb_max,
+                      float* d_fb) {
   if (!ctx) return VO_EINVAL;
+  const bool with_fb = d_fb != nullptr;                // the forward-backward launch (fb_max = 0, d_fb = null: the plain one)
+  VO_REQUIRE(ctx, !with_fb || fb_max > 0.0, "klt_track_fb: fb_max must be > 0 pixels (+inf allowed), got %g", fb_max);
+  VO_REQUIRE(ctx, with_fb || fb_max == 0.0, "klt_track_fb: fb_max without an fb array");
+  const float thr2 = with_fb ? (float)(fb_max * fb_max) : 0.f;
   const vo_klt_source src = src_in ? *src_in : vo_klt_source();
   const vo_klt_batch B = batch ? *batch : vo_klt_batch();
   const int S = B.S > 0 ? B.S : 1;
@@ -1284,25 +1384,42 @@ int vo_klt_track_ndev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_
     hipStream_t st = ctx->stream;
     const float me = (float)min_eig;
     const dim3 kgrid(vo_cdiv(N, KLT_WAVES), S), kblock(64 * KLT_WAVES);
+    // (every case: the plain launch as it always was, or the forward-backward instantiation of the same template)
     switch (win) {
       case 15:
         // 16 lanes per keypoint (four per wave).  32 lanes per keypoint (two per wave, the upper half of each group idle in
         // the row loops, the 18 rows of the template block in one pass instead of two) measured slower: round 3, step 87.6 ->
         // 91.3 us at one sequence, the kernel 199 -> 351 us at 16.
-        vo_launch_stop(ctx, klt_track16_kernel<15, 16>, dim3(vo_cdiv(N, 4), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
-                       max_iter, eps * eps, me, d_next_xy, d_status, d_err);
+        if (!with_fb)
+          vo_launch_stop(ctx, klt_track16_kernel<15, 16>, dim3(vo_cdiv(N, 4), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
+                         max_iter, eps * eps, me, d_next_xy, d_status, d_err, 0.f, (float*)nullptr);
+        else
+          vo_launch_stop(ctx, klt_track16_kernel<15, 16, true>, dim3(vo_cdiv(N, 4), S), dim3(64), 0, st, P, d_prev_xy, N, d_n,
+                         src, B, max_iter, eps * eps, me, d_next_xy, d_status, d_err, thr2, d_fb);
         break;
       case 17:   // the reference's default window (klt.py:29)
-        vo_launch_stop(ctx, klt_track16_kernel<17, 32>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
-                       max_iter, eps * eps, me, d_next_xy, d_status, d_err);
+        if (!with_fb)
+          vo_launch_stop(ctx, klt_track16_kernel<17, 32>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
+                         max_iter, eps * eps, me, d_next_xy, d_status, d_err, 0.f, (float*)nullptr);
+        else
+          vo_launch_stop(ctx, klt_track16_kernel<17, 32, true>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n,
+                         src, B, max_iter, eps * eps, me, d_next_xy, d_status, d_err, thr2, d_fb);
         break;
       case 21:
-        vo_launch_stop(ctx, klt_track16_kernel<21, 32>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
-                       max_iter, eps * eps, me, d_next_xy, d_status, d_err);
+        if (!with_fb)
+          vo_launch_stop(ctx, klt_track16_kernel<21, 32>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n, src, B,
+                         max_iter, eps * eps, me, d_next_xy, d_status, d_err, 0.f, (float*)nullptr);
+        else
+          vo_launch_stop(ctx, klt_track16_kernel<21, 32, true>, dim3(vo_cdiv(N, 2), S), dim3(64), 0, st, P, d_prev_xy, N, d_n,
+                         src, B, max_iter, eps * eps, me, d_next_xy, d_status, d_err, thr2, d_fb);
         break;
       default:
-        vo_launch_stop(ctx, klt_track_kernel<0>, kgrid, kblock, lds, st, P, d_prev_xy, N, d_n, src, B, win, max_iter, eps * eps,
-                       me, d_next_xy, d_status, d_err, lds_wave);
+        if (!with_fb)
+          vo_launch_stop(ctx, klt_track_kernel<0>, kgrid, kblock, lds, st, P, d_prev_xy, N, d_n, src, B, win, max_iter, eps * eps,
+                         me, d_next_xy, d_status, d_err, lds_wave, 0.f, (float*)nullptr);
+        else
+          vo_launch_stop(ctx, klt_track_kernel<0, true>, kgrid, kblock, lds, st, P, d_prev_xy, N, d_n, src, B, win, max_iter,
+                         eps * eps, me, d_next_xy, d_status, d_err, lds_wave, thr2, d_fb);
     }
   }
   return vo_check_launch(ctx, "klt_track_kernel");
@@ -1310,9 +1427,10 @@ int vo_klt_track_ndev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_
 
 extern "C" {
 
-int vo_klt_track(vo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_xy, int N,
-                 int win, int max_level, int max_iter, double eps, double min_eig, float* next_xy, uint8_t* status,
-                 float* err) {
+// fb == null: the plain tracker; otherwise the forward-backward one with fb_max
+static int klt_track_host(vo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_xy, int N,
+                          int win, int max_level, int max_iter, double eps, double min_eig, double fb_max, float* next_xy,
+                          uint8_t* status, float* err, float* fb) {
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, N >= 0, "klt_track: bad N");
   if (N == 0) return VO_OK;
@@ -1330,20 +1448,40 @@ int vo_klt_track(vo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int H, i
   VO_TRY(vo_ensure(ctx, s[11], (size_t)N * 8));
   VO_TRY(vo_ensure(ctx, s[12], (size_t)N));
   VO_TRY(vo_ensure(ctx, s[13], (size_t)N * 4));
+  if (fb) VO_TRY(vo_ensure(ctx, s[14], (size_t)N * 4));
   hipStream_t st = ctx->stream;
   VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img.p, prev, px, hipMemcpyHostToDevice, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(ctx->img2.p, next, px, hipMemcpyHostToDevice, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(s[10].p, prev_xy, (size_t)N * 8, hipMemcpyHostToDevice, st));
   VO_TRY(vo_pyramid_build_dev(ctx, (const uint8_t*)ctx->img.p, H, W, nl, (uint8_t*)s[8].p));
   VO_TRY(vo_pyramid_build_dev(ctx, (const uint8_t*)ctx->img2.p, H, W, nl, (uint8_t*)s[9].p));
-  VO_TRY(vo_klt_track_dev(ctx, (const uint8_t*)ctx->img.p, (const uint8_t*)s[8].p, (const uint8_t*)ctx->img2.p,
-                          (const uint8_t*)s[9].p, H, W, nl, (const float*)s[10].p, N, win, max_iter, eps, min_eig,
-                          (float*)s[11].p, (uint8_t*)s[12].p, (float*)s[13].p));
+  VO_TRY(vo_klt_track_ndev(ctx, (const uint8_t*)ctx->img.p, (const uint8_t*)s[8].p, (const uint8_t*)ctx->img2.p,
+                           (const uint8_t*)s[9].p, H, W, nl, (const float*)s[10].p, N, nullptr, win, max_iter, eps, min_eig,
+                           (float*)s[11].p, (uint8_t*)s[12].p, (float*)s[13].p, nullptr, nullptr, fb ? fb_max : 0.0,
+                           fb ? (float*)s[14].p : nullptr));
   VO_HIP_TRY(ctx, hipMemcpyAsync(next_xy, s[11].p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(status, s[12].p, (size_t)N, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipMemcpyAsync(err, s[13].p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+  if (fb) VO_HIP_TRY(ctx, hipMemcpyAsync(fb, s[14].p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
   VO_HIP_TRY(ctx, hipStreamSynchronize(st));
   return VO_OK;
+}
+
+int vo_klt_track(vo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_xy, int N,
+                 int win, int max_level, int max_iter, double eps, double min_eig, float* next_xy, uint8_t* status,
+                 float* err) {
+  return klt_track_host(ctx, prev, next, H, W, prev_xy, N, win, max_level, max_iter, eps, min_eig, 0.0, next_xy, status, err,
+                        nullptr);
+}
+
+int vo_klt_track_fb(vo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_xy, int N,
+                    int win, int max_level, int max_iter, double eps, double min_eig, double fb_max, float* next_xy,
+                    uint8_t* status, float* err, float* fb) {
+  if (!ctx) return VO_EINVAL;
+  VO_REQUIRE(ctx, klt_fb_max_ok(fb_max), "klt_track_fb: fb_max must be > 0 pixels (+inf allowed), got %g", fb_max);
+  VO_REQUIRE(ctx, N <= 0 || fb, "klt_track_fb: null pointer");
+  return klt_track_host(ctx, prev, next, H, W, prev_xy, N, win, max_level, max_iter, eps, min_eig, fb_max, next_xy, status,
+                        err, fb);
 }
 
 int vo_pyr_down(vo_ctx* ctx, const uint8_t* img, int H, int W, uint8_t* out) {

@@ -92,6 +92,10 @@ struct vo_pipeline {
   vo_seq_ctl* d_ctl = nullptr;       // [S]
   float *d_next = nullptr, *d_err = nullptr;   // [S][cap * 2], [S][cap]
   uint8_t* d_status = nullptr;
+  // vo_pipeline_set_klt_fb: the tracker's forward-backward check (0: off, the plain launch); d_fb [S][cap] beside d_err,
+  // made when the check is first switched on
+  double klt_fb = 0.0;
+  float* d_fb = nullptr;
   double *d_R = nullptr, *d_t = nullptr;       // [S][hyp * 9], [S][hyp * 3]
   uint8_t* d_valid = nullptr;
   int32_t *d_counts = nullptr, *d_samples = nullptr, *d_pend = nullptr;   // d_pend: [S][cap], state_walk_landmarks_kernel's scratch

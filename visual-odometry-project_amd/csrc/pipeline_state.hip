@@ -332,6 +332,30 @@ int vo_pipeline_set_camera_seq(vo_pipeline* p, int seq, const double* K, const d
   return VO_OK;
 }
 
+// ---- the tracker's forward-backward check (vo_hip.h, vo_pipeline_set_klt_fb): enqueue_tracker reads klt_fb and d_fb ----
+
+int vo_pipeline_set_klt_fb(vo_pipeline* p, double fb_max) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, p->cfg.tracker_mode == 0, "pipeline_set_klt_fb: KLT tracker mode only (the pipeline runs tracker_mode %d)",
+             p->cfg.tracker_mode);
+  VO_REQUIRE(ctx, fb_max >= 0.0, "pipeline_set_klt_fb: fb_max must be > 0 pixels (+inf allowed), or 0 for off; got %g", fb_max);
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_set_klt_fb: %d submitted step(s) not collected", p->n_flight);
+  if (fb_max > 0.0 && !p->d_fb) {
+    VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    VO_TRY(dev_alloc(p, &p->d_fb, (size_t)p->S * p->cap));
+  }
+  p->klt_fb = fb_max;
+  return VO_OK;
+}
+
+int vo_pipeline_get_klt_fb(vo_pipeline* p, double* fb_max) {
+  if (!p) return VO_EINVAL;
+  VO_REQUIRE(p->ctx, fb_max, "pipeline_get_klt_fb: null pointer");
+  *fb_max = p->klt_fb;
+  return VO_OK;
+}
+
 // An idle lane's control block carries VO_FAULT_IDLE: every kernel of the main chain returns on it as on a sticky fault (the
 // regroup leaves n_p3p = 0, the pose and landmark kernels write a fault record and nothing else), the detector's decision
 // says no, the tracker gets n2 = 0 features, and the pyramid's launches leave the lane out.  The host neither redoes its

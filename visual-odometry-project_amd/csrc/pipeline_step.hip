@@ -309,7 +309,8 @@ static int enqueue_tracker(vo_pipeline* p, const vo_pipeline::flight_t& f, bool 
     const int rc = vo_klt_track_ndev(p->trk, p->img(q0, f.prev_idx), p->pyr(q0, f.a), p->img(q0, f.next_idx), p->pyr(q0, f.b),
                                      c.H, c.W, p->n_levels, A.kp, p->cap, nullptr, c.klt_win, c.klt_max_iter, c.klt_eps,
                                      c.klt_min_eig, p->d_next + q * p->cap * 2, p->d_status + q * p->cap,
-                                     p->d_err + q * p->cap, &src, &kb);
+                                     p->d_err + q * p->cap, &src, &kb, p->klt_fb,
+                                     p->klt_fb > 0.0 ? p->d_fb + q * p->cap : nullptr);
     if (rc != VO_OK) return vo_set_error(ctx, rc, "tracker: %s", vo_last_error(p->trk));
   }
   if (p->trk->next_stop) {             // (the launch did not take the event)

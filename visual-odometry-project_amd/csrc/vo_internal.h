@@ -352,7 +352,8 @@ int vo_klt_track_ndev(vo_ctx* ctx, const uint8_t* d_prev, const uint8_t* d_prev_
                       const uint8_t* d_next_pyr, int H, int W, int n_levels, const float* d_prev_xy, int N,
                       const int32_t* d_n, int win, int max_iter, double eps, double min_eig, float* d_next_xy,
                       uint8_t* d_status, float* d_err, const vo_klt_source* src = nullptr,
-                      const vo_klt_batch* batch = nullptr);
+                      const vo_klt_batch* batch = nullptr, double fb_max = 0.0, float* d_fb = nullptr);
+// (fb_max, d_fb) != (0, null): the forward-backward launch (vo_hip.h, vo_klt_track_fb); d_fb strides like d_err
 int vo_pyramid_build_batch_dev(vo_ctx* ctx, const uint8_t* d_img, size_t img_stride, int S, int H, int W, int n_levels,
                                uint8_t* d_pyr, size_t pyr_stride);
 // Several sequences per launch (harris.hip): S images at d_img + s * img_stride -> S score maps at d_scores + s * H * W;

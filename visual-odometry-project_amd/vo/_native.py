@@ -211,6 +211,8 @@ _SIGS = {
     "vo_pyramid_build_dev": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "vo_klt_track": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp]),
     "vo_klt_track_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp]),
+    "vo_klt_track_fb": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
+    "vo_klt_track_fb_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "vo_triangulate_dlt": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "vo_triangulate_dlt_dev": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "vo_p3p_hypotheses": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp]),
@@ -290,6 +292,8 @@ _SIGS = {
     "vo_pipeline_set_frame_pinned": (_i, [_vp, _i, _i, _vp]),
     "vo_pipeline_frame_uploaded": (_i, [_vp, _i, _i]),
     "vo_pipeline_prepare": (_i, [_vp, _i]),
+    "vo_pipeline_set_klt_fb": (_i, [_vp, _d]),
+    "vo_pipeline_get_klt_fb": (_i, [_vp, _vp]),
     "vo_host_alloc": (_i, [_vp, C.c_size_t, C.POINTER(C.c_void_p)]),
     "vo_host_free": (_i, [_vp, _vp]),
     "vo_gray_from_bgr": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -894,6 +898,25 @@ class Context:
                                          int(max_iter), float(eps), float(min_eig), _ptr(out), _ptr(status), _ptr(err)))
         return out, status, err
 
+    def klt_track_fb(self, prev, nxt, prev_xy, win=17, max_level=2, max_iter=10, eps=0.03, min_eig=1e-4, fb_max=1.0):
+        """klt_track with the forward-backward check (vo_klt_track_fb): next_pts and err are the forward call's; fb is
+        the squared round-trip distance in px^2 (+inf where either pass failed); status = forward & backward &
+        (fb <= fb_max^2).  fb_max > 0 pixels, +inf allowed."""
+        prev = _c(prev, np.uint8)
+        nxt = _c(nxt, np.uint8)
+        assert prev.shape == nxt.shape and prev.ndim == 2
+        H, W = prev.shape
+        pts = _c(np.asarray(prev_xy).reshape(-1, 2), np.float32)
+        n = pts.shape[0]
+        out = np.empty((n, 2), np.float32)
+        status = np.empty(n, np.uint8)
+        err = np.empty(n, np.float32)
+        fb = np.empty(n, np.float32)
+        self._chk(self._lib.vo_klt_track_fb(self._h, _ptr(prev), _ptr(nxt), H, W, _ptr(pts), n, int(win), int(max_level),
+                                            int(max_iter), float(eps), float(min_eig), float(fb_max), _ptr(out),
+                                            _ptr(status), _ptr(err), _ptr(fb)))
+        return out, status, err, fb
+
     # ---- DLT ----
     def triangulate_dlt(self, x1, x2, C1, C2):
         x1 = _c(np.asarray(x1).reshape(-1, 2), np.float64)
@@ -1101,6 +1124,14 @@ class Context:
                                              C.c_void_p(d_next_pyr), H, W, int(n_levels), C.c_void_p(d_prev_xy), int(N),
                                              int(win), int(max_iter), float(eps), float(min_eig),
                                              C.c_void_p(d_next_xy), C.c_void_p(d_status), C.c_void_p(d_err)))
+
+    def klt_track_fb_dev(self, d_prev, d_prev_pyr, d_next, d_next_pyr, H, W, n_levels, d_prev_xy, N, win, max_iter, eps,
+                         min_eig, fb_max, d_next_xy, d_status, d_err, d_fb):
+        self._chk(self._lib.vo_klt_track_fb_dev(self._h, C.c_void_p(d_prev), C.c_void_p(d_prev_pyr), C.c_void_p(d_next),
+                                                C.c_void_p(d_next_pyr), H, W, int(n_levels), C.c_void_p(d_prev_xy), int(N),
+                                                int(win), int(max_iter), float(eps), float(min_eig), float(fb_max),
+                                                C.c_void_p(d_next_xy), C.c_void_p(d_status), C.c_void_p(d_err),
+                                                C.c_void_p(d_fb)))
 
     def triangulate_dlt_dev(self, d_x1, d_x2, n, d_C1, per_point, d_C2, d_X):
         self._chk(self._lib.vo_triangulate_dlt_dev(self._h, C.c_void_p(d_x1), C.c_void_p(d_x2), int(n),

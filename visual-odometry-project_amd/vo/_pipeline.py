@@ -158,6 +158,21 @@ class Pipeline:
         path (vo_pipeline_prepare).  Results do not depend on it."""
         self.ctx._chk(self.ctx._lib.vo_pipeline_prepare(self._h, int(idx)))
 
+    def set_klt_fb(self, fb_max):
+        """The tracker's forward-backward check from the next step on (vo_pipeline_set_klt_fb): fb_max > 0 pixels
+        (+inf allowed) switches it on, 0 off -- the state at creation.  KLT tracker mode, nothing in flight."""
+        fb_max = float(fb_max)
+        if not fb_max >= 0.0:
+            raise ValueError("set_klt_fb: fb_max must be > 0 pixels (+inf allowed), or 0 for off; got %r" % (fb_max,))
+        self.ctx._chk(self.ctx._lib.vo_pipeline_set_klt_fb(self._h, fb_max))
+
+    @property
+    def klt_fb(self):
+        """The forward-backward threshold in pixels (0.0: the check is off)."""
+        v = C.c_double(0.0)
+        self.ctx._chk(self.ctx._lib.vo_pipeline_get_klt_fb(self._h, C.byref(v)))
+        return float(v.value)
+
     def frame_uploaded(self, idx, wait=False):
         rc = self.ctx._lib.vo_pipeline_frame_uploaded(self._h, int(idx), 1 if wait else 0)
         if rc < 0:

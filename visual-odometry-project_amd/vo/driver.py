@@ -288,7 +288,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
                   redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                   bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
                   tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None,
-                  bootstrap_method: str = "8point", ba_mode: str = "full"):
+                  bootstrap_method: str = "8point", ba_mode: str = "full", klt_fb: float = None):
     """Same loop, same bootstrap, but the steady state runs as the device-resident pipeline (vo_pipeline_*):
     after the host bootstrap the Features / State arrays are handed to the GPU once, every later frame costs one
     image upload and one call, and nothing but the pose record comes back.  KLT tracker mode with the Harris
@@ -330,6 +330,10 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
     through the gates; the others are the record's), status (0, or 4 when no landmark was refined: the whole window was
     refused, or it is empty, L = 0 -- as the adjustment reports an empty window), cost0, cost (sums over the landmarks not
     refused), iterations (the largest), n_kept.  ba_feedback writes back the same way.
+    klt_fb: the tracker's forward-backward check in pixels (Pipeline.set_klt_fb, called once after the pipeline is made):
+    a feature is kept only if tracking it back from the new frame returns to within klt_fb of where it started.  None (the
+    default) makes no call: the run is the one it was.  Not > 0, or a pipeline that is not in tracker_mode "klt":
+    ValueError.  The bootstrap keeps the plain tracker.
     ba_feedback="stream" (ba_mode="structure" only; ValueError otherwise, and without ba_window): the refinement and its
     write-back are stream-ordered work of the pipeline (Pipeline.structure_loop, vo_hip.h "Structure loop") -- steps are not
     drained, two stay pending as without a back end, nothing is read back, and a refined landmark reaches the features one
@@ -349,7 +353,7 @@ def run_on_device(sequence: Sequence, max_frames: int = None, n_keypoints: int =
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
                      (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
                      ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method,
-                     ba_mode=ba_mode)
+                     ba_mode=ba_mode, klt_fb=klt_fb)
     out = run.run()[0]
     out["frame_seconds"] = out["frame_seconds"] - np.array(run.read_seconds)
     if tracks:
@@ -524,8 +528,12 @@ class _DeviceRun:
     SLOTS = 4
 
     def __init__(self, sequences, lanes, max_frames, context, bootstrap, tracks, boot_args, pipe_args, ba_window=None,
-                 ba_feedback=False, ba_params=None, bootstrap_method="8point", ba_mode="full"):
+                 ba_feedback=False, ba_params=None, bootstrap_method="8point", ba_mode="full", klt_fb=None):
         _check_bootstrap_route(bootstrap, bootstrap_method)
+        # the tracker's forward-backward check (Pipeline.set_klt_fb), set once after creation; None: no call at all
+        if klt_fb is not None and not float(klt_fb) > 0.0:
+            raise ValueError("klt_fb must be > 0 pixels (+inf allowed) or None, got %r" % (klt_fb,))
+        self.klt_fb = None if klt_fb is None else float(klt_fb)
         self.bootstrap_method = bootstrap_method
         if ba_window is not None and not tracks:
             raise ValueError("ba_window needs tracks=True: the window is built from the observation records")
@@ -598,6 +606,10 @@ class _DeviceRun:
         H, W = self.shapes[self.first]
         self.pipe = _native.Pipeline(self.ctx, H, W, self.SLOTS, self.camera_of(self.first), sequences=self.lanes,
                                      track_ids=self.tracks, **_pipeline_kwargs(state0, *self.pipe_args))
+        if self.klt_fb is not None:
+            if self.pipe.tracker != "klt":
+                raise ValueError("klt_fb belongs to tracker_mode 'klt', the pipeline runs %r" % (self.pipe.tracker,))
+            self.pipe.set_klt_fb(self.klt_fb)
         self.tap = _TrackTap(self.ctx, self.pipe, self.lanes) if self.tracks else None
         if self.ba_window is not None and self.ba_stream:
             self.ba = _StreamTap(self.ctx, self.pipe, self.lanes, self.ba_window, self.ba_params)
@@ -753,7 +765,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                         redetect_start_pose: str = "current", bootstrap_win: int = None, bootstrap_max_level: int = None,
                         bootstrap_threshold: float = 0.25, bootstrap: str = "host", detector: str = "harris",
                         tracks: bool = False, ba_window: int = None, ba_feedback: bool = False, ba_params: dict = None,
-                        bootstrap_method: str = "8point", ba_mode: str = "full"):
+                        bootstrap_method: str = "8point", ba_mode: str = "full", klt_fb: float = None):
     """run_on_device for many recordings at once: one pipeline of `lanes` sequences (default: one per recording, at most
     16), every lane with its recording's camera (vo_pipeline_set_camera_seq).  Each recording is bootstrapped on the host
     (_device_bootstrap); when one ends its lane takes the next recording of the queue (vo_pipeline_restart_seq) or
@@ -770,6 +782,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
     ba_window / ba_feedback / ba_params / ba_mode: as in run_on_device; the windows of all lanes that hold a full one go through one
     solver call per step, and a lane's window starts again with every recording.
     bootstrap_method: as in run_on_device, for every recording's host bootstrap.
+    klt_fb: as in run_on_device, for every lane.
 
     Returns one dict per recording, in input order, with run_on_device's keys (frame_seconds: the batch's wall time of
     each step the recording took part in, the delivery of the next step's frames included).  run_on_device is this
@@ -778,7 +791,7 @@ def run_batch_on_device(sequences, lanes: int = None, max_frames: int = None, n_
                      (n_keypoints, klt_win, klt_max_level, bootstrap_win, bootstrap_max_level, bootstrap_threshold),
                      (n_keypoints, klt_win, klt_max_level, hyp, redetect_start_pose, detector),
                      ba_window=ba_window, ba_feedback=ba_feedback, ba_params=ba_params, bootstrap_method=bootstrap_method,
-                     ba_mode=ba_mode).run()
+                     ba_mode=ba_mode, klt_fb=klt_fb).run()
     if ba_window is not None:
         for o in out:
             o.setdefault("ba", [])

@@ -26,6 +26,10 @@ class KLTTracker:
     _lk_params = dict(winSize=(17, 17), maxLevel=2, criteria=(TERM_CRITERIA_EPS | TERM_CRITERIA_COUNT, 10, 0.03))
     # points are kept only below this tracking error (klt.py:39)
     _error_threshold = 100
+    # Extension: forward-backward check.  None = the reference's filter alone (the call below is then exactly the
+    # plain one); a value in pixels = the tracker also tracks next -> prev and a point is kept only if it returns to
+    # within that distance of where it started (vo_klt_track_fb)
+    _fb_threshold = None
     # Extension for BASELINE.json configs[1] ("Harris+NMS -> KLT"): which detector find_corners runs.
     # "shi-tomasi" is the reference's cv2.goodFeaturesToTrack (klt.py:98); "harris" is the reference's own
     # HarrisCornerDetector.extractKeypoints (harris.py:86-158) with _harris_params.
@@ -133,9 +137,14 @@ class KLTTracker:
         crit = lk["criteria"]
         max_iter = crit[1] if crit[0] & TERM_CRITERIA_COUNT else 30
         eps = crit[2] if crit[0] & TERM_CRITERIA_EPS else 0.01
-        next_pts, status, error = self._context().klt_track(
-            self.old_img_gray, self.img_gray, self._old_frame.features.keypoints, win=lk["winSize"][0],
-            max_level=lk["maxLevel"], max_iter=max_iter, eps=eps)
+        if self._fb_threshold is None:
+            next_pts, status, error = self._context().klt_track(
+                self.old_img_gray, self.img_gray, self._old_frame.features.keypoints, win=lk["winSize"][0],
+                max_level=lk["maxLevel"], max_iter=max_iter, eps=eps)
+        else:
+            next_pts, status, error, _ = self._context().klt_track_fb(
+                self.old_img_gray, self.img_gray, self._old_frame.features.keypoints, win=lk["winSize"][0],
+                max_level=lk["maxLevel"], max_iter=max_iter, eps=eps, fb_max=self._fb_threshold)
         next_pts = next_pts.reshape((-1, 2, 1))
         keep = np.logical_and(status.flatten().astype(bool), (error < self._error_threshold).flatten())
         if sys.gettrace() is not None:
