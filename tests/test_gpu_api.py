@@ -190,7 +190,8 @@ def test_bootstrap_matches_reference_golden(ctx):
 def test_bootstrap_kernels_match_the_oracle(ctx):
     """Hypotheses, counts and masks of a batch of samples, the closing fit and the relative pose against
     oracle/bootstrap_np.py (itself pinned to the reference's golden) on a noisy two-view scene with gross outliers: both
-    error kinds, population-normalised and per-sample-normalised fits, at the bootstrap's size (2000 correspondences)."""
+    error kinds, population-normalised and per-sample-normalised fits, at the bootstrap's size (2000 correspondences).
+    (The 8-point kernels themselves are pinned to 50-digit values by tests/test_gpu_twoview_reference.py.)"""
     from oracle import bootstrap_np as bo
     cam1, cam2 = cameras()
     rng = np.random.default_rng(11)

@@ -21,7 +21,8 @@ def ctx():
     c.close()
 
 
-# ---------------- DLT (parity by tolerance: SVD route differs from LAPACK) ----------------
+# ---------------- DLT against the LAPACK oracle and the reference golden (the kernel is pinned to 50-digit values by
+# tests/test_gpu_twoview_reference.py, the oracle by tests/test_twoview_reference_host.py) ----------------
 def test_dlt_matches_reference_golden(ctx):
     g = np.load(os.path.join(G, "dlt_cameras.npz"))
     X = ctx.triangulate_dlt(g["x1"], g["x2"], g["C1"], g["C2"])

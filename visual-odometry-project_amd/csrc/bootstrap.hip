@@ -9,7 +9,12 @@
 //                      squared distance to the epipolar lines in both images; strict `<` threshold; counts + mask rows
 //   f8_fit_kernel      the 8-point fit over ALL (masked) correspondences (RANSAC's closing model_fn(population[inliers]),
 //                      src/vo/algorithms/ransac.py:123-127; _find_fundamental_matrix :165-222): Hartley normalisation,
-//                      the 9x9 normal matrix by a workgroup reduction, its smallest eigenvector by Jacobi, rank 2
+//                      the 9x9 normal matrix by a workgroup reduction and ALL its eigenvectors V by Jacobi; where its
+//                      eigenvalues show that squaring Q's conditioning cost accuracy (lambda8 < 1e-5 lambda1: small
+//                      baselines, near-planar scenes), a second pass over the points forms the normal matrix of Q V --
+//                      nearly diagonal and graded -- whose smallest eigenvector by Jacobi with a per-pair relative test
+//                      corrects V's; rank 2.  Pinned to 50-digit values at sigma8 / sigma1 of Q down to
+//                      1e-5 (tests/test_gpu_twoview_reference.py)
 //   relative_pose_kernel  E = K2^T F K1, its SVD (3x3 Jacobi), the four [R | +-T] (:245-277), the four cheirality
 //                      votes over the inliers by DLT (:313-332), the winner's triangulation of all points (:334-350)
 //
@@ -250,22 +255,31 @@ __global__ __launch_bounds__(256) void f_score_kernel(const double* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// 9x9 symmetric Jacobi in LDS (one work item): returns the eigenvector to the smallest eigenvalue in out[9]
-__device__ void sym9_min_eigvec(double* A /*81*/, double* V /*81*/, double* out) {
+// 9x9 symmetric cyclic Jacobi in LDS (one work item): A -> diagonal, V its eigenvectors (columns).  graded == false:
+// the sweeps end once off <= 1e-34 dia.  graded == true, for a nearly diagonal matrix whose diagonal spans many orders:
+// a pair is left alone once apq^2 <= 1e-32 app aqq and the sweeps end when none was rotated -- the global test stops
+// while the small diagonal entries are still coupled to each other.
+template <bool graded>
+__device__ void sym9_jacobi(double* A /*81*/, double* V /*81*/) {
   for (int e = 0; e < 81; ++e) V[e] = (e / 9 == e % 9) ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0.0, dia = 0.0;
-    for (int r = 0; r < 9; ++r)
-      for (int c = 0; c < 9; ++c) {
-        const double v = A[9 * r + c];
-        if (r == c) dia += v * v;
-        else off += v * v;
-      }
-    if (off == 0.0 || off <= 1e-34 * dia) break;
+    if (!graded) {
+      double off = 0.0, dia = 0.0;
+      for (int r = 0; r < 9; ++r)
+        for (int c = 0; c < 9; ++c) {
+          const double v = A[9 * r + c];
+          if (r == c) dia += v * v;
+          else off += v * v;
+        }
+      if (off == 0.0 || off <= 1e-34 * dia) break;
+    }
+    bool any = false;
     for (int p = 0; p < 8; ++p)
       for (int q = p + 1; q < 9; ++q) {
         const double apq = A[9 * p + q];
         if (apq == 0.0) continue;
+        if (graded && apq * apq <= 1e-32 * (A[9 * p + p] * A[9 * q + q])) continue;
+        any = true;
         const double theta = (A[9 * q + q] - A[9 * p + p]) / (2.0 * apq);
         const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
         const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
@@ -285,11 +299,8 @@ __device__ void sym9_min_eigvec(double* A /*81*/, double* V /*81*/, double* out)
           V[9 * k + q] = s * vp + c * vq;
         }
       }
+    if (graded && !any) break;
   }
-  int m = 0;
-  for (int c = 1; c < 9; ++c)
-    if (A[9 * c + c] < A[9 * m + m]) m = c;
-  for (int k = 0; k < 9; ++k) out[k] = V[9 * k + m];
 }
 
 __device__ __forceinline__ double block_sum(double v, double* s_red /*[4]*/, int tid) {
@@ -302,14 +313,18 @@ __device__ __forceinline__ double block_sum(double v, double* s_red /*[4]*/, int
 }
 
 // the 8-point fit over the points whose mask byte is set (all if mask == NULL); one workgroup
+// lambda8 / lambda1 of Q^T Q below which the null vector is refined (sigma8 / sigma1 < 3.2e-3).  The one-pass vector was
+// measured at up to 6e-18 lambda1 / lambda8 from the 50-digit one: above the threshold it is good to 6e-13.
+constexpr double F8_SECOND_PASS = 1e-5;
 struct f8_fit_lds {
-  double red[4], A[81], V[81], f[9];
+  double red[4], A[81], V[81], W[81], f[9];
+  int second;          // the first pass's eigenvalues ask for the second
 };
 
 __device__ __forceinline__ void f8_fit_body(const double* __restrict__ p1, const double* __restrict__ p2, int N,
                                             const uint8_t* __restrict__ mask, int normalize, double* __restrict__ Fout,
                                             int* __restrict__ n_used, f8_fit_lds& lds) {
-  double *s_red = lds.red, *s_A = lds.A, *s_V = lds.V, *s_f = lds.f;
+  double *s_red = lds.red, *s_A = lds.A, *s_V = lds.V, *s_W = lds.W, *s_f = lds.f;
   const int tid = threadIdx.x;
   hartley h1 = {1.0, 0.0, 0.0}, h2 = {1.0, 0.0, 0.0};
   double cnt = 0.0;
@@ -337,38 +352,89 @@ __device__ __forceinline__ void f8_fit_body(const double* __restrict__ p1, const
     h1 = {s1, -s1 * mx1, -s1 * my1};
     h2 = {s2, -s2 * mx2, -s2 * my2};
   }
-  // Q^T Q, upper triangle: 45 sums
+  // Up to two passes over the points.  The first forms Q^T Q (45 sums) and takes ALL its eigenvectors V by Jacobi: forming
+  // the product squares Q's conditioning, so the smallest of them is only good to about eps (sigma1 / sigma8)^2 -- measured
+  // 2e-18 lambda1 / lambda8 against 50-digit values.  Where lambda8 >= F8_SECOND_PASS lambda1 that is the answer.  Else the second
+  // forms the same 45 sums of q' = V^T q: its columns are orthogonal up to that error, so the matrix is nearly diagonal
+  // with the squared singular values on its diagonal, each small entry computed from small terms.  Its eigenvector f' to
+  // the smallest diagonal entry (graded Jacobi) is a small correction of a unit vector, and V f' is the null vector to the
+  // accuracy of a one-sided Jacobi iteration on Q itself.
   double acc[45];
+  for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll
-  for (int k = 0; k < 45; ++k) acc[k] = 0.0;
-  for (int i = tid; i < N; i += 256) {
-    if (mask && !mask[i]) continue;
-    const double a[3] = {h1.s * p1[2 * i] + h1.tx, h1.s * p1[2 * i + 1] + h1.ty, 1.0};
-    const double b[3] = {h2.s * p2[2 * i] + h2.tx, h2.s * p2[2 * i + 1] + h2.ty, 1.0};
-    double q[9];
+    for (int k = 0; k < 45; ++k) acc[k] = 0.0;
+    for (int i = tid; i < N; i += 256) {
+      if (mask && !mask[i]) continue;
+      const double a[3] = {h1.s * p1[2 * i] + h1.tx, h1.s * p1[2 * i + 1] + h1.ty, 1.0};
+      const double b[3] = {h2.s * p2[2 * i] + h2.tx, h2.s * p2[2 * i + 1] + h2.ty, 1.0};
+      double q[9];
 #pragma unroll
-    for (int u = 0; u < 3; ++u)
+      for (int u = 0; u < 3; ++u)
 #pragma unroll
-      for (int v = 0; v < 3; ++v) q[3 * u + v] = a[u] * b[v];
-    int k = 0;
+        for (int v = 0; v < 3; ++v) q[3 * u + v] = a[u] * b[v];
+      if (pass == 1) {
+        double qr[9];
 #pragma unroll
-    for (int r = 0; r < 9; ++r)
+        for (int j = 0; j < 9; ++j) {
+          double d = 0.0;
 #pragma unroll
-      for (int c = r; c < 9; ++c) acc[k++] += q[r] * q[c];
-  }
-  {
-    int k = 0;
+          for (int k = 0; k < 9; ++k) d += s_V[9 * k + j] * q[k];
+          qr[j] = d;
+        }
 #pragma unroll
-    for (int r = 0; r < 9; ++r)
-#pragma unroll
-      for (int c = r; c < 9; ++c) {
-        const double v = block_sum(acc[k++], s_red, tid);
-        if (tid == 0) s_A[9 * r + c] = s_A[9 * c + r] = v;
+        for (int j = 0; j < 9; ++j) q[j] = qr[j];
       }
+      int k = 0;
+#pragma unroll
+      for (int r = 0; r < 9; ++r)
+#pragma unroll
+        for (int c = r; c < 9; ++c) acc[k++] += q[r] * q[c];
+    }
+    {
+      int k = 0;
+#pragma unroll
+      for (int r = 0; r < 9; ++r)
+#pragma unroll
+        for (int c = r; c < 9; ++c) {
+          const double v = block_sum(acc[k++], s_red, tid);
+          if (tid == 0) s_A[9 * r + c] = s_A[9 * c + r] = v;
+        }
+    }
+    __syncthreads();
+    if (pass == 0) {
+      if (tid == 0) {
+        sym9_jacobi<false>(s_A, s_V);
+        int m = 0;
+        for (int c = 1; c < 9; ++c)
+          if (s_A[9 * c + c] < s_A[9 * m + m]) m = c;
+        double l1 = s_A[9 * m + m], l8 = 0.0;       // the largest eigenvalue and the second smallest
+        bool have = false;
+        for (int c = 0; c < 9; ++c) {
+          if (c == m) continue;
+          const double l = s_A[9 * c + c];
+          if (l > l1) l1 = l;
+          if (!have || l < l8) l8 = l;
+          have = true;
+        }
+        for (int k = 0; k < 9; ++k) s_f[k] = s_V[9 * k + m];
+        lds.second = !(l8 >= F8_SECOND_PASS * l1);  // (not finite: the second pass, which hands the NaN on)
+      }
+      __syncthreads();
+      if (!lds.second) break;                       // uniform: every work item reads the same word
+    }
   }
-  __syncthreads();
   if (tid == 0) {
-    sym9_min_eigvec(s_A, s_V, s_f);
+    if (lds.second) {
+      sym9_jacobi<true>(s_A, s_W);
+      int m = 0;
+      for (int c = 1; c < 9; ++c)
+        if (s_A[9 * c + c] < s_A[9 * m + m]) m = c;
+      for (int k = 0; k < 9; ++k) {
+        double d = 0.0;
+        for (int j = 0; j < 9; ++j) d += s_V[9 * k + j] * s_W[9 * j + m];
+        s_f[k] = d;
+      }
+    }
     double F[9];
 #pragma unroll
     for (int a = 0; a < 3; ++a)

@@ -248,7 +248,8 @@ int vo_fundamental_hypotheses_dev(vo_ctx* ctx, const double* d_p1, const double*
                                   int normalize_samples, int error_kind, double threshold, int32_t* d_samples, double* d_F,
                                   int32_t* d_counts, uint64_t* d_masks, int32_t* counts);
 //   fit: over the correspondences d_mask selects (nullable: all); d_F 9 doubles; d_n_used (nullable) their count
-int vo_fundamental_fit_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const uint8_t* d_mask, int normalize,
+//   (exported like the entry points above: tests/test_gpu_twoview_reference.py binds it by hand to read d_n_used)
+extern "C" int vo_fundamental_fit_dev(vo_ctx* ctx, const double* d_p1, const double* d_p2, int N, const uint8_t* d_mask, int normalize,
                            double* d_F, int32_t* d_n_used);
 //   relative pose: d_M 12, d_X N x 3, d_mask_out N (nullable), d_M4 48 (nullable)
 int vo_relative_pose_dev(vo_ctx* ctx, const double* d_x1, const double* d_x2, int N, const uint8_t* d_inliers, const double* K1,
