@@ -307,6 +307,69 @@ def test_builder_on_hand_made_records(ctx):
         ctx.free(p)
 
 
+def long_run_records():
+    """Three records (raw bytes, oldest first) whose newest has 1100 rows: more than the builder's 512 threads, so every
+    thread owns a run of 3 rows (the last run is short).  The middle row of every run, row 3 k + 1, is a landmark; k decides
+    where else its id is seen: k % 7 == 3 nowhere (no landmark), else k % 5 == 0 in both older records, else in the older one
+    of the parity of k.  The older records are shuffled among rows of other ids, and id 1046 (k = 15, seen in both) occurs
+    twice in the oldest: the first row's pixel is the observation."""
+    from vo._pipeline import TRACK_HEADER, TRACK_ROW
+    rng = np.random.default_rng(5)
+
+    def record(step, rows):
+        raw = np.zeros(16 + 48 * len(rows), np.uint8)
+        raw[:16].view(TRACK_HEADER)[0] = (len(rows), step, 5000, 0)
+        raw[16:].view(TRACK_ROW)[:] = rows
+        return raw
+
+    n = 1100
+    new = np.zeros(n, TRACK_ROW)
+    new["id"], new["x"], new["y"], new["state"] = 1000 + np.arange(n), np.arange(n) + 0.5, np.arange(n) * 0.25, 1
+    lm = np.arange(n) % 3 == 1
+    new["state"][lm] = 2
+    for c, f in (("X", 1.0), ("Y", -0.5), ("Z", 0.125)):
+        new[c] = np.where(lm, 4.0 + f * np.arange(n), np.nan)
+    k = np.arange(n) // 3
+    seen = lm & (k % 7 != 3)
+    older = []
+    for s in range(2):
+        here = new[seen & ((k % 5 == 0) | (k % 2 == s))].copy()
+        here["x"] += 0.25 * (2 - s)
+        here["state"], here["X"], here["Y"], here["Z"] = 1, np.nan, np.nan, np.nan
+        other = np.zeros(200 + 100 * s, TRACK_ROW)                     # ids the newest record does not carry
+        other["id"], other["x"] = 9000 + np.arange(len(other)), 7.0
+        rows = np.concatenate((here, other))[rng.permutation(len(here) + len(other))]
+        if s == 0:
+            twice = rows[rows["id"] == 1046].copy()
+            twice["x"], twice["y"] = 77.0, 88.0
+            rows = np.concatenate((rows, twice))                       # behind the first row that carries the id
+        older.append(record(1 + s, rows))
+    return older + [record(3, new)]
+
+
+def test_builder_with_runs_longer_than_a_row(ctx):
+    from vo._pipeline import TrackRecord
+    raws = long_run_records()
+    cap, W = 1100, 3
+    recs = [TrackRecord.from_bytes(r, cap) for r in raws]
+    assert len(recs[2]) == cap and (recs[0]["id"] == 1046).sum() == 2
+    want = numpy_window(recs, cap, cap, cap * W)
+    L, M = int(want["head"][0]), int(want["head"][1])
+    assert L == 315 and 2 * L < M < 3 * L and want["head"][2] == 0          # 367 middle rows, 52 of them seen nowhere else
+    at = want["lm_id"].tolist().index(1046)
+    assert want["obs_slot"][want["lm_start"][at]:want["lm_start"][at + 1]].tolist() == [0, 1, 2]
+    assert want["obs_xy"][want["lm_start"][at]].tolist() == [47.0, 11.5]        # the first row's pixel, not (77, 88)
+    d = [ctx.to_device(r) for r in raws]
+    same_window(device_window(ctx, d, cap, cap, cap * W), want)
+    # both cuts fall on the middle row of a run far from either end of the list
+    for L_cap, M_cap, flag in ((L // 2, (L // 2) * W, 1), (L, int(want["lm_start"][L // 3]) + 1, 2)):
+        cut = numpy_window(recs, cap, L_cap, M_cap)
+        assert cut["head"][2] == flag and 0 < cut["head"][0] < L
+        same_window(device_window(ctx, d, cap, L_cap, M_cap), cut)
+    for p in d:
+        ctx.free(p)
+
+
 def test_adjuster_solves_the_loops_window(ctx):
     """WindowBundleAdjuster on the posted loop: the window it solves is the builder's, the result the solver's on it; a
     break in the step counter drops what lies before it."""

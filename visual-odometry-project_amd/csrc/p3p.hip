@@ -15,6 +15,7 @@
 // fp64 throughout, FP contraction off, only + - * / sqrt: same rounding sequence
 // as the CPU oracle.
 #include "vo_internal.h"
+#include "rng_device.h"
 
 #pragma clang fp contract(off)
 
@@ -243,16 +244,6 @@ static double sum_sq_limit(double thr) {
   return r;
 }
 
-// NumPy's bounded draw on one 32-bit output of the generator (Lemire, ransac_host.hip):
-// `risky` is raised when the draw could have been rejected, i.e. when the sequential
-// generator might have consumed one more output than this position-based view assumes.
-__device__ __forceinline__ unsigned bounded_from_raw(unsigned raw, unsigned rng, bool& risky) {
-  const unsigned rex = rng + 1u;
-  const unsigned long long m = (unsigned long long)raw * rex;
-  if ((unsigned)m < rex) risky = true;
-  return (unsigned)(m >> 32);
-}
-
 // RAW == false: sample indices are given.
 // RAW == true : hypothesis h derives its sample from generator outputs raws[7h .. 7h+6] and the
 //   population size *d_n, both of which may still be in flight when the kernel is enqueued:
@@ -293,7 +284,7 @@ __device__ __forceinline__ void p3p_solve_quad(int gt, const double* __restrict_
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const unsigned j = (unsigned)(n - 4 + k);
-      const int val = (int)bounded_from_raw(rw[k], j, risky);
+      const int val = (int)vo_rng::bounded_from_raw(rw[k], j, risky);
       bool seen = false;
 #pragma unroll
       for (int q = 0; q < k; ++q) seen |= (sidx[q] == val);
@@ -301,7 +292,7 @@ __device__ __forceinline__ void p3p_solve_quad(int gt, const double* __restrict_
     }
 #pragma unroll
     for (int i = 3; i >= 1; --i) {
-      const int j = (int)bounded_from_raw(rw[4 + (3 - i)], (unsigned)i, risky);
+      const int j = (int)vo_rng::bounded_from_raw(rw[4 + (3 - i)], (unsigned)i, risky);
       int vj = sidx[0];
 #pragma unroll
       for (int q = 1; q <= i; ++q) vj = (j == q) ? sidx[q] : vj;

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "pipeline.h"
+#include "track_record_device.h"
 
 #pragma clang fp contract(off)
 
@@ -21,29 +22,13 @@ __global__ __launch_bounds__(256) void export_state_kernel(pose17 head, const do
   if (i < m) rec[17 + i] = land[i];
 }
 
-// The observation record of one step (vo_hip.h, "Track ids"): header {n, step, next_id, seq}, then a 48-byte row per feature,
-// written as six 8-byte words.  slot: where the collected step's regroup left next_id / the step counter (vo_seq_ctl.next_id).
+// The observation record of one step (track_record_device.h).  slot: where the collected step's regroup left next_id / the step counter (vo_seq_ctl.next_id).
 __global__ __launch_bounds__(256) void export_tracks_kernel(vo_feat F, const vo_seq_ctl* __restrict__ ctl, int slot, int n,
                                                             int cap, int seq, unsigned long long* __restrict__ rec) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  auto pack = [](int lo, int hi) { return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32); };
-  if (i == 0) {
-    rec[0] = pack(n, ctl->id_step[slot]);
-    rec[1] = pack(ctl->next_id[slot], seq);
-  }
+  if (i == 0) vo_track::write_header(rec, n, ctl->id_step[slot], ctl->next_id[slot], seq);
   if (i >= min(n, cap)) return;
-  const int2 id = F.ids[i];
-  const float x = F.kp[2 * i], y = F.kp[2 * i + 1];
-  const int st = F.state[i], cd = F.cand[i];
-  double X[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) X[k] = F.land[3 * i + k];
-  unsigned long long* row = rec + 2 + (size_t)6 * i;
-  row[0] = pack(id.x, id.y);
-  row[1] = pack(__float_as_int(x), __float_as_int(y));
-  row[2] = pack(st, cd);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) row[3 + k] = (unsigned long long)__double_as_longlong(st == 2 ? X[k] : vo_state_dev::dnan());
+  vo_track::write_row(rec, F, i);
 }
 
 // vo_pipeline_update_landmarks_seq: feature i of the sequence takes X[3 k ..] when its id is ids[k] (the first such k) and its
@@ -597,7 +582,7 @@ static int check_track_ids(vo_pipeline* p, const char* who, int seq, bool idle_n
   return VO_OK;
 }
 
-size_t vo_pipeline_tracks_record_bytes(int cap) { return (size_t)16 + (size_t)48 * (size_t)(cap > 0 ? cap : 0); }
+size_t vo_pipeline_tracks_record_bytes(int cap) { return 8 * vo_track::record_words(cap); }
 
 int vo_pipeline_get_track_ids_seq(vo_pipeline* p, int seq, int32_t* ids, int32_t* born, int32_t* n_out, int32_t* next_id) {
   if (!p) return VO_EINVAL;

@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "state_device.h"
 #include "dlt_device.h"
+#include "pose_step_device.h"
 
 #pragma clang fp contract(off)
 
@@ -185,9 +186,6 @@ __device__ __forceinline__ double lane_value(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// position of (a, b), a <= b, in the row-major upper triangle s[0..20]
-__device__ __forceinline__ int tri_index(int a, int b) { return a * 6 - (a * (a - 1)) / 2 + (b - a); }
-
 // Solves the 6x6 normal equations held one total per lane (lane k of the wave: s[k]) by Gauss-Jordan
 // elimination, lane i < 6 working on row i (no pivoting: the matrix is positive definite or the solve
 // is refused, the same condition under which a Cholesky factorisation exists).  Returns d[i] in lane i.
@@ -222,27 +220,6 @@ __device__ __forceinline__ bool solve6_rows(double tot, int lane, double* d_out)
   for (int j = 1; j < 6; ++j) diag = i == j ? row[j] : diag;
   *d_out = row[6] / diag;
   return ok;
-}
-
-// Rodrigues coefficients sin(th)/th and (1 - cos th)/th^2: their Taylor series in th^2 for the small
-// rotations an update step makes (nine terms, below 1e-17 for th < 1/4), the library functions otherwise
-__device__ __forceinline__ void rodrigues_coefficients(double th2, double* a, double* b) {
-  if (th2 < 0.0625) {
-    double sa = 1.0, sb = 1.0;
-    const double ca[8] = {1.0 / 272, 1.0 / 210, 1.0 / 156, 1.0 / 110, 1.0 / 72, 1.0 / 42, 1.0 / 20, 1.0 / 6};
-    const double cb[8] = {1.0 / 306, 1.0 / 240, 1.0 / 182, 1.0 / 132, 1.0 / 90, 1.0 / 56, 1.0 / 30, 1.0 / 12};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      sa = 1.0 - th2 * ca[k] * sa;
-      sb = 1.0 - th2 * cb[k] * sb;
-    }
-    *a = sa;
-    *b = 0.5 * sb;
-  } else {
-    const double th = sqrt(th2);
-    *a = sin(th) / th;
-    *b = (1.0 - cos(th)) / th2;
-  }
 }
 
 // Gauss-Newton on the pose in s_pose (s_try = the trial pose, both 12 doubles of LDS, initialised by the caller,

@@ -7,7 +7,7 @@
 //   copy               the post's per-lane words (activity, feature count, records since the reset, refined pose) from a
 //                      pinned ring of four slots into HBM
 //   memset             the id table of the ring slot the record goes to
-//   sl_record_kernel   (cap / 256, S)  the record, byte for byte export_tracks_kernel's, into the lane's ring slot; the pose
+//   sl_record_kernel   (cap / 256, S)  the record, through export_tracks_kernel's writers, into the lane's ring slot; the pose
 //                      into the pose ring; every row's id into the slot's table
 //   sl_join_kernel     (S) x 1024      header check, poses in age order, then the join: the rows of the newest record probe
 //                      the W - 1 older tables, a workgroup scan gives every landmark its place, and the window is written
@@ -24,12 +24,8 @@
 // "none", which is what window_match_kernel's linear scan returns.  Which word an id ends up in depends on the order of
 // arrival; what a lookup returns does not.
 //
-// The scan.  Thread t of the join owns the rows t run .. t run + run - 1 of the newest record (run = ceil(n / 1024)), counts
-// its landmarks and their observations, and an exclusive scan over the 1024 threads (wave scan by shuffles, the sixteen wave
-// totals through LDS) gives (l, o): how many landmarks and observations lie before its run IN ROW ORDER.  A landmark is kept
-// iff l < L_cap and o + c <= M_cap, which is window_build_kernel's rule with the same l and o, so the same prefix is kept,
-// the same flag names what cut it, and observations are written in ascending slot.  The probes are made twice (count, then
-// write) instead of being kept in a per-thread array: no scratch.
+// The join is window_build_kernel's: both run vo_window_emit (window_join_device.h), this one with the tables as its finder,
+// so the same prefix is kept and the same flag names what cut it.
 //
 // Stream edges.  Everything above is enqueued on the main stream by one host thread, in this order, behind the main-stream
 // chain of the step in flight (k + 1) and in front of the chain of whatever is submitted next (k + 2): regroup(k + 2), the
@@ -46,12 +42,12 @@
 #include <algorithm>
 
 #include "pipeline.h"
+#include "window_join_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SL_WMAX = 16;
 constexpr int SL_T = 256;                  // threads per workgroup of the per-row kernels
 constexpr int SL_JOIN_T = 1024;            // threads of the join's one workgroup per lane
 constexpr int SL_PARAM_RING = 4;           // pinned slots of the per-post lane words
@@ -126,20 +122,12 @@ __device__ __forceinline__ int sl_lookup(const unsigned long long* tab, int logT
   for (unsigned k = 0; k <= mask; ++k, h = (h + 1u) & mask) {
     const unsigned long long cur = tab[h];
     if (cur == SL_EMPTY) return -1;
-    if ((unsigned)(cur >> 32) == (unsigned)id) return (int)(unsigned)(cur & 0xffffffffull);
+    if ((unsigned)(cur >> 32) == (unsigned)id) return (int)(unsigned)cur;
   }
   return -1;
 }
 
-__device__ __forceinline__ unsigned long long sl_pack(int lo, int hi) {
-  return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32);
-}
-
-__device__ __forceinline__ int sl_rows(const unsigned long long* rec, int cap) {
-  return max(0, min((int)(unsigned)(rec[0] & 0xffffffffull), cap));
-}
-
-// The observation record of the step collected last (pipeline_state.hip, export_tracks_kernel: the same words) into ring slot
+// The observation record of the step collected last (track_record_device.h: export_tracks_kernel's writers) into ring slot
 // a.ring of lane blockIdx.y, its pose into the pose ring, its ids into the slot's table.  F: the features that step left;
 // par: where its regroup left next_id / the step counter.
 __global__ __launch_bounds__(SL_T) void sl_record_kernel(sl_args a, vo_feat Fall, int par) {
@@ -150,33 +138,19 @@ __global__ __launch_bounds__(SL_T) void sl_record_kernel(sl_args a, vo_feat Fall
   const vo_seq_ctl* ctl = a.ctl + q;
   unsigned long long* rec = sl_rec(a, q, a.ring);
   const int i = blockIdx.x * SL_T + threadIdx.x;
-  if (i == 0) {
-    rec[0] = sl_pack(n, ctl->id_step[par]);
-    rec[1] = sl_pack(ctl->next_id[par], (int)q);
-  }
+  if (i == 0) vo_track::write_header(rec, n, ctl->id_step[par], ctl->next_id[par], (int)q);
   if (blockIdx.x == 0 && threadIdx.x < 12) a.pose_ring[(q * (size_t)a.W + (size_t)a.ring) * 12 + threadIdx.x] = a.lane[q].pose[threadIdx.x];
   if (i >= min(n, a.cap)) return;
-  const int2 id = F.ids[i];
-  const float x = F.kp[2 * i], y = F.kp[2 * i + 1];
-  const int st = F.state[i], cd = F.cand[i];
-  double X[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) X[k] = F.land[3 * i + k];
-  unsigned long long* row = rec + 2 + (size_t)6 * i;
-  row[0] = sl_pack(id.x, id.y);
-  row[1] = sl_pack(__float_as_int(x), __float_as_int(y));
-  row[2] = sl_pack(st, cd);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) row[3 + k] = (unsigned long long)__double_as_longlong(st == 2 ? X[k] : vo_state_dev::dnan());
-  sl_insert(sl_tab(a, q, a.ring), a.logT, id.x, i);
+  const int id = vo_track::write_row(rec, F, i);
+  sl_insert(sl_tab(a, q, a.ring), a.logT, id, i);
 }
 
-// One workgroup per lane: the header check, the window's poses and intrinsics, and the join.
+// One workgroup per lane: the header check, the window's poses and intrinsics, and the join (window_join_device.h) with the
+// older records' id tables as its finder.
 __global__ __launch_bounds__(SL_JOIN_T) void sl_join_kernel(sl_args a) {
   __shared__ int s_full, s_step;
-  __shared__ int s_wl[SL_JOIN_T / 64], s_wo[SL_JOIN_T / 64];
-  __shared__ int s_tot[3];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ vo_window_lds<SL_JOIN_T> s_win;
+  const int tid = threadIdx.x;
   const size_t q = blockIdx.x;
   const sl_lane ln = a.lane[q];
   const int W = a.W;
@@ -187,12 +161,12 @@ __global__ __launch_bounds__(SL_JOIN_T) void sl_join_kernel(sl_args a) {
     // (vo/landmarks/window_ba.py, _headers): the host counts, the headers are read here
     int full = ln.active && ln.count >= W;
     int step = -1;
-    if (ln.active) step = (int)(unsigned)(sl_rec(a, q, a.ring)[0] >> 32);
+    if (ln.active) step = vo_track::step(sl_rec(a, q, a.ring));
     if (full) {
       int ps = 0, pn = 0;
       for (int s = 0; s < W; ++s) {
         const unsigned long long* r = sl_rec(a, q, (a.ring + 1 + s) % W);
-        const int st = (int)(unsigned)(r[0] >> 32), nx = (int)(unsigned)(r[1] & 0xffffffffull);
+        const int st = vo_track::step(r), nx = vo_track::next_id(r);
         if (s > 0 && (st != ps + 1 || nx < pn)) full = 0;
         ps = st;
         pn = nx;
@@ -200,7 +174,6 @@ __global__ __launch_bounds__(SL_JOIN_T) void sl_join_kernel(sl_args a) {
     }
     s_full = full;
     s_step = step;
-    s_tot[0] = s_tot[1] = s_tot[2] = 0;
   }
   if (tid < 12 * W) {
     const int s = tid / 12, k = tid - 12 * s;
@@ -210,124 +183,25 @@ __global__ __launch_bounds__(SL_JOIN_T) void sl_join_kernel(sl_args a) {
   }
   __syncthreads();
   const int full = s_full;
-  if (!full) {
-    if (tid == 0) {
-      head[0] = head[1] = head[2] = head[3] = 0;
-      lm_start[0] = 0;
-      vo_structure_loop_entry e;
-      e.step = s_step;
-      e.full = e.L = e.M = e.flags = e.n_written = 0;
-      e.summary.L = e.summary.n_refused = e.summary.n_kept = e.summary.max_iterations = 0;
-      e.summary.cost0 = e.summary.cost = 0.0;
-      a.entry[q] = e;
-    }
-    return;
-  }
-  const unsigned long long* newest = sl_rec(a, q, a.ring) + 2;
-  const int n_new = sl_rows(sl_rec(a, q, a.ring), a.cap);
-  const int run = (n_new + SL_JOIN_T - 1) / SL_JOIN_T;
-  const int r0 = min(tid * run, n_new), r1 = min(r0 + run, n_new);
-  int32_t* const lm_of_row = a.lm_of_row + q * (size_t)a.cap;
-  // observations of row r as a landmark, 0 when it is none (the newest record's own row counts as one)
-  auto n_obs = [&](int r) {
-    const unsigned long long* row = newest + (size_t)6 * r;
-    if ((int)(unsigned)(row[2] & 0xffffffffull) != 2) return 0;
-    const double X0 = __longlong_as_double((long long)row[3]), X1 = __longlong_as_double((long long)row[4]),
-                 X2 = __longlong_as_double((long long)row[5]);
-    if (!(isfinite(X0) && isfinite(X1) && isfinite(X2))) return 0;
-    const int id = (int)(unsigned)(row[0] & 0xffffffffull);
-    int c = 1;
-    for (int s = 0; s < W - 1; ++s) c += sl_lookup(sl_tab(a, q, (a.ring + 1 + s) % W), a.logT, id) >= 0 ? 1 : 0;
-    return c >= 2 ? c : 0;
-  };
-  int nl = 0, no = 0;
-  for (int r = r0; r < r1; ++r) {
-    const int c = n_obs(r);
-    nl += c > 0 ? 1 : 0;
-    no += c;
-  }
-  // exclusive scan of (nl, no) in thread order
-  int il = nl, io = no;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int tl = __shfl_up(il, off), to = __shfl_up(io, off);
-    if (lane >= off) {
-      il += tl;
-      io += to;
-    }
-  }
-  if (lane == 63) {
-    s_wl[wv] = il;
-    s_wo[wv] = io;
-  }
-  __syncthreads();
-  int l = il - nl, o = io - no;
-  for (int w = 0; w < wv; ++w) {
-    l += s_wl[w];
-    o += s_wo[w];
-  }
-  int32_t* const obs_slot = a.obs_slot + q * (size_t)a.M_cap;
-  double* const obs_xy = a.obs_xy + q * (size_t)a.M_cap * 2;
-  double* const X = a.X + q * (size_t)a.L_cap * 3;
-  double* const Xin = a.X0 + q * (size_t)a.L_cap * 3;
-  int32_t* const lm_id = a.lm_id + q * (size_t)a.L_cap;
-  int kept_l = 0, kept_o = 0, cut = 0;
-  for (int r = r0; r < r1; ++r) {
-    const int c = n_obs(r);
-    int mine = -1;
-    if (c > 0) {
-      if (l >= a.L_cap || o + c > a.M_cap) {
-        // the flag names what ended the list: only the first landmark left out sets it (the one before it was kept)
-        if (l == 0 || (l - 1 < a.L_cap && o <= a.M_cap)) cut |= l >= a.L_cap ? 1 : 2;
-      } else {
-        const unsigned long long* row = newest + (size_t)6 * r;
-        const int id = (int)(unsigned)(row[0] & 0xffffffffull);
-        lm_id[l] = id;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const double v = __longlong_as_double((long long)row[3 + k]);
-          X[3 * (size_t)l + k] = v;
-          Xin[3 * (size_t)l + k] = v;
-        }
-        lm_start[l] = o;
-        lm_start[l + 1] = o + c;                 // (the next landmark writes the same value)
-        int k = o;
-        for (int s = 0; s < W; ++s) {
-          const int m = s == W - 1 ? r : sl_lookup(sl_tab(a, q, (a.ring + 1 + s) % W), a.logT, id);
-          if (m < 0) continue;
-          const unsigned long long xy = sl_rec(a, q, (a.ring + 1 + s) % W)[2 + (size_t)6 * m + 1];
-          obs_slot[k] = s;
-          obs_xy[2 * (size_t)k] = (double)__int_as_float((int)(unsigned)(xy & 0xffffffffull));
-          obs_xy[2 * (size_t)k + 1] = (double)__int_as_float((int)(unsigned)(xy >> 32));
-          ++k;
-        }
-        mine = l;
-        ++kept_l;
-        kept_o += c;
-      }
-      ++l;
-      o += c;
-    }
-    lm_of_row[r] = mine;
-  }
-  if (kept_l) {
-    atomicAdd(&s_tot[0], kept_l);
-    atomicAdd(&s_tot[1], kept_o);
-  }
-  if (cut) atomicOr(&s_tot[2], cut);
-  __syncthreads();
+  if (full)
+    vo_window_emit<SL_JOIN_T>(
+        s_win, W, a.cap, a.L_cap, a.M_cap, [&](int s) { return sl_rec(a, q, (a.ring + 1 + s) % W); },
+        [&](int s, int id, int) { return sl_lookup(sl_tab(a, q, (a.ring + 1 + s) % W), a.logT, id); }, a.lm_id + q * (size_t)a.L_cap,
+        a.X + q * (size_t)a.L_cap * 3, a.X0 + q * (size_t)a.L_cap * 3, lm_start, a.obs_slot + q * (size_t)a.M_cap,
+        a.obs_xy + q * (size_t)a.M_cap * 2, a.lm_of_row + q * (size_t)a.cap);
   if (tid == 0) {
-    head[0] = s_tot[0];
-    head[1] = s_tot[1];
-    head[2] = s_tot[2];
+    const int L = full ? s_win.tot[0] : 0, M = full ? s_win.tot[1] : 0, flags = full ? s_win.tot[2] : 0;
+    head[0] = L;
+    head[1] = M;
+    head[2] = flags;
     head[3] = 0;
-    if (s_tot[0] == 0) lm_start[0] = 0;
+    if (!full) lm_start[0] = 0;
     vo_structure_loop_entry e;
     e.step = s_step;
-    e.full = 1;
-    e.L = s_tot[0];
-    e.M = s_tot[1];
-    e.flags = s_tot[2];
+    e.full = full;
+    e.L = L;
+    e.M = M;
+    e.flags = flags;
     e.n_written = 0;
     e.summary.L = e.summary.n_refused = e.summary.n_kept = e.summary.max_iterations = 0;
     e.summary.cost0 = e.summary.cost = 0.0;
@@ -452,7 +326,7 @@ int vo_structure_loop_create(vo_pipeline* p, const vo_structure_loop_config* cfg
   *out = nullptr;
   VO_REQUIRE(ctx, p->cfg.track_ids != 0, "structure_loop: the pipeline was created without track_ids");
   VO_REQUIRE(ctx, p->cfg.tracker_mode == 0, "structure_loop: tracker_mode must be 0 (klt), the pipeline runs mode %d", p->cfg.tracker_mode);
-  VO_REQUIRE(ctx, cfg->window >= 2 && cfg->window <= SL_WMAX, "structure_loop: window must be 2 .. %d records, got %d", SL_WMAX, cfg->window);
+  VO_REQUIRE(ctx, cfg->window >= 2 && cfg->window <= VO_WINDOW_WMAX, "structure_loop: window must be 2 .. %d records, got %d", VO_WINDOW_WMAX, cfg->window);
   VO_REQUIRE(ctx, !p->sloop, "structure_loop: the pipeline has a structure loop already");
   const int W = cfg->window, S = p->S, cap = p->cap;
   const int L_cap = cfg->L_cap ? cfg->L_cap : cap;
@@ -462,6 +336,9 @@ int vo_structure_loop_create(vo_pipeline* p, const vo_structure_loop_config* cfg
   VO_REQUIRE(ctx, M_cap >= 1 && (long long)M_cap <= M_max, "structure_loop: M_cap must be 0 (L_cap * window) or 1 .. L_cap * window observations, got %d",
              cfg->M_cap);
   VO_REQUIRE(ctx, cap >= 1 && cap <= (1 << 20), "structure_loop: the pipeline's feature capacity %d is beyond 1048576 rows", cap);
+  vo_lm_params lm;      // (the parameters both solvers share are refused here; the rest by the first post's vo_window_structure_dev)
+  VO_TRY(vo_resolve_lm_params(ctx, "window_structure", cfg->params.max_iter, cfg->params.max_trials, cfg->params.huber_px, cfg->params.lambda0,
+                              cfg->params.step_tol, &lm));
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   vo_structure_loop* lp = new vo_structure_loop();
   lp->p = p;
@@ -480,7 +357,7 @@ int vo_structure_loop_create(vo_pipeline* p, const vo_structure_loop_config* cfg
   a.M_cap = M_cap;
   a.logT = 4;
   while ((1 << a.logT) < 2 * cap) ++a.logT;
-  a.rec_words = vo_pipeline_tracks_record_bytes(cap) / 8;
+  a.rec_words = vo_track::record_words(cap);
   a.cams = p->d_cams;
   a.ctl = p->d_ctl;
   const size_t s = (size_t)S;

@@ -1,4 +1,6 @@
-// Context, error reporting, device-memory helpers and per-kernel event timing.
+// Context, error reporting, the window arena's argument checks, device-memory helpers and per-kernel event timing.
+#include <cmath>
+
 #include "vo_internal.h"
 
 int vo_set_error(vo_ctx* ctx, int code, const char* fmt, ...) {
@@ -9,6 +11,31 @@ int vo_set_error(vo_ctx* ctx, int code, const char* fmt, ...) {
     va_end(ap);
   }
   return code;
+}
+
+int vo_check_window_shape(vo_ctx* ctx, const char* who, int S, int W, int L_cap, int M_cap) {
+  VO_REQUIRE(ctx, S >= 1 && S <= 4096, "%s: S must be 1 .. 4096 windows, got %d", who, S);
+  VO_REQUIRE(ctx, W >= 2 && W <= VO_WINDOW_WMAX, "%s: W must be 2 .. %d slots, got %d", who, VO_WINDOW_WMAX, W);
+  VO_REQUIRE(ctx, L_cap >= 1 && L_cap <= (1 << 20), "%s: L_cap must be 1 .. 1048576 landmarks, got %d", who, L_cap);
+  VO_REQUIRE(ctx, M_cap >= 1 && (long long)M_cap <= (long long)L_cap * W, "%s: M_cap must be 1 .. L_cap * W observations, got %d",
+             who, M_cap);
+  return VO_OK;
+}
+
+int vo_resolve_lm_params(vo_ctx* ctx, const char* who, int max_iter, int max_trials, double huber_px, double lambda0,
+                         double step_tol, vo_lm_params* out) {
+  VO_REQUIRE(ctx, max_iter >= 0 && max_iter <= 50, "%s: max_iter must be 0 (default 10) .. 50, got %d", who, max_iter);
+  out->max_iter = max_iter ? max_iter : 10;
+  VO_REQUIRE(ctx, max_trials >= 0 && max_trials <= 1000, "%s: max_trials must be 0 (default 2 * max_iter) .. 1000, got %d", who,
+             max_trials);
+  out->max_trials = max_trials ? max_trials : 2 * out->max_iter;
+  VO_REQUIRE(ctx, huber_px >= 0.0 && std::isfinite(huber_px), "%s: huber_px must be 0 (squared loss) or a positive number of pixels", who);
+  out->huber = huber_px;
+  VO_REQUIRE(ctx, lambda0 >= 0.0 && std::isfinite(lambda0), "%s: lambda0 must be 0 (default 1e-3) or positive", who);
+  out->lambda0 = lambda0 > 0.0 ? lambda0 : 1e-3;
+  VO_REQUIRE(ctx, step_tol >= 0.0 && std::isfinite(step_tol), "%s: step_tol must be 0 (default 1e-10) or positive", who);
+  out->step_tol = step_tol > 0.0 ? step_tol : 1e-10;
+  return VO_OK;
 }
 
 int vo_ensure(vo_ctx* ctx, vo_buf& b, size_t bytes) {

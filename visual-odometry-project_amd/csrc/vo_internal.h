@@ -132,6 +132,18 @@ static inline int vo_check_launch(vo_ctx* ctx, const char* what) {
 
 static inline int vo_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// ---- the window arena (window_ba.hip, window_structure.hip, structure_loop.hip; defined in vo_ctx.hip) ----
+constexpr int VO_WINDOW_WMAX = 16;      // slots per window
+// S windows of W slots, at most L_cap landmarks and M_cap observations each; `who` heads the message
+int vo_check_window_shape(vo_ctx* ctx, const char* who, int S, int W, int L_cap, int M_cap);
+// The Levenberg-Marquardt parameters vo_ba_params and vo_structure_params share, checked, 0 replaced by its default.
+struct vo_lm_params {
+  int max_iter, max_trials;
+  double huber, lambda0, step_tol;
+};
+int vo_resolve_lm_params(vo_ctx* ctx, const char* who, int max_iter, int max_trials, double huber_px, double lambda0,
+                         double step_tol, vo_lm_params* out);
+
 // Tile order of the image kernels.  Workgroups are dealt to the eight XCDs round-robin by their linear id (ids equal
 // mod 8 share an L2 -- observed, not promised: speed only), so with tile = id neighbouring tiles never share an L2
 // and every halo byte is fetched once per tile that needs it.  This map gives the workgroups of one XCD a contiguous

@@ -26,15 +26,15 @@
 // join compares ids only and copies the rest.
 #include <cmath>
 
-#include "vo_internal.h"
+#include "pose_step_device.h"
+#include "window_join_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int BA_T = 512;
-constexpr int BA_WMAX = 16;                       // slots per window
-constexpr int BA_NMAX = 6 * (BA_WMAX - 1);        // unknowns of the reduced system
+constexpr int BA_NMAX = 6 * (VO_WINDOW_WMAX - 1);        // unknowns of the reduced system
 constexpr int BA_OBS_D = 57;                      // doubles of workspace per observation: Jp 12, Jl 6, w, e 2, W 18, Y 18
 constexpr int BA_LM_D = 18;                       // per landmark: V 6, g 3, V*^-1 6, trial X 3
 constexpr double BA_LAMBDA_MAX = 1e12, BA_LAMBDA_MIN = 1e-12;
@@ -55,10 +55,9 @@ struct ba_args {
 };
 
 __host__ __device__ inline size_t window_doubles(int L_cap, int M_cap) {
-  return (size_t)BA_OBS_D * (size_t)M_cap + (size_t)(BA_LM_D + BA_WMAX / 2) * (size_t)L_cap;
+  return (size_t)BA_OBS_D * (size_t)M_cap + (size_t)(BA_LM_D + VO_WINDOW_WMAX / 2) * (size_t)L_cap;
 }
 
-__device__ __forceinline__ int tri6(int a, int b) { return a * 6 - (a * (a - 1)) / 2 + (b - a); }     // a <= b
 __device__ __forceinline__ int low(int r, int c) { return (r * (r + 1)) / 2 + c; }                    // c <= r
 
 // sums of v[0 .. NV-1] over the workgroup, in every thread (see the head of the file for the order)
@@ -83,26 +82,6 @@ __device__ __forceinline__ void block_sums(double* v, double (*s_red)[4]) {
     v[k] = t;
   }
   __syncthreads();
-}
-
-// sin(th)/th and (1 - cos th)/th^2 exactly as refine.hip's rodrigues_coefficients forms them
-__device__ __forceinline__ void ba_rodrigues(double th2, double* a, double* b) {
-  if (th2 < 0.0625) {
-    double sa = 1.0, sb = 1.0;
-    const double ca[8] = {1.0 / 272, 1.0 / 210, 1.0 / 156, 1.0 / 110, 1.0 / 72, 1.0 / 42, 1.0 / 20, 1.0 / 6};
-    const double cb[8] = {1.0 / 306, 1.0 / 240, 1.0 / 182, 1.0 / 132, 1.0 / 90, 1.0 / 56, 1.0 / 30, 1.0 / 12};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      sa = 1.0 - th2 * ca[k] * sa;
-      sb = 1.0 - th2 * cb[k] * sb;
-    }
-    *a = sa;
-    *b = 0.5 * sb;
-  } else {
-    const double th = sqrt(th2);
-    *a = sin(th) / th;
-    *b = (1.0 - cos(th)) / th2;
-  }
 }
 
 struct ba_cam {
@@ -142,8 +121,8 @@ __device__ __forceinline__ void eval_partial(const double* pose, const double* _
 __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
   __shared__ double s_S[(BA_NMAX * (BA_NMAX + 1)) / 2];
   __shared__ double s_diag[BA_NMAX], s_b[BA_NMAX], s_y[BA_NMAX];
-  __shared__ double s_U[(BA_WMAX - 1) * 27];
-  __shared__ double s_pose[BA_WMAX * 12], s_try[BA_WMAX * 12];
+  __shared__ double s_U[(VO_WINDOW_WMAX - 1) * 27];
+  __shared__ double s_pose[VO_WINDOW_WMAX * 12], s_try[VO_WINDOW_WMAX * 12];
   __shared__ double s_red[BA_T / 64][4];
   __shared__ int s_flag;
   const int tid = threadIdx.x;
@@ -158,7 +137,7 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
   double* const work = a.work + q * window_doubles(a.L_cap, a.M_cap);
   double* const wobs = work;                                              // M_cap x BA_OBS_D
   double* const wlm = work + (size_t)BA_OBS_D * a.M_cap;                  // L_cap x BA_LM_D
-  int* const tab = (int*)(wlm + (size_t)BA_LM_D * a.L_cap);               // L_cap x BA_WMAX: landmark, slot -> observation
+  int* const tab = (int*)(wlm + (size_t)BA_LM_D * a.L_cap);               // L_cap x VO_WINDOW_WMAX: landmark, slot -> observation
   vo_ba_result* const res = a.res + q;
   const int nfix = a.n_fixed, nf = W - nfix, n = 6 * nf;
   const double huber = a.huber;
@@ -216,9 +195,9 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
     // the table landmark x slot -> observation (the CSR is sound here: every range lies in 0 .. M); slots ascend strictly
     bool bad = false;
     for (int i = tid; i < L; i += BA_T) {
-      int* row = tab + (size_t)BA_WMAX * i;
+      int* row = tab + (size_t)VO_WINDOW_WMAX * i;
 #pragma unroll
-      for (int s = 0; s < BA_WMAX; ++s) row[s] = -1;
+      for (int s = 0; s < VO_WINDOW_WMAX; ++s) row[s] = -1;
       int prev = -1;
       const int e = lm_start[i + 1];
       for (int o = lm_start[i]; o < e; ++o) {
@@ -346,7 +325,7 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
           double term[4];
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
-            const int o = tab[(size_t)BA_WMAX * min(i0 + v, L - 1) + nfix + j];
+            const int o = tab[(size_t)VO_WINDOW_WMAX * min(i0 + v, L - 1) + nfix + j];
             on[v] = i0 + v < L && o >= 0;
             const double* d = wobs + (size_t)BA_OBS_D * (on[v] ? o : 0);
             const double w = d[18];
@@ -426,7 +405,7 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
           double t[4];
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
-            const int* tr = tab + (size_t)BA_WMAX * min(i0 + v, L - 1) + nfix;
+            const int* tr = tab + (size_t)VO_WINDOW_WMAX * min(i0 + v, L - 1) + nfix;
             const int oj = tr[j], ok = tr[k];
             both[v] = i0 + v < L && oj >= 0 && ok >= 0;
             const double* y = wobs + (size_t)BA_OBS_D * (both[v] ? oj : 0) + 39 + 3 * r;
@@ -439,7 +418,7 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
         }
         double base = 0.0;
         if (j == k) {
-          base = s_U[27 * j + tri6(c, r)];
+          base = s_U[27 * j + tri_index(c, r)];
           if (r == c) base *= damp;
         }
         s_S[u] = base - acc;
@@ -448,7 +427,7 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
         const int j = tid / 6, r = tid - 6 * j;
         double acc = 0.0;
         for (int i = 0; i < L; ++i) {
-          const int o = tab[(size_t)BA_WMAX * i + nfix + j];
+          const int o = tab[(size_t)VO_WINDOW_WMAX * i + nfix + j];
           if (o < 0) continue;
           const double* y = wobs + (size_t)BA_OBS_D * o + 39 + 3 * r;
           const double* g = wlm + (size_t)BA_LM_D * i + 6;
@@ -507,7 +486,7 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
       const double* d = s_b + 6 * tid;
       nrm[1] += P[9] * P[9] + P[10] * P[10] + P[11] * P[11];
       double ca, cb;
-      ba_rodrigues(d[3] * d[3] + d[4] * d[4] + d[5] * d[5], &ca, &cb);
+      rodrigues_coefficients(d[3] * d[3] + d[4] * d[4] + d[5] * d[5], &ca, &cb);
       const double Wx[9] = {0.0, -d[5], d[4], d[5], 0.0, -d[3], -d[4], d[3], 0.0};
       double E[9];
 #pragma unroll
@@ -625,29 +604,23 @@ __global__ __launch_bounds__(BA_T) void window_ba_kernel(ba_args a) {
 
 constexpr int WB_T = 256;
 struct wb_records {
-  const unsigned long long* rec[BA_WMAX];     // oldest first; a record: 2 header words, then rows of 6 words
+  const vo_track::word* rec[VO_WINDOW_WMAX];     // oldest first
 };
-
-__device__ __forceinline__ int rec_rows(const unsigned long long* rec, int cap) {
-  const int n = (int)(unsigned)(rec[0] & 0xffffffffull);
-  return max(0, min(n, cap));
-}
 
 // match[r * W + s] = the first row of record s that carries the id of row r of the newest record, -1 when none
 __global__ __launch_bounds__(WB_T) void window_match_kernel(wb_records R, int W, int cap, int* __restrict__ match) {
   const int r = blockIdx.x * WB_T + threadIdx.x, s = blockIdx.y;
-  const int n_new = rec_rows(R.rec[W - 1], cap);
+  const int n_new = vo_track::rows(R.rec[W - 1], cap);
   if (r >= n_new) return;
   if (s == W - 1) {
     match[(size_t)r * W + s] = r;
     return;
   }
-  const int id = (int)(unsigned)(R.rec[W - 1][2 + (size_t)6 * r] & 0xffffffffull);
-  const unsigned long long* rows = R.rec[s] + 2;
-  const int n = rec_rows(R.rec[s], cap);
+  const int id = vo_track::row_id(vo_track::row(R.rec[W - 1], r));
+  const int n = vo_track::rows(R.rec[s], cap);
   int found = -1;
   for (int k = 0; k < n; ++k) {
-    if ((int)(unsigned)(rows[(size_t)6 * k] & 0xffffffffull) == id) {
+    if (vo_track::row_id(vo_track::row(R.rec[s], k)) == id) {
       found = k;
       break;
     }
@@ -655,89 +628,21 @@ __global__ __launch_bounds__(WB_T) void window_match_kernel(wb_records R, int W,
   match[(size_t)r * W + s] = found;
 }
 
-// One workgroup: thread t owns a run of consecutive rows of the newest record; the runs' landmark and observation counts
-// are scanned in thread order, so landmarks come out in row order.
+// One workgroup: the join (window_join_device.h) over the match table, and the window's head {L, M, flags, 0}.
 __global__ __launch_bounds__(BA_T) void window_build_kernel(wb_records R, int W, int cap, int L_cap, int M_cap,
                                                             const int* __restrict__ match, int32_t* __restrict__ head,
                                                             int32_t* __restrict__ lm_start, int32_t* __restrict__ obs_slot,
                                                             double* __restrict__ obs_xy, double* __restrict__ X,
                                                             int32_t* __restrict__ lm_id) {
-  __shared__ int s_nl[BA_T], s_no[BA_T];
-  __shared__ int s_tot[2];
-  const int tid = threadIdx.x;
-  const unsigned long long* newest = R.rec[W - 1] + 2;
-  const int n_new = rec_rows(R.rec[W - 1], cap);
-  const int run = (n_new + BA_T - 1) / BA_T;
-  const int r0 = min(tid * run, n_new), r1 = min(r0 + run, n_new);
-  // observations of row r as a landmark, 0 when it is none
-  auto n_obs = [&](int r) {
-    const unsigned long long* row = newest + (size_t)6 * r;
-    if ((int)(unsigned)(row[2] & 0xffffffffull) != 2) return 0;
-    const double X0 = __longlong_as_double((long long)row[3]), X1 = __longlong_as_double((long long)row[4]),
-                 X2 = __longlong_as_double((long long)row[5]);
-    if (!(isfinite(X0) && isfinite(X1) && isfinite(X2))) return 0;
-    int c = 0;
-    for (int s = 0; s < W; ++s) c += match[(size_t)r * W + s] >= 0 ? 1 : 0;
-    return c >= 2 ? c : 0;
-  };
-  int nl = 0, no = 0;
-  for (int r = r0; r < r1; ++r) {
-    const int c = n_obs(r);
-    nl += c > 0 ? 1 : 0;
-    no += c;
-  }
-  s_nl[tid] = nl;
-  s_no[tid] = no;
-  if (tid == 0) s_tot[0] = s_tot[1] = 0;
-  __syncthreads();
-  int l = 0, o = 0;
-  for (int t = 0; t < tid; ++t) {
-    l += s_nl[t];
-    o += s_no[t];
-  }
-  int kept_l = 0, kept_o = 0, cut = 0;
-  for (int r = r0; r < r1; ++r) {
-    const int c = n_obs(r);
-    if (c == 0) continue;
-    if (l >= L_cap || o + c > M_cap) {
-      // the flag names what ended the list: only the first landmark left out sets it (the one before it was kept)
-      if (l == 0 || (l - 1 < L_cap && o <= M_cap)) cut |= l >= L_cap ? 1 : 2;
-    } else {
-      const unsigned long long* row = newest + (size_t)6 * r;
-      lm_id[l] = (int)(unsigned)(row[0] & 0xffffffffull);
-      X[3 * l] = __longlong_as_double((long long)row[3]);
-      X[3 * l + 1] = __longlong_as_double((long long)row[4]);
-      X[3 * l + 2] = __longlong_as_double((long long)row[5]);
-      lm_start[l] = o;
-      lm_start[l + 1] = o + c;                 // (the next landmark writes the same value)
-      int k = o;
-      for (int s = 0; s < W; ++s) {
-        const int m = match[(size_t)r * W + s];
-        if (m < 0) continue;
-        const unsigned long long xy = R.rec[s][2 + (size_t)6 * m + 1];
-        obs_slot[k] = s;
-        obs_xy[2 * k] = (double)__int_as_float((int)(unsigned)(xy & 0xffffffffull));
-        obs_xy[2 * k + 1] = (double)__int_as_float((int)(unsigned)(xy >> 32));
-        ++k;
-      }
-      ++kept_l;
-      kept_o += c;
-    }
-    ++l;
-    o += c;
-  }
-  // (a landmark is kept iff l < L_cap and o + c <= M_cap; both grow along the rows, so what is kept is a prefix)
-  if (kept_l) {
-    atomicAdd(&s_tot[0], kept_l);
-    atomicAdd(&s_tot[1], kept_o);
-  }
-  if (cut) atomicOr(&head[2], cut);
-  __syncthreads();
-  if (tid == 0) {
-    head[0] = s_tot[0];
-    head[1] = s_tot[1];
+  __shared__ vo_window_lds<BA_T> s_win;
+  vo_window_emit<BA_T>(
+      s_win, W, cap, L_cap, M_cap, [&](int s) { return R.rec[s]; }, [&](int s, int, int r) { return match[(size_t)r * W + s]; },
+      lm_id, X, nullptr, lm_start, obs_slot, obs_xy, nullptr);
+  if (threadIdx.x == 0) {
+    head[0] = s_win.tot[0];
+    head[1] = s_win.tot[1];
+    head[2] = s_win.tot[2];
     head[3] = 0;
-    if (s_tot[0] == 0) lm_start[0] = 0;
   }
 }
 
@@ -745,27 +650,15 @@ int resolve_params(vo_ctx* ctx, const vo_ba_params* prm, ba_args* a) {
   vo_ba_params p;
   memset(&p, 0, sizeof(p));
   if (prm) p = *prm;
-  VO_REQUIRE(ctx, p.max_iter >= 0 && p.max_iter <= 50, "window_ba: max_iter must be 0 (default 10) .. 50, got %d", p.max_iter);
-  a->max_iter = p.max_iter ? p.max_iter : 10;
-  VO_REQUIRE(ctx, p.max_trials >= 0 && p.max_trials <= 1000, "window_ba: max_trials must be 0 (default 2 * max_iter) .. 1000, got %d",
-             p.max_trials);
-  a->max_trials = p.max_trials ? p.max_trials : 2 * a->max_iter;
+  vo_lm_params lm;
+  VO_TRY(vo_resolve_lm_params(ctx, "window_ba", p.max_iter, p.max_trials, p.huber_px, p.lambda0, p.step_tol, &lm));
+  a->max_iter = lm.max_iter;
+  a->max_trials = lm.max_trials;
+  a->huber = lm.huber;
+  a->lambda0 = lm.lambda0;
+  a->step_tol = lm.step_tol;
   VO_REQUIRE(ctx, p.n_fixed >= 0, "window_ba: n_fixed must be 0 (default 2) or the number of held slots, got %d", p.n_fixed);
   a->n_fixed = p.n_fixed ? p.n_fixed : 2;
-  VO_REQUIRE(ctx, p.huber_px >= 0.0 && std::isfinite(p.huber_px), "window_ba: huber_px must be 0 (squared loss) or a positive number of pixels");
-  a->huber = p.huber_px;
-  VO_REQUIRE(ctx, p.lambda0 >= 0.0 && std::isfinite(p.lambda0), "window_ba: lambda0 must be 0 (default 1e-3) or positive");
-  a->lambda0 = p.lambda0 > 0.0 ? p.lambda0 : 1e-3;
-  VO_REQUIRE(ctx, p.step_tol >= 0.0 && std::isfinite(p.step_tol), "window_ba: step_tol must be 0 (default 1e-10) or positive");
-  a->step_tol = p.step_tol > 0.0 ? p.step_tol : 1e-10;
-  return VO_OK;
-}
-
-int check_shape(vo_ctx* ctx, const char* who, int W, int L_cap, int M_cap) {
-  VO_REQUIRE(ctx, W >= 2 && W <= BA_WMAX, "%s: W must be 2 .. %d slots, got %d", who, BA_WMAX, W);
-  VO_REQUIRE(ctx, L_cap >= 1 && L_cap <= (1 << 20), "%s: L_cap must be 1 .. 1048576 landmarks, got %d", who, L_cap);
-  VO_REQUIRE(ctx, M_cap >= 1 && (long long)M_cap <= (long long)L_cap * W, "%s: M_cap must be 1 .. L_cap * W observations, got %d",
-             who, M_cap);
   return VO_OK;
 }
 
@@ -774,7 +667,7 @@ int check_shape(vo_ctx* ctx, const char* who, int W, int L_cap, int M_cap) {
 extern "C" {
 
 size_t vo_window_ba_workspace_bytes(int S, int W, int L_cap, int M_cap) {
-  if (S < 1 || W < 2 || W > BA_WMAX || L_cap < 1 || M_cap < 1) return 0;
+  if (S < 1 || W < 2 || W > VO_WINDOW_WMAX || L_cap < 1 || M_cap < 1) return 0;
   return (size_t)S * window_doubles(L_cap, M_cap) * sizeof(double);
 }
 
@@ -783,8 +676,7 @@ int vo_window_ba_dev(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const int3
                      const vo_ba_params* prm, vo_ba_result* d_results) {
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, d_counts && d_K && d_poses && d_X && d_lm_start && d_obs_slot && d_obs_xy && d_results, "window_ba: null pointer");
-  VO_REQUIRE(ctx, S >= 1 && S <= 4096, "window_ba: S must be 1 .. 4096 windows, got %d", S);
-  VO_TRY(check_shape(ctx, "window_ba", W, L_cap, M_cap));
+  VO_TRY(vo_check_window_shape(ctx, "window_ba", S, W, L_cap, M_cap));
   ba_args a;
   VO_TRY(resolve_params(ctx, prm, &a));
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -813,8 +705,7 @@ int vo_window_ba(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const int32_t*
                  vo_ba_result* results) {
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, counts && K && poses && X && lm_start && obs_slot && obs_xy && results, "window_ba: null pointer");
-  VO_REQUIRE(ctx, S >= 1 && S <= 4096, "window_ba: S must be 1 .. 4096 windows, got %d", S);
-  VO_TRY(check_shape(ctx, "window_ba", W, L_cap, M_cap));
+  VO_TRY(vo_check_window_shape(ctx, "window_ba", S, W, L_cap, M_cap));
   const size_t s = (size_t)S;
   const size_t bytes[8] = {s * 16,           s * 72,        s * W * 96,        s * L_cap * 24, s * ((size_t)L_cap + 1) * 4,
                            s * M_cap * 4,    s * M_cap * 16, s * sizeof(vo_ba_result)};
@@ -837,10 +728,10 @@ int vo_window_from_tracks_dev(vo_ctx* ctx, int W, const void* const* d_records, 
                               int32_t* d_lm_start, int32_t* d_obs_slot, double* d_obs_xy, double* d_X, int32_t* d_lm_id) {
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, d_records && d_head && d_lm_start && d_obs_slot && d_obs_xy && d_X && d_lm_id, "window_from_tracks: null pointer");
-  VO_TRY(check_shape(ctx, "window_from_tracks", W, L_cap, M_cap));
+  VO_TRY(vo_check_window_shape(ctx, "window_from_tracks", 1, W, L_cap, M_cap));
   VO_REQUIRE(ctx, cap >= 1 && cap <= (1 << 20), "window_from_tracks: cap must be 1 .. 1048576 rows, got %d", cap);
   wb_records R;
-  for (int s = 0; s < BA_WMAX; ++s) R.rec[s] = nullptr;
+  for (int s = 0; s < VO_WINDOW_WMAX; ++s) R.rec[s] = nullptr;
   for (int s = 0; s < W; ++s) {
     VO_REQUIRE(ctx, d_records[s] && ((uintptr_t)d_records[s] & 15) == 0, "window_from_tracks: record %d is null or not 16-byte aligned", s);
     R.rec[s] = (const unsigned long long*)d_records[s];
@@ -848,7 +739,6 @@ int vo_window_from_tracks_dev(vo_ctx* ctx, int W, const void* const* d_records, 
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   VO_TRY(vo_ensure(ctx, ctx->ba_match, (size_t)cap * W * sizeof(int)));
   hipStream_t st = ctx->stream;
-  VO_HIP_TRY(ctx, hipMemsetAsync(d_head, 0, 16, st));
   {
     vo_prof_scope ps(ctx, VO_K_WINDOW_BUILD);
     hipLaunchKernelGGL(window_match_kernel, dim3(vo_cdiv(cap, WB_T), W), dim3(WB_T), 0, st, R, W, cap, (int*)ctx->ba_match.p);

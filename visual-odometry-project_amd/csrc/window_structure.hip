@@ -25,7 +25,6 @@ namespace {
 constexpr int WS_T = 256;                         // threads per workgroup
 constexpr int WS_ROW = 16;                        // lanes per landmark
 constexpr int WS_LM = WS_T / WS_ROW;              // landmarks per workgroup
-constexpr int WS_WMAX = 16;                       // slots per window
 constexpr double WS_LAMBDA_MAX = 1e12, WS_LAMBDA_MIN = 1e-12;
 
 struct ws_args {
@@ -90,7 +89,7 @@ __device__ __forceinline__ ws_point ws_eval(const ws_obs& o, double fx, double f
 }
 
 __global__ __launch_bounds__(WS_T) void window_structure_kernel(ws_args a) {
-  __shared__ double s_pose[WS_WMAX * 12 + 4];
+  __shared__ double s_pose[VO_WINDOW_WMAX * 12 + 4];
   const int tid = threadIdx.x, r = tid & (WS_ROW - 1);
   const size_t q = blockIdx.y;
   const int W = a.W;
@@ -111,15 +110,15 @@ __global__ __launch_bounds__(WS_T) void window_structure_kernel(ws_args a) {
     const double v = a.poses[q * (size_t)W * 12 + tid];
     s_pose[tid] = v;
     wbad = wbad || !isfinite(v);
-  } else if (tid >= WS_WMAX * 12 && tid < WS_WMAX * 12 + 4) {
-    const int k = tid - WS_WMAX * 12;
+  } else if (tid >= VO_WINDOW_WMAX * 12 && tid < VO_WINDOW_WMAX * 12 + 4) {
+    const int k = tid - VO_WINDOW_WMAX * 12;
     const double v = a.K[q * 9 + (k == 0 ? 0 : k == 1 ? 4 : k == 2 ? 2 : 5)];        // fx, fy, cx, cy
     s_pose[tid] = v;
     wbad = wbad || !isfinite(v);
   }
   wbad = __syncthreads_or(wbad) != 0;
-  const double fx = s_pose[WS_WMAX * 12], fy = s_pose[WS_WMAX * 12 + 1], cx = s_pose[WS_WMAX * 12 + 2],
-               cy = s_pose[WS_WMAX * 12 + 3];
+  const double fx = s_pose[VO_WINDOW_WMAX * 12], fy = s_pose[VO_WINDOW_WMAX * 12 + 1], cx = s_pose[VO_WINDOW_WMAX * 12 + 2],
+               cy = s_pose[VO_WINDOW_WMAX * 12 + 3];
 
   // ---- the landmark of this row ----
   const bool live = i < rows;                                        // (from here on everything is the same along a row)
@@ -393,18 +392,13 @@ int resolve_params(vo_ctx* ctx, const vo_structure_params* prm, ws_args* a) {
   vo_structure_params p;
   memset(&p, 0, sizeof(p));
   if (prm) p = *prm;
-  VO_REQUIRE(ctx, p.max_iter >= 0 && p.max_iter <= 50, "window_structure: max_iter must be 0 (default 10) .. 50, got %d", p.max_iter);
-  a->max_iter = p.max_iter ? p.max_iter : 10;
-  VO_REQUIRE(ctx, p.max_trials >= 0 && p.max_trials <= 1000,
-             "window_structure: max_trials must be 0 (default 2 * max_iter) .. 1000, got %d", p.max_trials);
-  a->max_trials = p.max_trials ? p.max_trials : 2 * a->max_iter;
-  VO_REQUIRE(ctx, p.huber_px >= 0.0 && std::isfinite(p.huber_px),
-             "window_structure: huber_px must be 0 (squared loss) or a positive number of pixels");
-  a->huber = p.huber_px;
-  VO_REQUIRE(ctx, p.lambda0 >= 0.0 && std::isfinite(p.lambda0), "window_structure: lambda0 must be 0 (default 1e-3) or positive");
-  a->lambda0 = p.lambda0 > 0.0 ? p.lambda0 : 1e-3;
-  VO_REQUIRE(ctx, p.step_tol >= 0.0 && std::isfinite(p.step_tol), "window_structure: step_tol must be 0 (default 1e-10) or positive");
-  a->step_tol = p.step_tol > 0.0 ? p.step_tol : 1e-10;
+  vo_lm_params lm;
+  VO_TRY(vo_resolve_lm_params(ctx, "window_structure", p.max_iter, p.max_trials, p.huber_px, p.lambda0, p.step_tol, &lm));
+  a->max_iter = lm.max_iter;
+  a->max_trials = lm.max_trials;
+  a->huber = lm.huber;
+  a->lambda0 = lm.lambda0;
+  a->step_tol = lm.step_tol;
   VO_REQUIRE(ctx, p.f_tol >= 0.0 && std::isfinite(p.f_tol), "window_structure: f_tol must be 0 (default 1e-9) or positive");
   a->f_tol = p.f_tol > 0.0 ? p.f_tol : 1e-9;
   VO_REQUIRE(ctx, p.gate_px >= 0.0 && std::isfinite(p.gate_px), "window_structure: gate_px must be 0 (no gate) or a positive number of pixels");
@@ -412,15 +406,6 @@ int resolve_params(vo_ctx* ctx, const vo_structure_params* prm, ws_args* a) {
   VO_REQUIRE(ctx, p.min_parallax >= 0.0 && p.min_parallax < 3.141592653589793,
              "window_structure: min_parallax must be 0 (no gate) or an angle below pi, in radians");
   a->cos_limit = p.min_parallax > 0.0 ? std::cos(p.min_parallax) : 2.0;
-  return VO_OK;
-}
-
-int check_shape(vo_ctx* ctx, int S, int W, int L_cap, int M_cap) {
-  VO_REQUIRE(ctx, S >= 1 && S <= 4096, "window_structure: S must be 1 .. 4096 windows, got %d", S);
-  VO_REQUIRE(ctx, W >= 2 && W <= WS_WMAX, "window_structure: W must be 2 .. %d slots, got %d", WS_WMAX, W);
-  VO_REQUIRE(ctx, L_cap >= 1 && L_cap <= (1 << 20), "window_structure: L_cap must be 1 .. 1048576 landmarks, got %d", L_cap);
-  VO_REQUIRE(ctx, M_cap >= 1 && (long long)M_cap <= (long long)L_cap * W,
-             "window_structure: M_cap must be 1 .. L_cap * W observations, got %d", M_cap);
   return VO_OK;
 }
 
@@ -435,7 +420,7 @@ int vo_window_structure_dev(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, con
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, d_counts && d_K && d_poses && d_X && d_lm_start && d_obs_slot && d_obs_xy && d_results && d_summary,
              "window_structure: null pointer");
-  VO_TRY(check_shape(ctx, S, W, L_cap, M_cap));
+  VO_TRY(vo_check_window_shape(ctx, "window_structure", S, W, L_cap, M_cap));
   ws_args a;
   VO_TRY(resolve_params(ctx, prm, &a));
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -468,7 +453,7 @@ int vo_window_structure(vo_ctx* ctx, int S, int W, int L_cap, int M_cap, const i
                         const vo_structure_params* prm, vo_structure_result* results, vo_structure_summary* summary) {
   if (!ctx) return VO_EINVAL;
   VO_REQUIRE(ctx, counts && K && poses && X && lm_start && obs_slot && obs_xy && results && summary, "window_structure: null pointer");
-  VO_TRY(check_shape(ctx, S, W, L_cap, M_cap));
+  VO_TRY(vo_check_window_shape(ctx, "window_structure", S, W, L_cap, M_cap));
   const size_t s = (size_t)S;
   const size_t bytes[9] = {s * 16,        s * 72,         s * W * 96,
                            s * L_cap * 24, s * ((size_t)L_cap + 1) * 4,

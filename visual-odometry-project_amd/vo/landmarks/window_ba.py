@@ -61,22 +61,18 @@ class _Arena:
         self.d = {}
 
 
-class WindowBundleAdjuster:
-    """The last `window` observation records of one sequence and the poses of their frames; solve() adjusts them.
+class _WindowHolder:
+    """The last `window` observation records of one sequence (device pointers the caller keeps alive while they are among
+    them) and the poses of their frames.  cap: the capacity the records were exported with (Pipeline.cap); L_cap: landmarks
+    a window may hold (default: cap)."""
 
-    K: the sequence's intrinsics.  n_fixed, huber_px, max_iter: vo_ba_params (0 = its default).  cap: the capacity the
-    records were exported with (Pipeline.cap); L_cap: landmarks a window may hold (default: cap).  Records are device
-    pointers the caller keeps alive while they are among the last `window` pushed."""
-
-    def __init__(self, K, window=8, n_fixed=2, huber_px=0.0, max_iter=0, cap=None, L_cap=None, context=None):
+    def __init__(self, K, window, cap, L_cap, context):
         from vo import _native
         if not 2 <= int(window) <= 16:
-            raise ValueError("WindowBundleAdjuster: window must be 2 .. 16 frames, got %r" % (window,))
-        if not 1 <= int(n_fixed) < int(window):
-            raise ValueError("WindowBundleAdjuster: n_fixed must be 1 .. window - 1, got %r" % (n_fixed,))
+            raise ValueError("%s: window must be 2 .. 16 frames, got %r" % (type(self).__name__, window))
         self.ctx = context or _native.default_context()
         self.K = np.asarray(K, np.float64).reshape(3, 3).copy()
-        self.window, self.params = int(window), dict(n_fixed=int(n_fixed), huber_px=float(huber_px), max_iter=int(max_iter))
+        self.window = int(window)
         self.cap, self.L_cap = cap, L_cap
         self.records, self.poses = [], []
         self._arena = None
@@ -94,6 +90,20 @@ class WindowBundleAdjuster:
         if self._arena:
             self._arena.close()
             self._arena = None
+
+
+class WindowBundleAdjuster(_WindowHolder):
+    """The last `window` observation records of one sequence and the poses of their frames; solve() adjusts them.
+
+    K: the sequence's intrinsics.  n_fixed, huber_px, max_iter: vo_ba_params (0 = its default).  cap: the capacity the
+    records were exported with (Pipeline.cap); L_cap: landmarks a window may hold (default: cap).  Records are device
+    pointers the caller keeps alive while they are among the last `window` pushed."""
+
+    def __init__(self, K, window=8, n_fixed=2, huber_px=0.0, max_iter=0, cap=None, L_cap=None, context=None):
+        super().__init__(K, window, cap, L_cap, context)
+        if not 1 <= int(n_fixed) < int(window):
+            raise ValueError("WindowBundleAdjuster: n_fixed must be 1 .. window - 1, got %r" % (n_fixed,))
+        self.params = dict(n_fixed=int(n_fixed), huber_px=float(huber_px), max_iter=int(max_iter))
 
     def solve(self):
         """(poses (W, 12), ids (L,), landmarks (L, 3), result) of the window held, or None when fewer than `window`

@@ -12,10 +12,10 @@ import types
 
 import numpy as np
 
-from .window_ba import _full_windows, _join_windows, pose_cw12
+from .window_ba import _WindowHolder, _full_windows, _join_windows
 
 
-class WindowStructureRefiner:
+class WindowStructureRefiner(_WindowHolder):
     """The last `window` observation records of one sequence and the poses of their frames; solve() refines the landmarks.
 
     K: the sequence's intrinsics.  huber_px, max_iter, gate_px, min_parallax: vo_structure_params (0 = its default).  cap:
@@ -23,30 +23,8 @@ class WindowStructureRefiner:
     are device pointers the caller keeps alive while they are among the last `window` pushed."""
 
     def __init__(self, K, window=8, huber_px=0.0, max_iter=0, gate_px=0.0, min_parallax=0.0, cap=None, L_cap=None, context=None):
-        from vo import _native
-        if not 2 <= int(window) <= 16:
-            raise ValueError("WindowStructureRefiner: window must be 2 .. 16 frames, got %r" % (window,))
-        self.ctx = context or _native.default_context()
-        self.K = np.asarray(K, np.float64).reshape(3, 3).copy()
-        self.window = int(window)
+        super().__init__(K, window, cap, L_cap, context)
         self.params = dict(huber_px=float(huber_px), max_iter=int(max_iter), gate_px=float(gate_px), min_parallax=float(min_parallax))
-        self.cap, self.L_cap = cap, L_cap
-        self.records, self.poses = [], []
-        self._arena = None
-
-    def reset(self):
-        """Forgets the window (a hand-over: ids start again and a window must not span it)."""
-        self.records, self.poses = [], []
-
-    def push(self, d_record, pose_cw):
-        """The record of the next step (device pointer) and that frame's world -> camera pose."""
-        self.records = (self.records + [int(d_record)])[-self.window:]
-        self.poses = (self.poses + [pose_cw12(pose_cw)])[-self.window:]
-
-    def close(self):
-        if self._arena:
-            self._arena.close()
-            self._arena = None
 
     def solve(self):
         """The window held, refined: a namespace with poses (W, 12) as given, ids (L,), landmarks (L, 3), results (L,)
