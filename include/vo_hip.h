@@ -101,7 +101,9 @@ enum {
   VO_K_LOOP_RECORD = 33,        /* vo_structure_loop_post: the record into the ring and its ids into the table */
   VO_K_LOOP_JOIN = 34,          /* ... the header check and the join, one workgroup per lane */
   VO_K_LOOP_WRITE = 35,         /* ... the entry and the write-back (also when it is queued again behind a redone step) */
-  VO_K_COUNT = 36
+  VO_K_BRIEF_DESCRIBE = 36,     /* vo_brief_describe_dev's kernel */
+  VO_K_HAMMING_KNN2 = 37,       /* vo_hamming_knn2_dev's kernel */
+  VO_K_COUNT = 38
 };
 int vo_prof_enable(vo_ctx* ctx, int kernel_id);
 /* bracket only every n-th launch of a profiled kernel (default 1): the event pair itself costs
@@ -335,6 +337,52 @@ enum { VO_MATCH_PATH_FLOAT = 0, VO_MATCH_PATH_BYTE_DOT = 1, VO_MATCH_PATH_MFMA =
 int vo_match_knn2(vo_ctx* ctx, const float* q, int nq, const float* t, int nt, int D,
                   int32_t* best, double* d2, int* path);
 int vo_match_last_path(vo_ctx* ctx);
+
+/* ---- BRIEF-256 binary descriptors and Hamming matching (brief.hip) --------------------
+ * The project's own definition, in the spirit of ORB's rBRIEF (it is not OpenCV's pattern; the reference has no binary
+ * descriptor).  Everything is integer arithmetic except the centre and the ratio test's one multiply, so the kernels
+ * equal tests/brief_reference.py bit for bit on every input.
+ *   image    uint8 H x W, zero outside (as vo_patch_descriptors): rows stay index-aligned with the keypoints, no
+ *            keypoint is dropped.
+ *   centre   cx = floor(x + 0.5), cy = floor(y + 0.5) in float64, (x, y) as in kp_xy of vo_harris_keypoints.  A
+ *            non-finite coordinate, or a centre outside [-16, W + 16) x [-16, H + 16), gives an all-zero descriptor
+ *            and bin 0.
+ *   S(y, x)  the sum of I over the 5 x 5 box centred on (y, x): an integer, at most 6375.
+ *   pattern  256 pairs (a_i, b_i) of integer offsets inside the disc of radius 13, a_i != b_i, no pair twice, drawn by
+ *            np.random.default_rng(VO_BRIEF_SEED) from an isotropic Gaussian of sigma = 13 / 2 with rejection, and 30
+ *            rotated tables: table k turns every offset by 12 k degrees and rounds half away from zero in float64.
+ *            tools/make_brief_pattern.py draws them (its header lists every rejection rule), asserts that no rotated
+ *            coordinate lies within 1e-9 of a rounding boundary and that every rotated offset stays within radius 14
+ *            (so a descriptor reads at most 16 pixels from its centre), and writes csrc/brief_pattern.h.
+ *   bits     bit i = 1 iff S(c + a_i^k) < S(c + b_i^k), k the keypoint's bin (0 when not oriented); bit i is stored
+ *            in byte i / 8 at position i % 8, least significant first.  A descriptor is 32 bytes.
+ *   bin      (oriented = 1) on the raw image: m10 = sum dx I, m01 = sum dy I over dx^2 + dy^2 <= 15^2;
+ *            k = argmax_k (m10 C[k] + m01 Sn[k]) in int64, C[k] = round(16384 cos(2 pi k / 30)), Sn[k] likewise for
+ *            sin (both in csrc/brief_pattern.h); ties go to the lowest k, so a flat patch has bin 0.
+ * vo_brief_describe: host pointers; kp_xy N x 2 float64, desc N x 32 bytes, bin N bytes or NULL (the bins; all 0 when
+ * oriented = 0); 1 <= N <= 16384, oriented 0 or 1.  vo_brief_describe_dev: device pointers, enqueued on the context's
+ * stream, neither synchronises nor reads back.  vo_brief_pattern: the 30 x 256 x 4 table (ax, ay, bx, by) the library
+ * was built with.  A refused call returns VO_EINVAL with a message and writes nothing.                              */
+int vo_brief_describe(vo_ctx* ctx, const uint8_t* img, int H, int W, const double* kp_xy, int N, int oriented,
+                      uint8_t* desc, uint8_t* bin /* nullable */);
+int vo_brief_describe_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const double* d_kp_xy, int N, int oriented,
+                          uint8_t* d_desc, uint8_t* d_bin /* nullable */);
+int vo_brief_pattern(int8_t* out);
+/* Hamming 2-NN.  Rows of row_bytes bytes, row_bytes a multiple of 4 in 4 .. 64.  For every query the two train rows
+ * smallest under the total order (distance, train index): best nq x 2 train indices, dist nq x 2 distances, both int32;
+ * an absent neighbour is -1 with distance 0, as vo_match_knn2 has it.  vo_match_hamming_knn2: host pointers, nq and nt
+ * may be 0.  vo_hamming_knn2_dev: device pointers on a 4-byte boundary, nq >= 1, nt >= 0, enqueued on the context's
+ * stream without synchronising.
+ * vo_match_hamming_ratio: the pair list.  Queries are taken in order; query q gives (q, best) iff nt >= 2,
+ * float64(d1) < ratio * float64(d2) with one IEEE multiply, d1 <= max_dist when max_dist >= 0, and best was not taken by
+ * an earlier query that met the same three conditions -- the first-come rule of vo_match_knn2_ratio.  pairs: up to nq
+ * (query, train) rows; n_pairs: rows written.                                                                       */
+int vo_match_hamming_knn2(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int row_bytes,
+                          int32_t* best, int32_t* dist);
+int vo_hamming_knn2_dev(vo_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int row_bytes,
+                        int32_t* d_best, int32_t* d_dist);
+int vo_match_hamming_ratio(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int row_bytes,
+                           double ratio, int max_dist, int32_t* pairs, int32_t* n_pairs);
 
 /* ---- Shi-Tomasi corners -----------------------------------------------------------
  * [ref: src/vo/features/klt.py:98]  cv2.goodFeaturesToTrack(img, mask, maxCorners,

@@ -211,7 +211,8 @@ static const char* const k_names[VO_K_COUNT] = {
     "patch_descriptors", "pyr_down", "klt_track", "dlt_triangulate", "p3p_solve",
     "p3p_score", "reproj_inliers", "match_knn2", "track_gather", "nms_round", "nms_collect", "nms_rank", "nms_emit", "sift_scale_space", "sift_detect", "sift_describe", "refine_pose",
     "state_candidates", "state_regroup", "ransac_replay", "state_landmarks", "export_state", "shi_tomasi_chain", "window_ba", "window_build",
-    "twoview_hyp", "twoview_score", "window_structure", "loop_record", "loop_join", "loop_write"};
+    "twoview_hyp", "twoview_score", "window_structure", "loop_record", "loop_join", "loop_write",
+    "brief_describe", "hamming_knn2"};
 
 const char* vo_kernel_name(int k) {
   if (k < 0 || k >= VO_K_COUNT || !k_names[k]) return "";

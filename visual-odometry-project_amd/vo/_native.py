@@ -25,7 +25,8 @@ K_WINDOW_BA, K_WINDOW_BUILD = 28, 29          # vo_window_ba_dev's solver; vo_wi
 K_TWOVIEW_HYP, K_TWOVIEW_SCORE = 30, 31      # f8_hyp_kernel / e5_hyp_kernel and f_score_kernel / e5_score_kernel
 K_WINDOW_STRUCTURE = 32                       # vo_window_structure_dev, both launches
 K_LOOP_RECORD, K_LOOP_JOIN, K_LOOP_WRITE = 33, 34, 35     # vo_structure_loop_post's three kernels
-K_COUNT = 36
+K_BRIEF_DESCRIBE, K_HAMMING_KNN2 = 36, 37                 # vo_brief_describe_dev / vo_hamming_knn2_dev
+K_COUNT = 38
 
 
 class VoError(RuntimeError):
@@ -225,6 +226,12 @@ _SIGS = {
     "vo_knn2_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "vo_match_knn2": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, C.POINTER(_i)]),
     "vo_match_last_path": (_i, [_vp]),
+    "vo_brief_describe": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "vo_brief_describe_dev": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "vo_brief_pattern": (_i, [_vp]),
+    "vo_match_hamming_knn2": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "vo_hamming_knn2_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "vo_match_hamming_ratio": (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _vp, _vp]),
     "vo_good_features": (_i, [_vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _vp, _vp]),
     "vo_min_eigen_map": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "vo_good_features_capacity": (_i, [_i, _i, _i]),
@@ -548,6 +555,68 @@ class Context:
     def match_last_path(self):
         """The kernel the last match_knn2_ratio / match_knn2 call of this context kept (vo_match_last_path); -1: none ran."""
         return int(self._lib.vo_match_last_path(self._h))
+
+    # ---- BRIEF-256 and Hamming matching (csrc/brief.hip) ----
+    def brief_describe(self, img, kp_xy, oriented=False, want_bins=False):
+        """(N, 32) uint8 BRIEF-256 descriptors of the keypoints (vo_brief_describe), rows index-aligned with kp_xy;
+        with want_bins also the (N,) uint8 orientation bins (all 0 unless oriented)."""
+        img = _c(img, np.uint8)
+        assert img.ndim == 2
+        kp = _c(np.asarray(kp_xy).reshape(-1, 2), np.float64)
+        H, W = img.shape
+        n = kp.shape[0]
+        desc = np.empty((n, 32), np.uint8)
+        bins = np.empty((n,), np.uint8) if want_bins else None
+        self._chk(self._lib.vo_brief_describe(self._h, _ptr(img), H, W, _ptr(kp), n, 1 if oriented else 0, _ptr(desc),
+                                              _ptr(bins)))
+        return (desc, bins) if want_bins else desc
+
+    def brief_describe_dev(self, d_img, H, W, d_kp, N, oriented, d_desc, d_bin=None):
+        self._chk(self._lib.vo_brief_describe_dev(self._h, C.c_void_p(d_img), int(H), int(W), C.c_void_p(d_kp), int(N),
+                                                  1 if oriented else 0, C.c_void_p(d_desc), C.c_void_p(d_bin)))
+
+    def brief_pattern(self):
+        """The (30, 256, 4) int8 table (ax, ay, bx, by) the library was built with (vo_brief_pattern)."""
+        out = np.empty((30, 256, 4), np.int8)
+        rc = self._lib.vo_brief_pattern(_ptr(out))
+        if rc != VO_OK:
+            raise VoError(rc, "vo_brief_pattern failed")
+        return out
+
+    @staticmethod
+    def _byte_rows(q, t):
+        q, t = np.asarray(q), np.asarray(t)
+        if len(q) == 0 or len(t) == 0:                      # (no distance is computed: the rows' length does not matter)
+            return np.zeros((len(q), 4), np.uint8), np.zeros((len(t), 4), np.uint8)
+        q, t = _c(q.reshape(len(q), -1), np.uint8), _c(t.reshape(len(t), -1), np.uint8)
+        assert q.shape[1] == t.shape[1]
+        return q, t
+
+    def match_hamming_knn2(self, q, t):
+        """The two train rows nearest to every query under (Hamming distance, train index) (vo_match_hamming_knn2): best
+        (nq, 2) int32, -1 where absent; dist (nq, 2) int32, 0 where absent.  Rows are uint8, a multiple of 4 in 4 .. 64 long."""
+        q, t = self._byte_rows(q, t)
+        best = np.empty((q.shape[0], 2), np.int32)
+        dist = np.empty((q.shape[0], 2), np.int32)
+        self._chk(self._lib.vo_match_hamming_knn2(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], q.shape[1],
+                                                  _ptr(best), _ptr(dist)))
+        return best, dist
+
+    def hamming_knn2_dev(self, d_q, nq, d_t, nt, row_bytes, d_best, d_dist):
+        self._chk(self._lib.vo_hamming_knn2_dev(self._h, C.c_void_p(d_q), int(nq), C.c_void_p(d_t), int(nt), int(row_bytes),
+                                                C.c_void_p(d_best), C.c_void_p(d_dist)))
+
+    def match_hamming_ratio(self, q, t, ratio, max_dist=-1):
+        """(n, 2) int64 pairs (query, train) in query order: ratio test on the Hamming distances, the distance limit
+        (max_dist >= 0) and first-come uniqueness (vo_match_hamming_ratio)."""
+        if len(q) == 0 or len(t) == 0:
+            return np.empty((0, 2), np.int64)
+        q, t = self._byte_rows(q, t)
+        pairs = np.empty((q.shape[0], 2), np.int32)
+        n = C.c_int32(0)
+        self._chk(self._lib.vo_match_hamming_ratio(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], q.shape[1],
+                                                   float(ratio), int(max_dist), _ptr(pairs), C.byref(n)))
+        return pairs[: n.value].astype(np.int64)
 
     def knn2_u8_batch_dev(self, d_q, q_stride, d_nq, nq_stride, cap_q, d_t, t_stride, d_nt, nt_stride, cap_t, S, row_bytes,
                           d_best, d_d2):

@@ -1,5 +1,6 @@
 """Tracker selection (reference: src/vo/features/tracker.py): the one entry point the
 driver calls per frame."""
+from vo.features.brief import BRIEFDetector
 from vo.features.harris import HarrisCornerDetector
 from vo.features.klt import KLTTracker
 from vo.features.sift import SIFTDetector
@@ -9,6 +10,7 @@ _TRACKERS = {
     "klt": (KLTTracker, "track_features"),
     "harris": (HarrisCornerDetector, "featureMatcher"),
     "sift": (SIFTDetector, "get_sift_matches"),
+    "brief": (BRIEFDetector, "get_brief_matches"),     # not in the reference: corners + BRIEF-256 + Hamming matching
 }
 
 
