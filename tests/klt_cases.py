@@ -1,5 +1,5 @@
 """The case table of the Lucas-Kanade tracker's tests.  tests/test_klt_reference_host.py runs every case through the oracle
-(oracle/csrc/klt.c) and tests/test_gpu_klt_reference.py through the kernels of csrc/klt.hip; both compare the result with the
+(oracle/csrc/klt.c) and tests/test_gpu_klt_reference.py through the kernels of csrc/klt.hip and csrc/pyramid.hip; both compare the result with the
 float64 definition of tests/klt_reference.py by the checks at the end of this file, and the GPU file also with the oracle bit
 for bit.
 
@@ -205,8 +205,8 @@ def _build():
             name = "win%d_%s" % (win, tex)
 
             def g(win=win, name=name):
-                # (which kernel a window gets, MAX_WIN and PYR_PAD are read from csrc/klt.hip by the host file's
-                #  test_constants_are_the_kernels)
+                # (which kernel a window gets and MAX_WIN are read from csrc/klt.hip, PYR_PAD from csrc/pyramid_device.h, by
+                #  the host file's test_constants_are_the_kernels)
                 assert 3 <= win <= MAX_WIN
                 # 96 x 128 with three levels: level 2 is 24 x 32, a side <= PYR_PAD, so the bordered builder takes the
                 # per-level kernels and their border reflects more than once

@@ -1,5 +1,5 @@
 """-m gpu: the Lucas-Kanade kernels of csrc/klt.hip (klt_track16_kernel<15,16>, <17,32>, <21,32> and the generic
-klt_track_kernel<0>) and the pyramid builders against the float64 definition of tests/klt_reference.py, directly, on every
+klt_track_kernel<0>) and the pyramid builders of csrc/pyramid.hip against the float64 definition of tests/klt_reference.py, directly, on every
 case of tests/klt_cases.py -- and, separately, against the oracle bit for bit.  tests/test_klt_reference_host.py runs the same
 checks on the oracle and asserts each case's edge and the 10 % cap."""
 import os

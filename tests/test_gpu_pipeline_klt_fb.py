@@ -27,8 +27,8 @@ def start():
     return stream, feats, T, list(zip(order[:-1], order[1:]))
 
 
-def fb_pipe(ctx, stream, feats, T, fb_max=P["fb_max"], **kw):
-    pipe = make_pipe(ctx, stream, P["N"], P["hyp"], win=P["win"], lvl=P["lvl"], redetect_start_pose=P["redetect"], **kw)
+def fb_pipe(ctx, stream, feats, T, fb_max=P["fb_max"], win=P["win"], **kw):
+    pipe = make_pipe(ctx, stream, P["N"], P["hyp"], win=win, lvl=P["lvl"], redetect_start_pose=P["redetect"], **kw)
     if fb_max is not None:
         pipe.set_klt_fb(fb_max)
     pipe.set_state(0, feats, T, T)
@@ -122,6 +122,13 @@ def test_lookahead_equals_blocking_steps(ctx, start, blocking):
 
 def test_two_sequences_equal_each_run_alone(ctx, start, blocking):
     """sequences = 2: the stream above and another scene from another start; fb strides like err."""
+    two_sequences_equal_each_run_alone(ctx, start, blocking, P["win"], P["fb_max"])
+
+
+def two_sequences_equal_each_run_alone(ctx, start, blocking, win, fb_max, device_only=False, **pipe_kw):
+    """blocking: (records, state, generator) of `start`'s sequence run alone at this window and threshold (None: plain).
+    pipe_kw: further pipeline settings of every run; device_only: no step of any run may take the host path, and each
+    sequence re-detects."""
     import copy
     from pipeline_oracle import initial_features
     from vo import _native, synthetic
@@ -129,14 +136,15 @@ def test_two_sequences_equal_each_run_alone(ctx, start, blocking):
     other = synthetic.Stream(P["F"], P["H"], P["W"], seed=2030, start=1)
     f1, T1 = initial_features(other, 0, P["N"])
     f1 = copy.deepcopy(f1)
-    alone = fb_pipe(ctx, other, f1, T1)
+    alone = fb_pipe(ctx, other, f1, T1, fb_max=fb_max, win=win, **pipe_kw)
     res1 = run_all(alone, pairs, False)
     st1, g1 = finish(alone)
     alone.close()
-    pipe = _native.Pipeline(ctx, P["H"], P["W"], P["F"], stream.K, n_keypoints=P["N"], klt_win=P["win"], klt_max_level=P["lvl"],
+    pipe = _native.Pipeline(ctx, P["H"], P["W"], P["F"], stream.K, n_keypoints=P["N"], klt_win=win, klt_max_level=P["lvl"],
                             hyp=P["hyp"], p3p_threshold=1.0, max_iterations=1000, refine_iters=20, sequences=2,
-                            redetect_start_pose=P["redetect"])
-    pipe.set_klt_fb(P["fb_max"])
+                            redetect_start_pose=P["redetect"], **pipe_kw)
+    if fb_max is not None:
+        pipe.set_klt_fb(fb_max)
     for q, (s, f, t) in enumerate(((stream, feats, T), (other, f1, T1))):
         for i in range(P["F"]):
             pipe.set_frame(i, s.image(i), seq=q)
@@ -150,6 +158,8 @@ def test_two_sequences_equal_each_run_alone(ctx, start, blocking):
     for q, (res, st_ref, g_ref) in enumerate((blocking, (res1, st1, g1))):
         for k in range(len(pairs)):
             assert fields(got[k][q]) == fields(res[k]), ("sequence", q, "step", k)
+            assert not device_only or (got[k][q].recovered == 0 and res[k].recovered == 0), ("sequence", q, "step", k)
+        assert not device_only or sum(r.redetected for r in res) >= 1, ("sequence", q)
         st, g = finish(pipe, q)
         same_state(st, st_ref)
         assert g == g_ref

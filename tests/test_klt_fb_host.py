@@ -191,7 +191,11 @@ def test_drivers_take_klt_fb_and_refuse_bad_values():
 
 # ---- the loop guard ----
 
+OTHER_WINDOWS = (9, 17, 21)          # the generic kernel and the two other row kernels (LOOP's 15 is the third)
+
+
 def loop_start():
+    """Stream, thinned start features and start pose of the loop; the same for every window (the start does not track)."""
     import copy
     from pipeline_oracle import initial_features
     from vo import synthetic
@@ -205,13 +209,29 @@ def loop_start():
     return stream, feats, T
 
 
-def oracle_loop(stream, fb_max, seed=2023):
+def oracle_loop(stream, fb_max, seed=2023, win=LOOP["win"]):
     from pipeline_oracle import OracleLoop
-    p = LOOP
+    p = dict(LOOP, win=win)
     kw = dict(refine_iters=20, redetect_start_pose=p["redetect"], seed=seed)
     if fb_max is None:
         return OracleLoop(stream, p["N"], p["win"], p["lvl"], **kw)
     return fbo.FBOracleLoop(stream, p["N"], p["win"], p["lvl"], fb_max=fb_max, **kw)
+
+
+@pytest.mark.parametrize("fb_max", [None, LOOP["fb_max"]], ids=["plain", "fb"])
+@pytest.mark.parametrize("win", OTHER_WINDOWS)
+def test_oracle_loops_redetect_at_the_other_windows(win, fb_max):
+    """What tests/test_gpu_pipeline_klt_windows.py needs of the reference alone: at windows 9, 17 and 21 the loop's tracked
+    count rises in at least one step, which only a re-detect does (measured: one such step plain, two with the check, at
+    every window)."""
+    stream, feats, T = loop_start()
+    orc = oracle_loop(stream, fb_max, win=win)
+    assert orc.cfg["win"] == win and LOOP["win"] == 15
+    orc.set_state(0, feats, T, T)
+    counts = [orc.step(b)["n_tracked"] for b in stream.order(LOOP["steps"])[1:]]
+    rises = sum(1 for a, b in zip(counts[:-1], counts[1:]) if b > a)
+    print("window", win, "fb" if fb_max else "plain", counts, "rises", rises)
+    assert rises >= 1, counts
 
 
 def test_fb_oracle_loop_drops_features_the_plain_loop_keeps():

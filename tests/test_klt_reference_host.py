@@ -42,16 +42,28 @@ def test_num_levels_oracle_equals_definition(H, W, win, max_level):
 
 def test_constants_are_the_kernels():
     """MAX_WIN, PYR_PAD and the windows that get a specialised kernel (with its keypoints per wave: 64 lanes / lanes per
-    keypoint, which is also the launch's divisor of N), read from csrc/klt.hip."""
+    keypoint, which is also the launch's divisor of N), read from csrc/klt.hip (MAX_WIN, the launch table and the one row
+    launch made from it), csrc/pyramid_device.h (PYR_PAD) and csrc/pyramid.hip (the one-launch condition)."""
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "visual-odometry-project_amd", "csrc", "klt.hip")).read()
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "visual-odometry-project_amd", "csrc")
+    src, header, pyramid = (open(os.path.join(csrc, name)).read() for name in ("klt.hip", "pyramid_device.h", "pyramid.hip"))
     assert int(re.search(r"constexpr int MAX_WIN = (\d+);", src).group(1)) == kc.MAX_WIN
-    assert int(re.search(r"constexpr int PYR_PAD = (\d+);", src).group(1)) == kc.PYR_PAD
-    assert re.search(r"n_levels >= 3 && h2 > PYR_PAD && w2 > PYR_PAD", src)
-    launches = re.findall(r"case (\d+):.*?klt_track16_kernel<(\d+), (\d+)>, dim3\(vo_cdiv\(N, (\d+)\)", src, re.S)
-    assert launches and all(a == b and 64 // int(lanes) == int(div) for a, b, lanes, div in launches)
-    assert {int(a): int(div) for a, b, lanes, div in launches} == kc.SPECIALISED
+    assert int(re.search(r"constexpr int PYR_PAD = (\d+);", header).group(1)) == kc.PYR_PAD
+    assert "PYR_PAD =" not in src + pyramid and '#include "pyramid_device.h"' in src and '#include "pyramid_device.h"' in pyramid
+    assert re.search(r"n_levels >= 3 && h2 > PYR_PAD && w2 > PYR_PAD", pyramid)
+    # the table {window, lanes per keypoint}, whatever it and its fields are called ...
+    struct = re.search(r"struct (\w+) \{\s*int (\w+), (\w+);\s*\};\s*constexpr \1 (\w+)\[\] = \{(.*?)\};", src, re.S)
+    kind, f_win, f_lanes, table, body = struct.groups()
+    rows = [(int(a), int(b)) for a, b in re.findall(r"\{(\d+), (\d+)\}", body)]
+    # ... and every row launch is made from one entry of it: the kernel's window, its lanes per keypoint and the divisor of N
+    launches = re.findall(r"klt_track16_kernel<(\w+)\.(\w+), (\w+)\.(\w+), \w+>, dim3\(vo_cdiv\(N, 64 / (\w+)\.(\w+)\)", src)
+    assert len(launches) == 1 and len(re.findall(r"klt_track16_kernel<", src)) == 1
+    e1, a, e2, b, e3, c = launches[0]
+    assert e1 == e2 == e3 and (a, b, c) == (f_win, f_lanes, f_lanes)
+    assert re.search(r"constexpr %s %s = %s\[" % (kind, e1, table), src)
+    assert rows and all(64 % lanes == 0 for win, lanes in rows)
+    assert {win: 64 // lanes for win, lanes in rows} == kc.SPECIALISED
     assert all(n % kc.SPECIALISED[win] == rem for (win, n), rem in kc.REMAINDER.items())
 
 

@@ -1,6 +1,6 @@
 """Measurements of the tracker's forward-backward check (vo_klt_track_fb, vo_pipeline_set_klt_fb).
 
-kernel   1376 x 1241, ~2350 features, window 15, 3 levels, at 1 and 16 sequences (the same frame pair in 16 buffers of
+kernel   1376 x 1241, ~2350 features, every window of --win (default 15), 3 levels, at 1 and 16 sequences (the same frame pair in 16 buffers of
          its own): the forward launch, the fused forward-backward launch, and the unfused composition -- two plain launches
          (the second with the pyramids exchanged, from the first one's points) and a compare kernel.  The composition and
          the compare kernel exist in this tool only: a helper compiled here against csrc/vo_internal.h, which launches
@@ -11,7 +11,11 @@ loop     bench.py's resident one-sequence and 16-sequence loops (tools/dev/track
 stream   --loop-frames frames of the configuration stream through run_on_device with and without klt_fb: RMS position
          error after the one-scale fit, P3P inliers and inlier ratio, features the tracker's filter drops per step.
 
-    python3 tools/dev/klt_fb.py [--parts kernel,loop,stream] [--repeats 20] [--loop-frames 40] [--fb 1.0] [--helper-dir DIR] [--json OUT]
+--tree ROOT measures another checkout of the project (its package, its built library, its csrc for the helper) with this
+tool's code, in the manner of tools/dev/track_ids.py: two trees are compared by alternating fresh processes of this tool.
+
+    python3 tools/dev/klt_fb.py [--parts kernel,loop,stream] [--win 15[,17,...]] [--tree ROOT] [--repeats 20] [--loop-frames 40]
+                                [--fb 1.0] [--helper-dir DIR] [--json OUT]
 """
 import argparse
 import ctypes as C
@@ -83,7 +87,7 @@ extern "C" int klt_fb_time(vo_ctx* ctx, int form, const uint8_t* d_img, const ui
 """
 
 
-def build_helper(lib_path, helper_dir=None):
+def build_helper(lib_path, helper_dir=None, root=ROOT):
     """Compiles HELPER (or takes the one a previous --helper-dir run left) and loads it.  It is not linked against
     libvo_hip.so: the library is opened once more with RTLD_GLOBAL so that the helper's references resolve to it."""
     d = helper_dir or tempfile.mkdtemp(prefix="klt_fb_")
@@ -91,9 +95,9 @@ def build_helper(lib_path, helper_dir=None):
     src, out = os.path.join(d, "helper.hip"), os.path.join(d, "libklt_fb_helper.so")
     if not (os.path.exists(out) and os.path.exists(src) and open(src).read() == HELPER):
         open(src, "w").write(HELPER)
-        csrc = os.path.join(ROOT, "visual-odometry-project_amd", "csrc")
+        csrc = os.path.join(root, "visual-odometry-project_amd", "csrc")
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-ffp-contract=off",
-                        "-I" + csrc, "-I" + os.path.join(ROOT, "include"), src, "-o", out], check=True)
+                        "-I" + csrc, "-I" + os.path.join(root, "include"), src, "-o", out], check=True)
     C.CDLL(lib_path, mode=C.RTLD_GLOBAL)
     return C.CDLL(out)
 
@@ -106,20 +110,20 @@ def part_kernel(a, out):
     import numpy as np
     from vo import _native, synthetic
     ctx = _native.Context(0)
-    helper = build_helper(_native.lib_path(), a.helper_dir)
+    helper = build_helper(_native.lib_path(), a.helper_dir, a.tree)
     st = synthetic.Stream(2, H, W_IMG)
     img_a, img_b = st.image(0), st.image(1)
     kp = ctx.harris_keypoints(img_a, 9, 0.09, N_KP, 5).astype(np.float32)
     pts = np.ascontiguousarray(np.concatenate([kp, kp[:350] + 0.5]))
     N = len(pts)
-    nl = ctx.klt_num_levels(H, W_IMG, WIN, MAX_LEVEL)
-    pb = ctx.pyramid_bytes(H, W_IMG, nl)
     d_a, d_b = ctx.to_device(img_a), ctx.to_device(img_b)
     vp, f = C.c_void_p, helper.klt_fb_time
     f.restype = C.c_int
     f.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double,
                   C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float)]
-    for S in (1, 16):
+    for win, S in ((w, S) for w in a.win for S in (1, 16)):
+        nl = ctx.klt_num_levels(H, W_IMG, win, MAX_LEVEL)
+        pb = ctx.pyramid_bytes(H, W_IMG, nl)
         pa, pn = ctx.alloc(S * pb), ctx.alloc(S * pb)
         for q in range(S):
             ctx.pyramid_build_dev(d_a, H, W_IMG, nl, pa + q * pb)
@@ -131,14 +135,14 @@ def part_kernel(a, out):
         for form, name in ((0, "forward"), (1, "fused"), (2, "unfused"), (0, "forward_again")):
             ms, xs = C.c_float(0), []
             for r in range(a.repeats + 3):
-                rc = f(ctx._h, form, d_a, pa, pn, pb, S, H, W_IMG, nl, xy, N, WIN, 10, 0.03, 1e-4, a.fb, *bufs, C.byref(ms))
+                rc = f(ctx._h, form, d_a, pa, pn, pb, S, H, W_IMG, nl, xy, N, win, 10, 0.03, 1e-4, a.fb, *bufs, C.byref(ms))
                 assert rc == 0, (name, rc)
                 if r >= 3:
                     xs.append(1e3 * ms.value)
             res[name] = dict(us_median=med(xs), us_min=round(min(xs), 2), us_max=round(max(xs), 2))
             if form:
                 res[name]["kept"] = int(ctx.download(bufs[1], (S * N,), np.uint8)[:N].sum())
-        out["kernel_S%d" % S] = dict(points=N, **res)
+        out["kernel_S%d" % S + ("" if win == WIN else "_w%d" % win)] = dict(points=N, **res)
         for b in [pa, pn, xy] + bufs:
             ctx.free(b)
     ctx.close()
@@ -146,7 +150,7 @@ def part_kernel(a, out):
 
 def part_loop(a, out):
     import track_ids as ti
-    ti.use_tree(ROOT)
+    ti.use_tree(a.tree)
     for S in (1, 16):
         env = ti.setup(S)
         steps = 1500 if S == 1 else max(2 * (env["bench"].N_FRAMES - 1 - env["bench"].PASS_START), 1500 // 8)
@@ -169,7 +173,7 @@ def part_stream(a, out):
     from vo import _native, driver
     from vo.primitives import Sequence
     ctx = _native.Context(0)
-    kw = dict(n_keypoints=N_KP, klt_win=WIN, klt_max_level=MAX_LEVEL, hyp=4000, context=ctx, bootstrap_win=21, bootstrap_max_level=3,
+    kw = dict(n_keypoints=N_KP, klt_win=a.win[0], klt_max_level=MAX_LEVEL, hyp=4000, context=ctx, bootstrap_win=21, bootstrap_max_level=3,
               bootstrap_threshold=1.0)
     for name, fb in (("plain", None), ("fb", a.fb)):
         seq = Sequence("synthetic", n_frames=a.loop_frames, height=H, width=W_IMG, channels=1)
@@ -196,7 +200,13 @@ def main():
     ap.add_argument("--fb", type=float, default=1.0)
     ap.add_argument("--helper-dir", default=None, help="where the compiled helper is kept (default: a temporary directory)")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--win", default=str(WIN), help="tracker window; the kernel part takes a list (15,17,21,9)")
+    ap.add_argument("--tree", default=ROOT, help="the checkout to measure (default: the one this tool lies in)")
     a = ap.parse_args()
+    a.win = [int(w) for w in a.win.split(",")]
+    a.tree = os.path.abspath(a.tree)
+    import track_ids
+    track_ids.use_tree(a.tree)
 
     class Report(dict):
         def __setitem__(self, k, v):
