@@ -384,6 +384,48 @@ int vo_hamming_knn2_dev(vo_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* 
 int vo_match_hamming_ratio(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int row_bytes,
                            double ratio, int max_dist, int32_t* pairs, int32_t* n_pairs);
 
+/* ---- FAST-9 corners (fast.hip) ------------------------------------------------------------
+ * The project's own definition, in the spirit of Rosten's FAST-9/16 segment test (the reference has no such detector, and
+ * nothing is compared against OpenCV's).  Everything is integer arithmetic, so the kernels equal tests/fast_reference.py
+ * bit for bit on every input, with no margins.
+ *   circle   radius 3, sixteen offsets (dx, dy) clockwise from the top, c_0 .. c_15:
+ *            (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3)
+ *   score    for p = (x, y) with 3 <= x < W - 3 and 3 <= y < H - 3, I the centre byte, all arithmetic int32:
+ *              s(p) = max over k = 0..15 of max( min_{j=0..8} (c_{(k+j) mod 16} - I), min_{j=0..8} (I - c_{(k+j) mod 16}) )
+ *            -- nine contiguous circle pixels, the wrap included.  p is a corner iff s(p) > threshold, 0 <= threshold <=
+ *            254: exactly "nine contiguous pixels all brighter than I + threshold, or all darker than I - threshold",
+ *            strict.  The score map is H x W uint8: s(p) for a corner (1 .. 255), 0 otherwise and on the border of 3.  An
+ *            image with H < 7 or W < 7 has an all-zero map and no corners: a result, not an error.
+ *   nonmax   (nonmax = 1) with index = y W + x, a corner survives iff none of its eight neighbours is a corner that beats
+ *            it: one of higher score, or of the same score and lower index.  A local maximum under a total order, decided
+ *            from the map alone and not a greedy walk: of a plateau a a a in one row only the first survives, although
+ *            the second, which suppresses the third, is itself suppressed.  Two survivors are never adjacent, so they
+ *            number at most ceil((H-6)/2) ceil((W-6)/2).  nonmax = 0: every corner survives.
+ *   cut      n = min(N, survivors), 1 <= N <= 16384; the n survivors first in the order (score descending, index
+ *            ascending).  kp_xy: n rows of float64 (x, y), integer-valued -- the layout vo_harris_keypoints writes and
+ *            vo_brief_describe_dev reads; kp_score (nullable): their n scores; total (nullable): the survivors before the
+ *            cut.  Rows at and beyond n are not written.
+ * vo_fast_score: the map, host arrays.  vo_fast_keypoints: one image, host arrays; vo_fast_keypoints_batch: S images of
+ * one size, kp_xy S blocks of N rows, kp_score (nullable) S blocks of N bytes, n S counts.  All three upload, run the
+ * stages of the _dev form (S = 1 for one image) and download.
+ * vo_fast_keypoints_batch_dev: device pointers; enqueues a fixed launch sequence on the context's stream and neither
+ * synchronises nor reads anything back.  Image q at d_imgs + q * img_stride, its rows at d_kp_xy + q * xy_stride * 2
+ * (xy_stride rows, at least N), its scores at d_kp_score + q * xy_stride (nullable), its count in d_n[q], its survivors
+ * before the cut in d_total[q] (nullable).  The workspace (two H x W byte maps, two words per image row, N indices and scores
+ * and a control block per image) belongs to the context and grows with the largest call; no list of survivors is kept,
+ * so there is no capacity to exceed.
+ * VO_EINVAL, with the context usable afterwards and nothing written: a null pointer (but the nullable ones), H or W < 1,
+ * H W >= 2^31, threshold outside 0 .. 254, nonmax other than 0 or 1, N outside 1 .. 16384, S outside 1 .. 65535,
+ * img_stride < H W, xy_stride < N.                                                                                   */
+int vo_fast_score(vo_ctx* ctx, const uint8_t* img, int H, int W, int threshold, uint8_t* score);
+int vo_fast_keypoints(vo_ctx* ctx, const uint8_t* img, int H, int W, int threshold, int nonmax, int N, double* kp_xy,
+                      uint8_t* kp_score /* nullable */, int32_t* n);
+int vo_fast_keypoints_batch(vo_ctx* ctx, const uint8_t* imgs, int S, int H, int W, int threshold, int nonmax, int N,
+                            double* kp_xy /* S N 2 */, uint8_t* kp_score /* S N, nullable */, int32_t* n /* S */);
+int vo_fast_keypoints_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, int threshold,
+                                int nonmax, int N, double* d_kp_xy, size_t xy_stride /* rows, >= N */,
+                                uint8_t* d_kp_score /* nullable */, int32_t* d_n, int32_t* d_total /* nullable */);
+
 /* ---- Shi-Tomasi corners -----------------------------------------------------------
  * [ref: src/vo/features/klt.py:98]  cv2.goodFeaturesToTrack(img, mask, maxCorners,
  * qualityLevel, minDistance, blockSize).  xy: vo_good_features_capacity(H, W, max_corners)

@@ -232,6 +232,10 @@ _SIGS = {
     "vo_match_hamming_knn2": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "vo_hamming_knn2_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "vo_match_hamming_ratio": (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _vp, _vp]),
+    "vo_fast_score": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "vo_fast_keypoints": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vo_fast_keypoints_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vo_fast_keypoints_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "vo_good_features": (_i, [_vp, _vp, _i, _i, _vp, _i, _d, _d, _i, _vp, _vp]),
     "vo_min_eigen_map": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "vo_good_features_capacity": (_i, [_i, _i, _i]),
@@ -617,6 +621,55 @@ class Context:
         self._chk(self._lib.vo_match_hamming_ratio(self._h, _ptr(q), q.shape[0], _ptr(t), t.shape[0], q.shape[1],
                                                    float(ratio), int(max_dist), _ptr(pairs), C.byref(n)))
         return pairs[: n.value].astype(np.int64)
+
+    # ---- FAST-9 corners (csrc/fast.hip) ----
+    def fast_score(self, img, threshold=20):
+        """The (H, W) uint8 FAST-9 score map (vo_fast_score): s(p) where p is a corner, 0 elsewhere."""
+        img = _c(img, np.uint8)
+        assert img.ndim == 2
+        H, W = img.shape
+        out = np.empty((H, W), np.uint8)
+        self._chk(self._lib.vo_fast_score(self._h, _ptr(img), H, W, int(threshold), _ptr(out)))
+        return out
+
+    def fast_keypoints(self, img, threshold=20, num_keypoints=1000, nonmax=True, want_scores=False):
+        """(n, 2) float64 (x, y) of the n = min(num_keypoints, survivors) strongest FAST-9 corners in the order (score
+        descending, index ascending) (vo_fast_keypoints); with want_scores also their (n,) uint8 scores."""
+        img = _c(img, np.uint8)
+        assert img.ndim == 2
+        H, W = img.shape
+        kp = np.empty((int(num_keypoints), 2), np.float64)
+        sc = np.empty((int(num_keypoints),), np.uint8) if want_scores else None
+        n = C.c_int32(0)
+        self._chk(self._lib.vo_fast_keypoints(self._h, _ptr(img), H, W, int(threshold), 1 if nonmax else 0,
+                                              int(num_keypoints), _ptr(kp), _ptr(sc), C.byref(n)))
+        return (kp[: n.value].copy(), sc[: n.value].copy()) if want_scores else kp[: n.value].copy()
+
+    def fast_keypoints_batch(self, imgs, threshold=20, num_keypoints=1000, nonmax=True, want_scores=False):
+        """FAST-9 corners of S images of one size in one set of launches (vo_fast_keypoints_batch): `imgs` is an (S, H, W)
+        uint8 array or a list of equal-shape 2-D arrays.  Returns a list of S items, each what fast_keypoints(image, ...)
+        returns."""
+        imgs, _ = self._image_stack("fast_keypoints_batch", imgs)
+        S, H, W = imgs.shape
+        N = int(num_keypoints)
+        kp = np.empty((S, max(N, 0), 2), np.float64)
+        sc = np.empty((S, max(N, 0)), np.uint8) if want_scores else None
+        n = np.zeros(S, np.int32)
+        self._chk(self._lib.vo_fast_keypoints_batch(self._h, _ptr(imgs), S, H, W, int(threshold), 1 if nonmax else 0, N,
+                                                    _ptr(kp), _ptr(sc), _ptr(n)))
+        if want_scores:
+            return [(kp[q, : n[q]].copy(), sc[q, : n[q]].copy()) for q in range(S)]
+        return [kp[q, : n[q]].copy() for q in range(S)]
+
+    def fast_keypoints_batch_dev(self, d_imgs, img_stride, S, H, W, d_kp_xy, xy_stride, d_n, threshold=20, num_keypoints=1000,
+                                 nonmax=True, d_kp_score=None, d_total=None):
+        """vo_fast_keypoints_batch_dev on device pointers (alloc / to_device): enqueued on the context's stream, nothing
+        read back."""
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        self._chk(self._lib.vo_fast_keypoints_batch_dev(self._h, vp(d_imgs), int(img_stride), int(S), int(H), int(W),
+                                                        int(threshold), 1 if nonmax else 0, int(num_keypoints), vp(d_kp_xy),
+                                                        int(xy_stride), vp(d_kp_score), vp(d_n), vp(d_total)))
 
     def knn2_u8_batch_dev(self, d_q, q_stride, d_nq, nq_stride, cap_q, d_t, t_stride, d_nt, nt_stride, cap_t, S, row_bytes,
                           d_best, d_d2):

@@ -1,6 +1,7 @@
 """Tracker selection (reference: src/vo/features/tracker.py): the one entry point the
 driver calls per frame."""
 from vo.features.brief import BRIEFDetector
+from vo.features.fast import FASTBRIEFDetector
 from vo.features.harris import HarrisCornerDetector
 from vo.features.klt import KLTTracker
 from vo.features.sift import SIFTDetector
@@ -11,6 +12,7 @@ _TRACKERS = {
     "harris": (HarrisCornerDetector, "featureMatcher"),
     "sift": (SIFTDetector, "get_sift_matches"),
     "brief": (BRIEFDetector, "get_brief_matches"),     # not in the reference: corners + BRIEF-256 + Hamming matching
+    "fast": (FASTBRIEFDetector, "get_brief_matches"),  # ... with FAST-9 corners in front
 }
 
 
