@@ -434,7 +434,40 @@ int vo_fast_keypoints_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_s
  * eigenvalue map, thresholded 3x3 maxima, descending order (value, then address) and the
  * greedy minimum-distance rule over OpenCV's cell grid, as parallel rounds over all
  * candidates (one launch per round) or, where those cannot take the image, as one
- * workgroup's walk: the stages of vo_good_features_batch_dev below for one image.         */
+ * workgroup's walk: the stages of vo_good_features_batch_dev below for one image.
+ *
+ * The rule in full (tests/good_features_reference.py states it in exact integers and float64;
+ * oracle/csrc/goodfeatures.c and the kernels are held to it):
+ *   gradients  gx = [-1 0 1; -2 0 2; -1 0 1] and gy = its transpose, as a correlation on the
+ *              uint8 image, border reflect-101 (.. 2 1 | 0 1 2 ..); integers, |g| <= 1020.
+ *   sums       Sxx, Sxy, Syy = sums of gx gx, gx gy, gy gy over the block x block box at offsets
+ *              -(block/2) .. block - 1 - block/2 in x and in y (an even box reaches one pixel
+ *              further up and left than down and right); outside the image the product images
+ *              are reflected, reflect-101, as often as it takes (a box wider than the image
+ *              passes both edges repeatedly; a side of 1 has one pixel).  Exact integers,
+ *              block in 1..31.  (OpenCV sums the scaled products in float32 in its own order:
+ *              the one documented difference.)
+ *   scale      s = 1 / (4 * block * 255); s2 = (float)(s * s), the product made in double.
+ *   value      float32, every operation rounded once, no contraction:
+ *                a = (float)Sxx * s2 * 0.5f;  b = (float)Sxy * s2;  c = (float)Syy * s2 * 0.5f;
+ *                eig = (a + c) - sqrtf((a - c) * (a - c) + b * b)
+ *              the smaller eigenvalue of s^2 [Sxx Sxy; Sxy Syy], within 10 * 2^-24 * (a + c) of
+ *              it (first order; the error goes with the trace, not with the eigenvalue), and
+ *              exactly 0 where the sums are 0.  It may be negative by that much on an edge.
+ *   threshold  m = the largest eig over the pixels with mask != 0 (all of them without a mask,
+ *              border pixels included); thr = (float)((double)m * quality).  No allowed pixel:
+ *              no corner.  quality > 0.
+ *   keep       a pixel is a candidate when all five hold: eig > thr; eig != 0; mask != 0 there;
+ *              it lies in rows 1..H-2 and columns 1..W-2; eig equals the largest value of its
+ *              3x3 neighbourhood after values <= thr are replaced by 0 (forbidden and border
+ *              neighbours count; tied neighbours are all kept).
+ *   order      eig descending; equal values: the higher address y * W + x first.
+ *   distance   in that order a candidate is accepted unless an already accepted corner has
+ *              dx*dx + dy*dy < min_dist * min_dist (double; a corner exactly min_dist away is
+ *              kept).  The test is made only when min_dist >= 1: below that (0 included) every
+ *              candidate is accepted.
+ *   limit      the first max_corners accepted corners; max_corners <= 0: all of them.
+ *   output     (x, y) as float32 whole numbers, in the order of acceptance.                 */
 int vo_good_features(vo_ctx* ctx, const uint8_t* img, int H, int W, const uint8_t* mask,
                      int max_corners, double quality, double min_dist, int block, float* xy,
                      int32_t* n);

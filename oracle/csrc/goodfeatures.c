@@ -5,8 +5,17 @@
  * Reference call site: src/vo/features/klt.py:98
  *     cv2.goodFeaturesToTrack(img, mask=mask, maxCorners=500, qualityLevel=0.01,
  *                             minDistance=8, blockSize=7)                 (klt.py:24-26)
- * PARITY UNPINNED against OpenCV (opencv-python==4.8.1.78 is absent; the reference has no
- * test for it).  Restated algorithm (cornerMinEigenVal + goodFeaturesToTrack):
+ * PINNED to the definition of tests/good_features_reference.py (cornerMinEigenVal +
+ * goodFeaturesToTrack in exact integers and float64, independent of this file) by
+ * tests/test_good_features_reference_host.py: the map within 10 * 2^-24 * (a + c) of the
+ * smaller eigenvalue at every pixel and bit-equal to the float32 formula below on the
+ * definition's sums; the corners equal to the brute-force rule on this file's own map over
+ * shapes x blocks x parameters x masks, and to the rule on the definition's float64 map
+ * wherever every decision survives the bound (ties by address included); include/vo_hip.h
+ * states the rule in full, DESIGN.md section 2 the bound, the cases and the mutations tried.
+ * STILL OPEN: bit parity with OpenCV itself (opencv-python==4.8.1.78 is absent; the reference
+ * has no test for it) -- OpenCV's float32 summation order, the difference named at the end.
+ * Restated algorithm:
  *   Dx, Dy   3x3 Sobel (correlation), reflect-101 border, scaled by 1 / (4 * blockSize * 255)
  *   cov      blockSize x blockSize box sums of Dx^2, DxDy, Dy^2 (anchor at the centre,
  *            reflect-101 border)
