@@ -383,6 +383,30 @@ int vo_hamming_knn2_dev(vo_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* 
                         int32_t* d_best, int32_t* d_dist);
 int vo_match_hamming_ratio(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int row_bytes,
                            double ratio, int max_dist, int32_t* pairs, int32_t* n_pairs);
+/* The batch forms the frame pipeline's FAST + BRIEF tracker mode is made of: device pointers only, every count in device
+ * memory, enqueued on the context's stream; neither synchronises nor reads anything back.  The one-image entry points
+ * above launch the same kernels with S = 1.
+ * vo_brief_describe_batch_dev: image q at d_imgs + q * img_stride, its keypoints at d_kp_xy + q * xy_stride * 2 (the
+ * layout vo_fast_keypoints_batch_dev writes), its count in d_n[q]; rows 0 .. min(max(d_n[q], 0), N) - 1 are described into
+ * d_desc + q * desc_stride (bytes), their bins into d_bin + q * xy_stride (nullable).  Rows at and beyond the count are
+ * not written.  VO_EINVAL: a null pointer, S outside 1 .. 65535, N outside 1 .. 16384, img_stride < H W, xy_stride < N,
+ * desc_stride < 32 N.
+ * vo_match_hamming_batch_dev: vo_match_hamming_ratio's rule for S sequences, arguments as the pipeline's other matcher
+ * takes them: sequence z's queries at d_q + z * q_stride (bytes), their number at d_nq[z * nq_stride] (ints; it may be a
+ * field of an array of structures), train rows and count likewise; a count is clamped to 0 .. cap.  Its pairs go to
+ * d_pairs + z * cap_q * 2 (query, train; query order), their number to d_npairs[z]; rows of d_pairs at and beyond that
+ * number are not written, rows of d_q / d_t at and beyond a count never read.  The workspace (2-NN lists and one owner
+ * table per sequence) belongs to the context and grows with the largest call.  VO_EINVAL: a null pointer, row_bytes
+ * not a multiple of 4 in 4 .. 64, rows or strides off a 4-byte boundary, a capacity < 1, S outside 1 .. 65535, S > 1
+ * with blocks that overlap or a count stride of 0, ratio NaN.                                                       */
+int vo_brief_describe_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W,
+                                const double* d_kp_xy, size_t xy_stride /* rows */, const int32_t* d_n /* S counts */,
+                                int N /* rows launched per image */, int oriented, uint8_t* d_desc,
+                                size_t desc_stride /* bytes */, uint8_t* d_bin /* nullable */);
+int vo_match_hamming_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride /* ints */,
+                               int cap_q, const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride, int cap_t,
+                               int S, int row_bytes, double ratio, int max_dist, int32_t* d_pairs /* S x cap_q x 2 */,
+                               int32_t* d_npairs /* S */);
 
 /* ---- FAST-9 corners (fast.hip) ------------------------------------------------------------
  * The project's own definition, in the spirit of Rosten's FAST-9/16 segment test (the reference has no such detector, and
@@ -728,7 +752,7 @@ typedef struct vo_pipeline_config {
                                     are independent, so they batch).  0 = 1.  Every sequence has its own frame
                                     store, Features, State, RANSAC object and generator; the plain entry points
                                     address sequence 0, the _seq forms any of them.  KLT and Harris tracker
-                                    modes: any S; SIFT tracker mode: one.                                */
+                                    modes: any S; SIFT tracker mode: one.  The FAST tracker mode: any S. */
   int32_t tracker_mode;          /* 0: KLT tracker with the Harris detector (everything above); 1: SIFT
                                     [ref: src/vo/features/tracker.py:60-61, src/vo/features/sift.py:23-56] -- per frame
                                     detect + describe (every keypoint with sift_cap = -1, as the reference keeps; else
@@ -745,7 +769,17 @@ typedef struct vo_pipeline_config {
                                     uniqueness on the matrix cores (361 values padded to 384), then as mode 1.  Any
                                     number of sequences: patches, matcher, regroup and descriptor gather take all of
                                     them in one launch each; lanes (vo_pipeline_set_active_seq / _restart_seq) are KLT
-                                    mode only.  debug_fault_every > 0 forces the fault at the pair regroup.          */
+                                    mode only.  debug_fault_every > 0 forces the fault at the pair regroup.
+                                    3: FAST + BRIEF (the project's own ORB-style front end, vo/features/fast.py) -- per
+                                    frame the up to n_keypoints strongest FAST-9 corners (non-maximum suppression on;
+                                    however many the frame has: the count stays on the device) and their BRIEF-256
+                                    descriptors (32-byte rows) on the detection stream, a Hamming 2-NN with the ratio
+                                    (0.8) / distance (64) / first-come rule on the main stream, then as mode 2: any
+                                    number of sequences, every stage one launch for all of them, the same refusals
+                                    (detector = 1, lanes, bootstrap, the tracker's forward-backward check, the
+                                    structure loop), debug_fault_every > 0 at the pair regroup.  Descriptor rows
+                                    handed over or read back carry 32 values.
+                                    Threshold, orientation and distance limit: vo_pipeline_set_fast_brief.           */
   int32_t sift_cap;              /* keypoints kept per frame in SIFT mode: 1..4000 (<= feature_cap) the strongest;
                                     0 = n_keypoints; -1 = every keypoint [ref: src/vo/features/sift.py:10, nfeatures = 0]
                                     up to feature_cap -- a frame with more, or whose SIFT lists overflow, fails its step
@@ -755,7 +789,8 @@ typedef struct vo_pipeline_config {
                                     is allocated and the regroup kernels are the ones without a word of it.  (The field
                                     takes the four bytes that were padding in front of match_ratio: every other field
                                     keeps its offset and the structure its size.)                                     */
-  double match_ratio;            /* 0 = the reference's: 0.8 in SIFT mode (sift.py:49), 0.85 in Harris mode (harris.py:255) */
+  double match_ratio;            /* 0 = the reference's: 0.8 in SIFT mode (sift.py:49), 0.85 in Harris mode (harris.py:255);
+                                    0.8 in FAST mode                                                                  */
   int32_t detector;              /* tracker_mode 0: what refills the feature set when fewer than redetect_fraction of the
                                     tracks are left.  0: Harris response + greedy NMS, exactly n_keypoints keypoints
                                     (harris_patch, harris_kappa, nms_radius above).  1: Shi-Tomasi corners, the reference's
@@ -961,6 +996,14 @@ int vo_pipeline_prepare(vo_pipeline* p, int idx);
  * bootstrap (vo_pipeline_bootstrap_seq) keeps its plain tracker.  _get_ reads the value back (0: off).                    */
 int vo_pipeline_set_klt_fb(vo_pipeline* p, double fb_max);
 int vo_pipeline_get_klt_fb(vo_pipeline* p, double* fb_max);
+/* The settings of the FAST + BRIEF tracker mode (tracker_mode = 3), FASTBRIEFDetector's defaults at creation (20, not
+ * oriented, 64; match_ratio = 0 means 0.8 in this mode).  fast_threshold: 0 = 20, valid 0 .. 254; brief_oriented: 0 or 1;
+ * brief_max_distance: the largest Hamming distance a pair may have, 0 = 64, < 0 = no limit, at most 256.  A value out of
+ * range is refused with a message naming it, as is a pipeline in another mode or with a step in flight; the settings hold
+ * from the next submitted step on.  vo_pipeline_config is not involved: its layout is the one it was.  _get_ reads the
+ * values in force back.                                                                                               */
+int vo_pipeline_set_fast_brief(vo_pipeline* p, int fast_threshold, int brief_oriented, int brief_max_distance);
+int vo_pipeline_get_fast_brief(vo_pipeline* p, int32_t* fast_threshold, int32_t* brief_oriented, int32_t* brief_max_distance);
 int vo_host_alloc(vo_ctx* ctx, size_t bytes, void** out);
 int vo_host_free(vo_ctx* ctx, void* p);          /* ctx may be NULL */
 /* ---- frame ingest: three-channel frames and lens undistortion on the device ------------------------------------

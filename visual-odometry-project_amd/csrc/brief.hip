@@ -48,11 +48,25 @@ __device__ __forceinline__ unsigned box_sum(const uint8_t* win, int ox, int oy) 
 // path: a centre whose window misses the image reads zeros, gives box sums of 0, no bit set and bin 0 -- which is what
 // the definition asks for outside [-16, W + 16) x [-16, H + 16).  A centre the range test refuses (and a wave past N) is
 // moved to (-64, -64), where the window lies outside every image; that keeps every wave on one path to the barrier.
-__global__ __launch_bounds__(BR_T) void brief_describe_kernel(const uint8_t* __restrict__ img, int H, int W,
-                                                              const double* __restrict__ kp_xy, int N, int oriented,
-                                                              uint8_t* __restrict__ desc, uint8_t* __restrict__ bin) {
+// blockIdx.y = image: its bytes at img + y * img_stride, its keypoints at kp_xy + y * xy_stride * 2, its descriptors at
+// desc + y * desc_stride (bytes), its bins at bin + y * xy_stride.  d_n (nullable): the images' row counts, in device
+// memory -- image y describes rows 0 .. min(max(d_n[y], 0), N) - 1, and a workgroup whose four rows all lie beyond that
+// leaves before it loads anything (the whole workgroup takes the branch: nobody is left at the barrier).
+__global__ __launch_bounds__(BR_T) void brief_describe_kernel(const uint8_t* __restrict__ img, size_t img_stride, int H, int W,
+                                                              const double* __restrict__ kp_xy, size_t xy_stride,
+                                                              const int* __restrict__ d_n, int N, int oriented,
+                                                              uint8_t* __restrict__ desc, size_t desc_stride,
+                                                              uint8_t* __restrict__ bin) {
   __shared__ __attribute__((aligned(16))) uint8_t s_win[BR_WAVES][BR_WIN * BR_ROW];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (d_n) N = min(max(d_n[blockIdx.y], 0), N);
+  if ((int)(blockIdx.x * BR_WAVES) >= N) return;
+  if (blockIdx.y) {
+    img += blockIdx.y * img_stride;
+    kp_xy += blockIdx.y * xy_stride * 2;
+    desc += blockIdx.y * desc_stride;
+    if (bin) bin += blockIdx.y * xy_stride;
+  }
   const int n = blockIdx.x * BR_WAVES + wv;
   int cx = -4 * BR_REACH, cy = -4 * BR_REACH;
   if (n < N) {
@@ -147,12 +161,32 @@ __device__ __forceinline__ void key_insert(unsigned long long& k0, unsigned long
 
 // WP: words of a row held in registers, 8 for rows up to 32 bytes, 16 above; the words past the row's own are zero.
 // VEC: rows are exactly WP words and start on 16-byte boundaries, so a row is WP / 4 loads of four words.
+// The sequences of a batch: where they lie and where their counts are (all strides 0 and no counts: one set, nq x nt)
+struct hamming_batch {
+  const int *d_nq = nullptr, *d_nt = nullptr;     // sequence z: d_nq[z * nq_stride] queries of the nq launched, likewise nt
+  int nq_stride = 0, nt_stride = 0;
+  size_t q_stride = 0, t_stride = 0;              // words between two sequences' first rows
+};
+
+// blockIdx.y = sequence: its lists at best / dist + y * 2 * nq.  A count is clamped to 0 .. the launched size; rows at and
+// beyond it are neither read nor written, and a workgroup whose eight queries all lie beyond it leaves at once.
 template <int WP, bool VEC>
 __global__ __launch_bounds__(HM_T) void hamming_knn2_kernel(const unsigned* __restrict__ q, int nq, const unsigned* __restrict__ t,
-                                                            int nt, int words, int* __restrict__ best, int* __restrict__ dist) {
+                                                            int nt, int words, int* __restrict__ best, int* __restrict__ dist,
+                                                            const hamming_batch hb) {
   __shared__ unsigned long long s_k[HM_Q][HM_T / 64][2];
   const int tid = threadIdx.x, qi = tid & (HM_Q - 1), sl = tid / HM_Q;
   const int q0 = blockIdx.x * HM_Q;
+  {
+    const size_t z = blockIdx.y;
+    best += z * 2 * (size_t)nq;
+    dist += z * 2 * (size_t)nq;
+    q += z * hb.q_stride;
+    t += z * hb.t_stride;
+    if (hb.d_nq) nq = min(max(hb.d_nq[z * hb.nq_stride], 0), nq);
+    if (hb.d_nt) nt = min(max(hb.d_nt[z * hb.nt_stride], 0), nt);
+  }
+  if (q0 >= nq) return;
   auto load_row = [&](const unsigned* __restrict__ base, size_t row, unsigned (&out)[WP]) {
     if constexpr (VEC) {
       const uint4* p = reinterpret_cast<const uint4*>(base + row * WP);
@@ -208,27 +242,45 @@ __global__ __launch_bounds__(HM_T) void hamming_knn2_kernel(const unsigned* __re
 }
 
 // The pair list.  Query i passes when both neighbours exist, float64(d1) < ratio * float64(d2) (one IEEE multiply, strict)
-// and d1 <= max_dist (max_dist >= 0).  A train row goes to the lowest query that passes with it (atomicMin), and the
-// pairs come out in query order through an ordered compaction, 1024 queries per round.  One workgroup.  match.hip's
+// and d1 <= max_dist (max_dist >= 0).  A train row goes to the lowest query that passes with it (atomicMin, its returned
+// value unused), and the pairs come out in query order through an ordered compaction, 1024 queries per round.  One
+// workgroup per sequence (blockIdx.x): lists at best / dist + x * 2 * nq, owner table at owner + x * nt, pairs at
+// pairs + x * 2 * nq, count in n_pairs[x]; the counts as in hamming_knn2_kernel.  The workgroup presets its own owner
+// entries (above every query) before it contests them, so no launch in front of it has to.  match.hip's
 // ratio_unique_kernel is the same rule on float32 square roots of float64 distances; integer distances and the
 // distance limit need their own test, so the pass is written here.
 constexpr int HR_T = 1024;
 __global__ __launch_bounds__(HR_T) void hamming_ratio_unique_kernel(const int* __restrict__ best, const int* __restrict__ dist,
-                                                                   int nq, double ratio, int max_dist,
-                                                                   int* __restrict__ owner /* nt, preset above every query */,
-                                                                   int* __restrict__ pairs, int* __restrict__ n_pairs) {
+                                                                   int nq, int nt, double ratio, int max_dist,
+                                                                   int* __restrict__ owner, int* __restrict__ pairs,
+                                                                   int* __restrict__ n_pairs, const hamming_batch hb) {
   __shared__ int s_scan[HR_T];
   __shared__ int s_base;
   const int tid = threadIdx.x;
+  {
+    const size_t z = blockIdx.x;
+    best += z * 2 * (size_t)nq;
+    dist += z * 2 * (size_t)nq;
+    pairs += z * 2 * (size_t)nq;
+    owner += z * (size_t)nt;
+    n_pairs += z;
+    if (hb.d_nq) nq = min(max(hb.d_nq[z * hb.nq_stride], 0), nq);
+    if (hb.d_nt) nt = min(max(hb.d_nt[z * hb.nt_stride], 0), nt);
+  }
+  if (nt < 2) nq = 0;                                     // (a pair needs both neighbours; the lists may not have been written)
   auto passes = [&](int i) -> bool {
     const int b0 = best[2 * (size_t)i], b1 = best[2 * (size_t)i + 1];
     if (b0 < 0 || b1 < 0) return false;
     const int d1 = dist[2 * (size_t)i], d2 = dist[2 * (size_t)i + 1];
     return (double)d1 < ratio * (double)d2 && (max_dist < 0 || d1 <= max_dist);
   };
+  if (nq > 0)
+    for (int j = tid; j < nt; j += HR_T) __hip_atomic_store(&owner[j], INT_MAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) s_base = 0;
+  __threadfence();
+  __syncthreads();
   for (int i = tid; i < nq; i += HR_T)
     if (passes(i)) atomicMin(&owner[best[2 * (size_t)i]], i);
-  if (tid == 0) s_base = 0;
   __threadfence();
   __syncthreads();
   for (int base = 0; base < nq; base += HR_T) {
@@ -274,6 +326,28 @@ int hamming_check(vo_ctx* ctx, const char* who, int nq, int nt, int row_bytes) {
   return VO_OK;
 }
 
+// the 2-NN lists of S sequences (hb: where they lie; S = 1 with an empty hb: one set of nq x nt rows)
+int knn2_launch(vo_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int S, int row_bytes, int32_t* d_best,
+                int32_t* d_dist, const hamming_batch& hb) {
+  const int words = row_bytes / 4;
+  // whole rows of 32 or 64 bytes on 16-byte boundaries are read four words at a time; every other shape word by word
+  const bool vec = (words == 8 || words == 16) && (((uintptr_t)d_q | (uintptr_t)d_t) & 15) == 0 && ((hb.q_stride | hb.t_stride) & 3) == 0;
+  const dim3 grid(vo_cdiv(nq, HM_Q), S), block(HM_T);
+  const unsigned *uq = (const unsigned*)d_q, *ut = (const unsigned*)d_t;
+  {
+    vo_prof_scope ps(ctx, VO_K_HAMMING_KNN2);
+    if (vec && words == 8)
+      hipLaunchKernelGGL((hamming_knn2_kernel<8, true>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist, hb);
+    else if (vec)
+      hipLaunchKernelGGL((hamming_knn2_kernel<16, true>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist, hb);
+    else if (words <= 8)
+      hipLaunchKernelGGL((hamming_knn2_kernel<8, false>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist, hb);
+    else
+      hipLaunchKernelGGL((hamming_knn2_kernel<16, false>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist, hb);
+  }
+  return vo_check_launch(ctx, "hamming_knn2_kernel");
+}
+
 // the rows go up to scratch[0] / scratch[1], the lists are left in scratch[2] (best) and scratch[3] (dist); nq, nt >= 1
 int hamming_host(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int row_bytes) {
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -298,6 +372,28 @@ int vo_brief_pattern(int8_t* out) {
   return VO_OK;
 }
 
+int vo_brief_describe_batch_dev(vo_ctx* ctx, const uint8_t* d_imgs, size_t img_stride, int S, int H, int W, const double* d_kp_xy,
+                                size_t xy_stride, const int32_t* d_n, int N, int oriented, uint8_t* d_desc, size_t desc_stride,
+                                uint8_t* d_bin) {
+  if (!ctx) return VO_EINVAL;
+  VO_TRY(describe_check(ctx, d_imgs, H, W, d_kp_xy, N, oriented, d_desc));
+  VO_REQUIRE(ctx, d_n, "brief_describe_batch_dev: null pointer");
+  VO_REQUIRE(ctx, S >= 1 && S <= 65535, "brief_describe_batch_dev: S = %d, must be 1 .. 65535", S);
+  VO_REQUIRE(ctx, img_stride >= (size_t)H * W, "brief_describe_batch_dev: img_stride %zu is below H * W = %zu", img_stride,
+             (size_t)H * W);
+  VO_REQUIRE(ctx, xy_stride >= (size_t)N, "brief_describe_batch_dev: xy_stride %zu is below N = %d", xy_stride, N);
+  VO_REQUIRE(ctx, desc_stride >= (size_t)N * 32, "brief_describe_batch_dev: desc_stride %zu is below 32 N = %zu", desc_stride,
+             (size_t)N * 32);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  {
+    vo_prof_scope ps(ctx, VO_K_BRIEF_DESCRIBE);
+    hipLaunchKernelGGL(brief_describe_kernel, dim3(vo_cdiv(N, BR_WAVES), S), dim3(BR_T), 0, ctx->stream, d_imgs, img_stride, H, W,
+                       d_kp_xy, xy_stride, (const int*)d_n, N, oriented, d_desc, desc_stride, d_bin);
+  }
+  return vo_check_launch(ctx, "brief_describe_kernel");
+}
+
+// (the batch kernel with one image and every row: no count is read)
 int vo_brief_describe_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const double* d_kp_xy, int N, int oriented,
                           uint8_t* d_desc, uint8_t* d_bin) {
   if (!ctx) return VO_EINVAL;
@@ -305,8 +401,8 @@ int vo_brief_describe_dev(vo_ctx* ctx, const uint8_t* d_img, int H, int W, const
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   {
     vo_prof_scope ps(ctx, VO_K_BRIEF_DESCRIBE);
-    hipLaunchKernelGGL(brief_describe_kernel, dim3(vo_cdiv(N, BR_WAVES)), dim3(BR_T), 0, ctx->stream, d_img, H, W, d_kp_xy, N,
-                       oriented, d_desc, d_bin);
+    hipLaunchKernelGGL(brief_describe_kernel, dim3(vo_cdiv(N, BR_WAVES)), dim3(BR_T), 0, ctx->stream, d_img, (size_t)0, H, W,
+                       d_kp_xy, (size_t)0, (const int*)nullptr, N, oriented, d_desc, (size_t)0, d_bin);
   }
   return vo_check_launch(ctx, "brief_describe_kernel");
 }
@@ -339,23 +435,42 @@ int vo_hamming_knn2_dev(vo_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* 
   VO_REQUIRE(ctx, d_q && d_best && d_dist && (d_t || nt == 0), "hamming_knn2_dev: null pointer");
   VO_REQUIRE(ctx, ((uintptr_t)d_q & 3) == 0 && ((uintptr_t)d_t & 3) == 0, "hamming_knn2_dev: rows must start on a 4-byte boundary");
   VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int words = row_bytes / 4;
-  // whole rows of 32 or 64 bytes on 16-byte boundaries are read four words at a time; every other shape word by word
-  const bool vec = (words == 8 || words == 16) && (((uintptr_t)d_q | (uintptr_t)d_t) & 15) == 0;
-  const dim3 grid(vo_cdiv(nq, HM_Q)), block(HM_T);
-  const unsigned *uq = (const unsigned*)d_q, *ut = (const unsigned*)d_t;
-  {
-    vo_prof_scope ps(ctx, VO_K_HAMMING_KNN2);
-    if (vec && words == 8)
-      hipLaunchKernelGGL((hamming_knn2_kernel<8, true>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist);
-    else if (vec)
-      hipLaunchKernelGGL((hamming_knn2_kernel<16, true>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist);
-    else if (words <= 8)
-      hipLaunchKernelGGL((hamming_knn2_kernel<8, false>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist);
-    else
-      hipLaunchKernelGGL((hamming_knn2_kernel<16, false>), grid, block, 0, ctx->stream, uq, nq, ut, nt, words, (int*)d_best, (int*)d_dist);
-  }
-  return vo_check_launch(ctx, "hamming_knn2_kernel");
+  return knn2_launch(ctx, d_q, nq, d_t, nt, 1, row_bytes, d_best, d_dist, hamming_batch());
+}
+
+int vo_match_hamming_batch_dev(vo_ctx* ctx, const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, int nq_stride, int cap_q,
+                               const uint8_t* d_t, size_t t_stride, const int32_t* d_nt, int nt_stride, int cap_t, int S,
+                               int row_bytes, double ratio, int max_dist, int32_t* d_pairs, int32_t* d_npairs) {
+  if (!ctx) return VO_EINVAL;
+  const char* who = "match_hamming_batch_dev";
+  VO_REQUIRE(ctx, row_bytes_ok(row_bytes), "%s: row_bytes = %d, must be a multiple of 4 in 4 .. 64", who, row_bytes);
+  VO_REQUIRE(ctx, d_q && d_nq && d_t && d_nt && d_pairs && d_npairs, "%s: null pointer", who);
+  VO_REQUIRE(ctx, cap_q >= 1 && cap_t >= 1 && cap_q <= (1 << 24) && cap_t <= (1 << 24), "%s: bad capacities cap_q = %d, cap_t = %d",
+             who, cap_q, cap_t);
+  VO_REQUIRE(ctx, S >= 1 && S <= 65535, "%s: S = %d, must be 1 .. 65535", who, S);
+  VO_REQUIRE(ctx, ratio == ratio, "%s: ratio is not a number", who);
+  VO_REQUIRE(ctx, ((uintptr_t)d_q & 3) == 0 && ((uintptr_t)d_t & 3) == 0 && (q_stride & 3) == 0 && (t_stride & 3) == 0,
+             "%s: rows must start on a 4-byte boundary", who);
+  VO_REQUIRE(ctx, S == 1 || (q_stride >= (size_t)cap_q * row_bytes && t_stride >= (size_t)cap_t * row_bytes),
+             "%s: per-sequence blocks overlap", who);
+  VO_REQUIRE(ctx, S == 1 || (nq_stride != 0 && nt_stride != 0), "%s: the sequences share a count", who);
+  VO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  vo_buf* s = ctx->scratch;
+  const size_t Sz = (size_t)S;
+  VO_TRY(vo_ensure(ctx, s[10], Sz * cap_q * 8));          // best
+  VO_TRY(vo_ensure(ctx, s[11], Sz * cap_q * 8));          // dist
+  VO_TRY(vo_ensure(ctx, s[12], Sz * cap_t * 4));          // owner of every train row, per sequence
+  hamming_batch hb;
+  hb.d_nq = (const int*)d_nq;
+  hb.d_nt = (const int*)d_nt;
+  hb.nq_stride = nq_stride;
+  hb.nt_stride = nt_stride;
+  hb.q_stride = q_stride / 4;
+  hb.t_stride = t_stride / 4;
+  VO_TRY(knn2_launch(ctx, d_q, cap_q, d_t, cap_t, S, row_bytes, (int32_t*)s[10].p, (int32_t*)s[11].p, hb));
+  hipLaunchKernelGGL(hamming_ratio_unique_kernel, dim3(S), dim3(HR_T), 0, ctx->stream, (const int*)s[10].p, (const int*)s[11].p,
+                     cap_q, cap_t, ratio, max_dist, (int*)s[12].p, (int*)d_pairs, (int*)d_npairs, hb);
+  return vo_check_launch(ctx, "hamming_ratio_unique_kernel");
 }
 
 int vo_match_hamming_knn2(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int row_bytes, int32_t* best,
@@ -395,9 +510,8 @@ int vo_match_hamming_ratio(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t*
   VO_TRY(vo_ensure(ctx, s[8], (size_t)nq * 8 + 8));       // pairs, then their number
   int* d_pairs = (int*)s[8].p;
   int* d_n = d_pairs + (size_t)nq * 2;
-  VO_HIP_TRY(ctx, hipMemsetAsync(s[7].p, 0x7f, (size_t)nt * 4, st));      // 0x7f7f7f7f: above every query index
-  hipLaunchKernelGGL(hamming_ratio_unique_kernel, dim3(1), dim3(HR_T), 0, st, (const int*)s[2].p, (const int*)s[3].p, nq, ratio,
-                     max_dist, (int*)s[7].p, d_pairs, d_n);
+  hipLaunchKernelGGL(hamming_ratio_unique_kernel, dim3(1), dim3(HR_T), 0, st, (const int*)s[2].p, (const int*)s[3].p, nq, nt,
+                     ratio, max_dist, (int*)s[7].p, d_pairs, d_n, hamming_batch());
   VO_TRY(vo_check_launch(ctx, "hamming_ratio_unique_kernel"));
   int n = 0;
   VO_HIP_TRY(ctx, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, st));

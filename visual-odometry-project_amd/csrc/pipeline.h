@@ -142,9 +142,14 @@ struct vo_pipeline {
   // Both descriptor modes keep up to frame_rows keypoints per frame (Harris: n_keypoints; SIFT: cfg.sift_cap, or with
   // cfg.sift_cap = -1 (sift_all) every keypoint of the frame, frame_rows = feature_cap; a frame that has more, or whose
   // SIFT lists overflow, is a VO_FAULT_CAPACITY step -- d_sover says which and how many).
+  // FAST + BRIEF tracker mode (tracker_mode = 3; vo/features/fast.py's FASTBRIEFDetector): the frame's FAST-9 corners -- up
+  // to n_keypoints, however many the frame has: the count stays in d_frame_n -- and their BRIEF-256 descriptors (32-byte
+  // rows) on the detection stream, the Hamming 2-NN with the ratio / distance / first-come rule on the main stream; the
+  // regroup, the descriptor gather and everything behind them are the Harris mode's, for any number of sequences.
   int frame_rows = 0;
   bool sift_all = false;
-  int desc_row = 128;                // bytes per descriptor row: 128 (SIFT) or 384 (361 patch bytes, padded)
+  int desc_row = 128;                // bytes per descriptor row: 128 (SIFT), 384 (361 patch bytes, padded) or 32 (BRIEF-256)
+  int fast_threshold = 20, brief_oriented = 0, brief_max_distance = 64;   // vo_pipeline_set_fast_brief (FASTBRIEFDetector's defaults)
   float* d_skp = nullptr;            // [3][frame_rows * 6]   keypoint rows of the frame in slot s (SIFT: one sequence)
   int32_t* d_sover = nullptr;        // [3][2] sift_all: the frame in slot s -- its verdict (vo_sift_all_batch_dev's d_over),
                                      //        its keypoint count (-1: list overflow)

@@ -198,7 +198,8 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   VO_REQUIRE(ctx, cfg->K[0] != 0.0 && cfg->K[4] != 0.0, "pipeline: singular intrinsics");
   VO_REQUIRE(ctx, cfg->refine_iters >= 0 && cfg->refine_iters <= 100, "pipeline: refine_iters must be in 0..100");
   VO_REQUIRE(ctx, cfg->sequences >= 0 && cfg->sequences <= 256, "pipeline: sequences must be in 1..256");
-  VO_REQUIRE(ctx, cfg->tracker_mode >= 0 && cfg->tracker_mode <= 2, "pipeline: tracker_mode must be 0 (klt), 1 (sift) or 2 (harris)");
+  VO_REQUIRE(ctx, cfg->tracker_mode >= 0 && cfg->tracker_mode <= 3,
+             "pipeline: tracker_mode must be 0 (klt), 1 (sift), 2 (harris) or 3 (fast)");
   VO_REQUIRE(ctx, cfg->tracker_mode != 1 || cfg->sequences <= 1, "pipeline: the SIFT tracker mode runs one sequence per pipeline");
   VO_REQUIRE(ctx, cfg->tracker_mode != 1 || cfg->sift_cap >= -1,
              "pipeline: sift_cap must be -1 (every keypoint), 0 (n_keypoints) or 1..4000, got %d", cfg->sift_cap);
@@ -320,9 +321,9 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
   PA(dev_alloc(p, &p->d_newkp, (size_t)cap * 2));
   PA(dev_alloc(p, &p->d_pairs, (size_t)cap * 2 * (cfg->tracker_mode != 0 ? Sz : 1)));
   if (cfg->tracker_mode != 0) {
-    p->desc_row = cfg->tracker_mode == 2 ? 384 : 128;
+    p->desc_row = cfg->tracker_mode == 2 ? 384 : cfg->tracker_mode == 3 ? 32 : 128;
     p->sift_all = cfg->tracker_mode == 1 && cfg->sift_cap == -1;
-    p->frame_rows = cfg->tracker_mode == 2 ? cfg->n_keypoints
+    p->frame_rows = cfg->tracker_mode >= 2 ? cfg->n_keypoints
                   : p->sift_all          ? cap
                                          : (cfg->sift_cap > 0 ? cfg->sift_cap : cfg->n_keypoints);
     if (rc == VO_OK && !p->sift_all && (p->frame_rows > cap || p->frame_rows > 4000))
@@ -434,6 +435,27 @@ int vo_pipeline_create(vo_ctx* ctx, const vo_pipeline_config* cfg, vo_pipeline**
       if (rc != VO_OK) vo_set_error(ctx, rc, "pipeline: %s", vo_last_error(p->det));
     }
     if (rc == VO_OK && hipStreamSynchronize(p->det->stream) != hipSuccess) rc = vo_set_error(ctx, VO_EHIP, "pipeline: the detection stream failed");
+    if (rc != VO_OK) {
+      vo_pipeline_destroy(p);
+      return rc;
+    }
+  }
+  if (cfg->tracker_mode == 3) {
+    // The FAST workspace of the detection context and the matcher's lists and owner tables of the caller's, sized for all S
+    // sequences before the first step: one pass of the front on frame slot 0 (whatever it holds) and one of the matcher
+    // with every count at zero (no step allocates).  The counts the front left go back to zero.
+    rc = vo_fast_keypoints_batch_dev(p->det, p->img(0, 0), p->img_stride(), S, cfg->H, cfg->W, p->fast_threshold, 1, N, p->kp(0, 0),
+                                     p->det_stride() / 2, nullptr, p->frame_n(0, 0), nullptr);
+    if (rc != VO_OK) vo_set_error(ctx, rc, "pipeline: %s", vo_last_error(p->det));
+    if (rc == VO_OK && hipStreamSynchronize(p->det->stream) != hipSuccess) rc = vo_set_error(ctx, VO_EHIP, "pipeline: the detection stream failed");
+    if (rc == VO_OK && mset(ctx->stream, p->d_frame_n, 0, (4 * Sz + 4) * 4) != hipSuccess) rc = vo_set_error(ctx, VO_EHIP, "pipeline: hipMemset failed");
+    if (rc == VO_OK) {
+      rc = vo_match_hamming_batch_dev(ctx, p->fdesc(0, 0), (size_t)cap * p->desc_row, &p->d_ctl->n, (int)(sizeof(vo_seq_ctl) / 4), cap,
+                                      p->frame_desc(0, 0), (size_t)p->frame_rows * p->desc_row, p->frame_n(0, 0), 1, p->frame_rows, S,
+                                      p->desc_row, 0.8, 64, p->d_pairs, p->npairs(0));
+      if (rc != VO_OK) rc = vo_set_error(ctx, rc, "pipeline: the matcher's workspace: %s", std::string(vo_last_error(ctx)).c_str());
+    }
+    if (rc == VO_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = vo_set_error(ctx, VO_EHIP, "pipeline: the main stream failed");
     if (rc != VO_OK) {
       vo_pipeline_destroy(p);
       return rc;

@@ -219,7 +219,7 @@ int vo_pipeline_set_descriptors_seq(vo_pipeline* p, int seq, const float* desc, 
   VO_REQUIRE(ctx, seq >= 0 && seq < p->S, "pipeline_set_descriptors: bad sequence index");
   VO_REQUIRE(ctx, p->have_state && p->n_flight == 0, "pipeline_set_descriptors: hand the state over first (nothing in flight)");
   VO_REQUIRE(ctx, n >= 0 && n <= p->cap && (n == 0 || desc), "pipeline_set_descriptors: bad arguments");
-  const int D = p->cfg.tracker_mode == 2 ? 361 : 128;     // values per row handed in; rows are padded to desc_row bytes
+  const int D = p->cfg.tracker_mode == 2 ? 361 : p->cfg.tracker_mode == 3 ? 32 : 128;     // values per row handed in; rows are padded to desc_row bytes
   std::vector<uint8_t> b((size_t)n * p->desc_row, 0);
   for (int i = 0; i < n; ++i)
     for (int k = 0; k < D; ++k) {
@@ -246,7 +246,7 @@ int vo_pipeline_get_descriptors_seq(vo_pipeline* p, int seq, float* desc, int32_
   n = std::max(0, std::min(n, p->cap));
   if (n_out) *n_out = n;
   if (!desc || n == 0) return VO_OK;
-  const int D = p->cfg.tracker_mode == 2 ? 361 : 128;
+  const int D = p->cfg.tracker_mode == 2 ? 361 : p->cfg.tracker_mode == 3 ? 32 : 128;
   std::vector<uint8_t> b((size_t)n * p->desc_row);
   VO_HIP_TRY(ctx, mcpy(st, b.data(), p->fdesc(p->cur, seq), b.size(), hipMemcpyDeviceToHost));
   for (int i = 0; i < n; ++i)
@@ -338,6 +338,36 @@ int vo_pipeline_get_klt_fb(vo_pipeline* p, double* fb_max) {
   if (!p) return VO_EINVAL;
   VO_REQUIRE(p->ctx, fb_max, "pipeline_get_klt_fb: null pointer");
   *fb_max = p->klt_fb;
+  return VO_OK;
+}
+
+// ---- the FAST + BRIEF tracker mode's settings (vo_hip.h, vo_pipeline_set_fast_brief): enqueue_fast_front and the chain's
+// matcher read them when a step is enqueued, so they hold from the next submit on ----
+
+int vo_pipeline_set_fast_brief(vo_pipeline* p, int fast_threshold, int brief_oriented, int brief_max_distance) {
+  if (!p) return VO_EINVAL;
+  vo_ctx* ctx = p->ctx;
+  VO_REQUIRE(ctx, p->cfg.tracker_mode == 3, "pipeline_set_fast_brief: FAST tracker mode only (the pipeline runs tracker_mode %d)",
+             p->cfg.tracker_mode);
+  VO_REQUIRE(ctx, fast_threshold >= 0 && fast_threshold <= 254, "pipeline_set_fast_brief: fast_threshold = %d, must be 0 (= 20) .. 254",
+             fast_threshold);
+  VO_REQUIRE(ctx, brief_oriented == 0 || brief_oriented == 1, "pipeline_set_fast_brief: brief_oriented = %d, must be 0 or 1",
+             brief_oriented);
+  VO_REQUIRE(ctx, brief_max_distance <= 256, "pipeline_set_fast_brief: brief_max_distance = %d, must be at most 256 (0 = 64, < 0 = no limit)",
+             brief_max_distance);
+  VO_REQUIRE(ctx, p->n_flight == 0, "pipeline_set_fast_brief: %d submitted step(s) not collected", p->n_flight);
+  p->fast_threshold = fast_threshold == 0 ? 20 : fast_threshold;
+  p->brief_oriented = brief_oriented;
+  p->brief_max_distance = brief_max_distance == 0 ? 64 : brief_max_distance;
+  return VO_OK;
+}
+
+int vo_pipeline_get_fast_brief(vo_pipeline* p, int32_t* fast_threshold, int32_t* brief_oriented, int32_t* brief_max_distance) {
+  if (!p) return VO_EINVAL;
+  VO_REQUIRE(p->ctx, fast_threshold && brief_oriented && brief_max_distance, "pipeline_get_fast_brief: null pointer");
+  *fast_threshold = p->fast_threshold;
+  *brief_oriented = p->brief_oriented;
+  *brief_max_distance = p->brief_max_distance;
   return VO_OK;
 }
 

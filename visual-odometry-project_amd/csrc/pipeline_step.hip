@@ -428,6 +428,27 @@ static int enqueue_harris_front(vo_pipeline* p, const vo_pipeline::flight_t& f, 
   return rc != VO_OK ? launch_error(p, err_buf, rc, "harris front", vo_last_error(p->det)) : VO_OK;
 }
 
+// FAST + BRIEF tracker mode: the new frame's FAST-9 corners (non-maximum suppression on, the n_keypoints strongest) and their
+// BRIEF-256 descriptors, on the detection stream; slot f.b.  All sequences: one detection and one describe call (the
+// sequence is a grid dimension of every kernel).  The corner count of every sequence goes straight into the slot's frame
+// counts, which the describe kernel, the matcher and the regroup read where they lie: nothing comes back to the host.
+static int enqueue_fast_front(vo_pipeline* p, const vo_pipeline::flight_t& f, char* err_buf = nullptr) {
+  const vo_pipeline_config& c = p->cfg;
+  vo_ctx* det = p->det;
+  const int frame = f.next_idx;
+  bool wait_ok = hipStreamWaitEvent(det->stream, p->evImg[frame], 0) == hipSuccess;   // the frame's upload (tracker's stream)
+  if (wait_ok && p->n_pinned[frame] > 0) wait_ok = hipStreamWaitEvent(det->stream, p->evUp[frame], 0) == hipSuccess;   // (pinned)
+  if (!wait_ok) return launch_error(p, err_buf, VO_EHIP, "fast front", "hipStreamWaitEvent failed");
+  int rc = vo_fast_keypoints_batch_dev(det, p->img(0, frame), p->img_stride(), p->S, c.H, c.W, p->fast_threshold, 1, c.n_keypoints,
+                                       p->kp(0, f.b), p->det_stride() / 2, nullptr, p->frame_n(f.b, 0), nullptr);
+  if (rc == VO_OK)
+    rc = vo_brief_describe_batch_dev(det, p->img(0, frame), p->img_stride(), p->S, c.H, c.W, p->kp(0, f.b), p->det_stride() / 2,
+                                     p->frame_n(f.b, 0), c.n_keypoints, p->brief_oriented, p->frame_desc(f.b, 0),
+                                     (size_t)p->frame_rows * p->desc_row, nullptr);
+  if (rc == VO_OK && hipEventRecord(p->evPyr[f.b], det->stream) != hipSuccess) rc = VO_EHIP;
+  return rc != VO_OK ? launch_error(p, err_buf, rc, "fast front", vo_last_error(det)) : VO_OK;
+}
+
 // main-stream chain of a step in a descriptor mode: 2-NN + ratio + uniqueness against the current Features' descriptors
 // (sift.py:38-54), Matches regroup from the pair list (matches.py:26-212) with the descriptors following their
 // keypoints, then hypotheses and pose as in the KLT mode.  (q0, Sn): sequences q0 .. q0 + Sn - 1 (all of them, or one
@@ -438,7 +459,7 @@ static int enqueue_chain_desc(vo_pipeline* p, const vo_pipeline::flight_t& f, bo
   vo_ctx* ctx = p->ctx;
   const vo_pipeline_config& c = p->cfg;
   hipStream_t st = ctx->stream;
-  const bool harris = c.tracker_mode == 2;
+  const bool harris = c.tracker_mode == 2, fast = c.tracker_mode == 3;
   const size_t row = (size_t)p->desc_row, q = (size_t)q0;
   const vo_feat A = vo_feat_seq(p->F[f.fcur], q), B = vo_feat_seq(p->F[1 - f.fcur], q);
   const uint8_t* descA = p->fdesc(f.fcur, q0);
@@ -457,8 +478,13 @@ static int enqueue_chain_desc(vo_pipeline* p, const vo_pipeline::flight_t& f, bo
     VO_TRY(vo_check_launch(ctx, "sift_fit_kernel"));
   }
   const double ratio = c.match_ratio > 0.0 ? c.match_ratio : (harris ? 0.85 : 0.8);        // harris.py:255 / sift.py:49
-  VO_TRY(vo_match_u8_batch_dev(ctx, descA, (size_t)p->cap * row, &ctl->n, (int)(sizeof(vo_seq_ctl) / 4), p->cap, new_desc,
-                               (size_t)p->frame_rows * row, n_new, 1, p->frame_rows, Sn, ratio, pairs, n_pairs, p->desc_row));
+  if (fast)           // (Hamming distances, the ratio and the distance limit: vo/features/fast.py's defaults, 0.8 and 64)
+    VO_TRY(vo_match_hamming_batch_dev(ctx, descA, (size_t)p->cap * row, &ctl->n, (int)(sizeof(vo_seq_ctl) / 4), p->cap, new_desc,
+                                      (size_t)p->frame_rows * row, n_new, 1, p->frame_rows, Sn, p->desc_row, ratio,
+                                      p->brief_max_distance, pairs, n_pairs));
+  else
+    VO_TRY(vo_match_u8_batch_dev(ctx, descA, (size_t)p->cap * row, &ctl->n, (int)(sizeof(vo_seq_ctl) / 4), p->cap, new_desc,
+                                 (size_t)p->frame_rows * row, n_new, 1, p->frame_rows, Sn, ratio, pairs, n_pairs, p->desc_row));
   const double* new_kp = p->d_newkp;
   vo_pairs_batch bt;
   bt.pairs = (size_t)p->cap * 2;
@@ -467,7 +493,7 @@ static int enqueue_chain_desc(vo_pipeline* p, const vo_pipeline::flight_t& f, bo
   bt.n2 = 1;
   bt.debug_fault_every = debug_fault_every > 0 ? debug_fault_every : 0;
   bt.par = (int)(f.k & 1);
-  if (harris) {
+  if (harris || fast) {
     new_kp = p->kp(q0, f.b);           // the detector's keypoints are float64 pairs already
     bt.new_kp = p->det_stride();
   } else {
@@ -519,6 +545,7 @@ void worker_main(vo_pipeline* p) {
     const vo_pipeline::flight_t j = p->jobs[seen & 3];
     const int rc = p->cfg.tracker_mode == 1   ? enqueue_sift(p, j, p->worker_err)
                    : p->cfg.tracker_mode == 2 ? enqueue_harris_front(p, j, p->worker_err)
+                   : p->cfg.tracker_mode == 3 ? enqueue_fast_front(p, j, p->worker_err)
                                               : enqueue_detection(p, j.next_idx, j.b, false, p->worker_err);
     if (rc != VO_OK) p->worker_rc = rc;
     ++seen;
@@ -598,8 +625,8 @@ static int flush_desc_chains(vo_pipeline* p, int must_reach = -1) {
     }
     VO_TRY(worker_check(p));
     for (int q = 0; q < p->S; ++q) VO_TRY(ensure_raws(p, q));
-    // (the test hook in the Harris mode only: the SIFT mode's chain never had it)
-    VO_TRY(enqueue_chain_desc(p, f, false, p->cfg.tracker_mode == 2 ? p->cfg.debug_fault_every : 0, 0, p->S, f.seq));
+    // (the test hook in the Harris and FAST modes only: the SIFT mode's chain never had it)
+    VO_TRY(enqueue_chain_desc(p, f, false, p->cfg.tracker_mode >= 2 ? p->cfg.debug_fault_every : 0, 0, p->S, f.seq));
     --p->desc_chains_pending;
   }
   return VO_OK;
@@ -645,15 +672,15 @@ int vo_pipeline_submit(vo_pipeline* p, int prev_idx, int next_idx) {
     // main-stream chain (its SIFT launches are made by now), so the two threads' launches overlap across frames.
     // Two threads make the launches, a frame each: even flights' go to the worker, odd flights' are made here (each
     // thread on its own SIFT context, so that two frames' chains also run side by side on the GPU).
-    if (p->threads_budget >= 2 && ((f.k & 1) == 0 || c.tracker_mode == 2)) {      // (harris: one detection context, the worker's)
+    if (p->threads_budget >= 2 && ((f.k & 1) == 0 || c.tracker_mode >= 2)) {      // (harris, fast: one detection context, the worker's)
       const unsigned my = p->job_posted.load(std::memory_order_relaxed);
       if ((int)(p->job_done.load(std::memory_order_acquire) - my) >= 0) sync_prof(p);   // (idle worker: its context's flags are ours)
       f.front_job = post_job(p, f);
     } else {
       copy_prof((f.k & 1) ? p->det : p->trk, ctx);          // (budget 1: both contexts are this thread's)
-      if (c.tracker_mode == 2) {
+      if (c.tracker_mode >= 2) {
         copy_prof(p->det, ctx);
-        VO_TRY(enqueue_harris_front(p, f));
+        VO_TRY(c.tracker_mode == 2 ? enqueue_harris_front(p, f) : enqueue_fast_front(p, f));
       } else {
         VO_TRY(enqueue_sift(p, f));
       }

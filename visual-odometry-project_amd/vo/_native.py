@@ -231,6 +231,8 @@ _SIGS = {
     "vo_brief_pattern": (_i, [_vp]),
     "vo_match_hamming_knn2": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "vo_hamming_knn2_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "vo_brief_describe_batch_dev": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp]),
+    "vo_match_hamming_batch_dev": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _i, _i, _i, _i, _d, _i, _vp, _vp]),
     "vo_match_hamming_ratio": (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _vp, _vp]),
     "vo_fast_score": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "vo_fast_keypoints": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
@@ -305,6 +307,8 @@ _SIGS = {
     "vo_pipeline_prepare": (_i, [_vp, _i]),
     "vo_pipeline_set_klt_fb": (_i, [_vp, _d]),
     "vo_pipeline_get_klt_fb": (_i, [_vp, _vp]),
+    "vo_pipeline_set_fast_brief": (_i, [_vp, _i, _i, _i]),
+    "vo_pipeline_get_fast_brief": (_i, [_vp, _vp, _vp, _vp]),
     "vo_host_alloc": (_i, [_vp, C.c_size_t, C.POINTER(C.c_void_p)]),
     "vo_host_free": (_i, [_vp, _vp]),
     "vo_gray_from_bgr": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -579,6 +583,15 @@ class Context:
         self._chk(self._lib.vo_brief_describe_dev(self._h, C.c_void_p(d_img), int(H), int(W), C.c_void_p(d_kp), int(N),
                                                   1 if oriented else 0, C.c_void_p(d_desc), C.c_void_p(d_bin)))
 
+    def brief_describe_batch_dev(self, d_imgs, img_stride, S, H, W, d_kp_xy, xy_stride, d_n, N, oriented, d_desc, desc_stride,
+                                 d_bin=None):
+        """vo_brief_describe_batch_dev on device pointers (alloc / to_device): image q describes its first
+        min(max(d_n[q], 0), N) rows; enqueued on the context's stream, nothing read back."""
+        self._chk(self._lib.vo_brief_describe_batch_dev(self._h, C.c_void_p(d_imgs), int(img_stride), int(S), int(H), int(W),
+                                                        C.c_void_p(d_kp_xy), int(xy_stride), C.c_void_p(d_n), int(N),
+                                                        1 if oriented else 0, C.c_void_p(d_desc), int(desc_stride),
+                                                        C.c_void_p(d_bin) if d_bin else None))
+
     def brief_pattern(self):
         """The (30, 256, 4) int8 table (ax, ay, bx, by) the library was built with (vo_brief_pattern)."""
         out = np.empty((30, 256, 4), np.int8)
@@ -609,6 +622,15 @@ class Context:
     def hamming_knn2_dev(self, d_q, nq, d_t, nt, row_bytes, d_best, d_dist):
         self._chk(self._lib.vo_hamming_knn2_dev(self._h, C.c_void_p(d_q), int(nq), C.c_void_p(d_t), int(nt), int(row_bytes),
                                                 C.c_void_p(d_best), C.c_void_p(d_dist)))
+
+    def match_hamming_batch_dev(self, d_q, q_stride, d_nq, nq_stride, cap_q, d_t, t_stride, d_nt, nt_stride, cap_t, S, row_bytes,
+                                ratio, max_dist, d_pairs, d_npairs):
+        """vo_match_hamming_batch_dev on device pointers: match_hamming_ratio's rule for S sequences whose counts lie in
+        device memory, enqueued on the context's stream."""
+        self._chk(self._lib.vo_match_hamming_batch_dev(self._h, C.c_void_p(d_q), int(q_stride), C.c_void_p(d_nq), int(nq_stride),
+                                                       int(cap_q), C.c_void_p(d_t), int(t_stride), C.c_void_p(d_nt),
+                                                       int(nt_stride), int(cap_t), int(S), int(row_bytes), float(ratio),
+                                                       int(max_dist), C.c_void_p(d_pairs), C.c_void_p(d_npairs)))
 
     def match_hamming_ratio(self, q, t, ratio, max_dist=-1):
         """(n, 2) int64 pairs (query, train) in query order: ratio test on the Hamming distances, the distance limit

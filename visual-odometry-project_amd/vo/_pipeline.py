@@ -57,7 +57,8 @@ class Pipeline:
                  max_iterations=1000, seed=2023, refine_iters=0, feature_cap=0, bearing_threshold=0.0075,
                  redetect_fraction=0.8, debug_fault_every=0, redetect_start_pose="identity", sequences=1,
                  detect_margin=0.01, debug_never_detect=0, detect_losses=2.5, tracker="klt", sift_cap=0, match_ratio=0.0,
-                 detector="harris", st_quality=0.0, st_min_distance=0.0, st_block=0, track_ids=False):
+                 detector="harris", st_quality=0.0, st_min_distance=0.0, st_block=0, track_ids=False,
+                 fast_threshold=0, brief_oriented=False, brief_max_distance=0):
         from vo import _native
         self.ctx = ctx
         self.cfg = _native.PipelineConfig()
@@ -79,7 +80,8 @@ class Pipeline:
         c.detect_margin = float(detect_margin)       # < 0: the detector runs on every frame
         c.debug_never_detect = int(debug_never_detect)
         c.detect_losses = float(detect_losses)
-        c.tracker_mode = {"klt": 0, "sift": 1, "harris": 2}[tracker]         # src/vo/features/tracker.py:54-63
+        # src/vo/features/tracker.py:54-63; "fast": the project's FAST-9 + BRIEF-256 front end (vo/features/fast.py)
+        c.tracker_mode = {"klt": 0, "sift": 1, "harris": 2, "fast": 3}[tracker]
         c.sift_cap = int(sift_cap)   # SIFT mode: -1 every keypoint (<= feature_cap), 0 n_keypoints, 1..4000 the strongest
         c.match_ratio = float(match_ratio)
         # KLT mode's re-detect: "harris" (response + NMS, exactly n_keypoints) or "shi-tomasi" (the reference's
@@ -104,6 +106,15 @@ class Pipeline:
         self._pinned_src = {}
         ctx._pipelines.add(self)
         self.cap = ctx._lib.vo_pipeline_feature_cap(self._h)
+        if tracker == "fast":
+            # FASTBRIEFDetector's settings (0 / False / 0: its defaults -- threshold 20, not oriented, distance limit 64;
+            # brief_max_distance < 0: no limit); ignored in the other modes.  A refused value closes the pipeline again.
+            try:
+                ctx._chk(ctx._lib.vo_pipeline_set_fast_brief(self._h, int(fast_threshold), 1 if brief_oriented else 0,
+                                                             int(brief_max_distance)))
+            except Exception:
+                self.close()
+                raise
         self.seed(np.random.default_rng(seed))
 
     def close(self):
@@ -208,16 +219,23 @@ class Pipeline:
 
     def set_state(self, idx, features, curr_pose, prev_pose=None, num_features=None, seq=0):
         """Hands over `features` (a vo.primitives.Features: the current frame's, e.g. after the bootstrap) and
-        State's poses (4x4 camera-to-world) for frame slot `idx`."""
+        State's poses (4x4 camera-to-world) for frame slot `idx`.  In the descriptor tracker modes ("sift", "harris",
+        "fast") features.descriptors goes with them: n rows of 128, 361 or (fast: BRIEF-256 bytes) 32 whole numbers 0..255."""
         n = features.length
+        desc = None
+        if self.tracker in ("sift", "harris", "fast"):       # ("fast": n x 32 BRIEF-256 bytes)
+            desc = np.asarray(features.descriptors)
+            if desc.size != n * self._desc_len():            # (before anything is handed over)
+                raise ValueError("set_state: %d descriptor values for %d features of %d each (tracker %r)"
+                                 % (desc.size, n, self._desc_len(), self.tracker))
+            desc = _c(desc.reshape(n, self._desc_len()), np.float32)
         keep, args = self._state_args(features, curr_pose, prev_pose, num_features)
         self.ctx._chk(self.ctx._lib.vo_pipeline_set_state_seq(self._h, int(seq), int(idx), *args))
-        if self.tracker in ("sift", "harris"):
-            desc = _c(np.asarray(features.descriptors).reshape(n, self._desc_len()), np.float32)
+        if desc is not None:
             self.ctx._chk(self.ctx._lib.vo_pipeline_set_descriptors_seq(self._h, int(seq), _ptr(desc), n))
 
     def _desc_len(self):
-        return 128 if self.tracker == "sift" else 361
+        return {"sift": 128, "fast": 32}.get(self.tracker, 361)
 
     # ---- lanes: many recordings through one pipeline ----
     def set_camera(self, K, seq, Kinv=None):
@@ -328,7 +346,7 @@ class Pipeline:
 
     def get_descriptors(self, seq=0):
         """The descriptors the current Features of sequence `seq` carry (descriptor tracker modes; nothing in flight):
-        n x 361 (Harris) or n x 128 (SIFT) float32, whole numbers, in feature order -- what set_state handed over, regrouped
+        n x 361 (Harris), n x 128 (SIFT) or n x 32 (FAST: the BRIEF-256 bytes) float32, whole numbers, in feature order -- what set_state handed over, regrouped
         with the keypoints since."""
         n = C.c_int32()
         desc = np.empty((self.cap, self._desc_len()), np.float32)
